@@ -13,6 +13,8 @@ events/s is reported next to it.  For N > 1 (one process per GPU: `bench.py --gp
 are all-reduced by RCCL every step, value = sum over ranks INCLUDING the reconciliation of the GPU-local item tables every
 sync_every steps (the bare step is reported next to it as value_step_only).  No torch anywhere: the ranks meet through gru4rec_amd/launch.py
 (file rendezvous of the RCCL unique id) and synchronise through the communicator (g4r_comm_max_i64).
+`--dump-outputs DIR` writes what the timed steps computed (losses, then parameters and hidden state after the last one) as .npy files;
+the inputs depend on the arguments alone, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -144,9 +146,12 @@ def make_plan(cfg, n_steps, rank, nranks, seed=42, session_items=0):
     n_sessions = int(n_steps * B / 2.6) + 8 * B           # ~2.9 scoring events per session
     n_items = min(cfg['n_items'], session_items) if session_items > 0 else cfg['n_items']
     # the generator is deterministic; its output for a 10 M-item catalogue takes ~20 s of host time, so consecutive invocations on
-    # one box (profile passes) share it through a file in the temp directory
+    # one box (profile passes) share it through a file in the temp directory.  The file name carries a digest of the generator's
+    # source: a checkout whose generator differs never reads another checkout's sessions
+    import hashlib
     import tempfile
-    cache = os.path.join(tempfile.gettempdir(), 'g4r_synth_%d_%d_%d_v1.npz' % (n_sessions * nranks, n_items, seed))
+    gen = hashlib.sha1(open(synth.__file__, 'rb').read()).hexdigest()[:12]
+    cache = os.path.join(tempfile.gettempdir(), 'g4r_synth_%d_%d_%d_%s.npz' % (n_sessions * nranks, n_items, seed, gen))
     if os.path.exists(cache):
         z = np.load(cache)
         sizes, ids, items_all = z['sizes'], z['ids'], z['items_all']
@@ -263,6 +268,46 @@ def cpu_baseline(cfg, plan, support, budget_s=15.0):
                 events_per_s=best[2] / best[3], host_cpus=os.cpu_count())
 
 
+DUMP_BYTES = 64 * 10 ** 6 - (1 << 16)      # --dump-outputs: the most it writes, less room for the .npy headers
+DUMP_SEED = 20240917       # --dump-outputs: the item rows kept when the item table does not fit
+
+
+def dump_outputs(m, cfg, plan, t_last, losses, out_dir):
+    """What the timed steps computed, as a caller of the step receives it: the loss of every timed step (`losses`, the last entry is
+    step t_last's), and the model after step t_last -- per layer i the GRU weights `Wx_i` `Wh_i` `Wrz_i` `Bh_i` and the hidden state
+    `H_i`, the item table `Wy` and item biases `By`.  Written as out_dir/<name>.npy, float32.  When everything would exceed
+    DUMP_BYTES, `Wy` / `By` keep only the rows step t_last gathered as inputs / targets plus a fixed seeded sample of the others;
+    `Wy_rows` (float64) names them.  Returns {'dir', 'bytes', 'arrays': {name: shape}} for the result line."""
+    L, B, I = cfg['layers'], cfg['batch_size'], cfg['n_items']
+    arrs = {'losses': np.asarray(losses, dtype=np.float32)}
+    for i, D in enumerate(L):
+        n_in = L[i - 1] if i > 0 else L[-1]      # constrained embedding: layer 0 reads rows of Wy
+        arrs['Wx_%d' % i] = m.get_param('Wx', (n_in, 3 * D), i)
+        arrs['Wh_%d' % i] = m.get_param('Wh', (D, D), i)
+        arrs['Wrz_%d' % i] = m.get_param('Wrz', (D, 2 * D), i)
+        arrs['Bh_%d' % i] = m.get_param('Bh', (3 * D,), i)
+        arrs['H_%d' % i] = m.get_param('H', (B, D), i)
+    Wy = m.get_param('Wy', (I, L[-1]))
+    By = m.get_param('By', (I,))
+    room = DUMP_BYTES - sum(a.nbytes for a in arrs.values())
+    if Wy.nbytes + By.nbytes <= room:
+        arrs['Wy'], arrs['By'] = Wy, By
+    else:
+        n_rows = max(0, room // (Wy.shape[1] * 4 + 4 + 8))
+        last = np.unique(np.concatenate([plan['in_idx'][t_last], plan['out_idx'][t_last]]).astype(np.int64))[:n_rows]
+        others = np.setdiff1d(np.arange(I, dtype=np.int64), last, assume_unique=True)
+        pick = np.random.RandomState(DUMP_SEED).choice(others, size=n_rows - len(last), replace=False)
+        rows = np.sort(np.concatenate([last, pick]))
+        arrs['Wy_rows'] = rows.astype(np.float64)
+        arrs['Wy'], arrs['By'] = Wy[rows], By[rows]
+    del Wy, By
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {'dir': out_dir, 'bytes': int(sum(a.nbytes for a in arrs.values())),
+            'arrays': {name: list(a.shape) for name, a in arrs.items()}}
+
+
 def large_catalogue_legs(timeout=150):
     """`bench.py --config cfg4m` without / with --defer in child processes -> {'immediate': {...}, 'deferred': {...}} (mini-batches/s, us per
     step, the update launch, and for the deferred run the flush launch priced on the bytes it moves)."""
@@ -311,7 +356,12 @@ def main():
                     '2 M-item catalogue, without / with deferred row updates) that fill roofline_gather_scatter.deferred_flush and large_catalogue')
     ap.add_argument('--long-steps', type=int, default=2000, help='a run of --steps below this also times that many steps behind the timed region and '
                     'reports them as "long_run" (a 20-step window is ~1 ms; 0 = off)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what they computed -- the losses of the '
+                    'timed steps, the parameters and hidden state after the last one -- as DIR/<name>.npy (float32; at most 64 MB, a fixed '
+                    'sample of item rows beyond that), rank 0 only, so that two builds can be compared output for output')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     cfg = CONFIGS[args.config]
     from gru4rec_amd import launch
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -375,6 +425,10 @@ def main():
         rank_dts = launch.gather_us(m, rank, world, dt_own)
         dt = max(rank_dts)                        # MAX over ranks
     losses = m.get_losses(args.warmup, args.steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # read back before any later step (long run, per-kernel passes) moves the model on
+        dumped = dump_outputs(m, cfg, plan, args.warmup + args.steps - 1, losses, args.dump_outputs)
     long_run = None
     if n_long:
         # the same measurement over >= 2000 steps right behind the timed region (the driver's --steps 20 is a ~1 ms window)
@@ -409,6 +463,8 @@ def main():
         'loss_finite': bool(np.isfinite(losses).all()),
     }
     out['config']['defer_updates'] = bool(args.defer)
+    if dumped:
+        out['dump_outputs'] = dumped
     if long_run:
         out['long_run'] = long_run
     if sync_in_timed:

@@ -4,12 +4,17 @@
 1. The REFERENCE's own source (on the Theano stand-in) trains a small model and writes it with its own `savemodel`
    -> tests/golden/checkpoint/ref_checkpoint.pickle, plus the scores its `predict_next_batch` gives for two batches
    -> tests/golden/checkpoint/ref_checkpoint_pred.npz.
-2. Reverse direction, checked here because it needs /root/reference: the product class loads that pickle, writes it
-   again with ITS `savemodel`, and the reference's `loadmodel` + `predict_next_batch` must reproduce the same scores.
+2. Reverse direction, checked here because it needs the reference source: the product class loads that pickle, writes it
+   again with ITS `savemodel`, and the reference's `loadmodel` + `predict_next_batch` must reproduce the same scores.  What the
+   reference's environment resolved while reading the product-written files -- every global, and every attribute a `getattr` in
+   the pickle asked of the reference's objects (bound methods pickle that way) -- is recorded in
+   tests/golden/checkpoint/ref_reader.npz: tests/test_checkpoint.py holds today's product-written files to it.
 Run:  python oracle/make_checkpoint_fixture.py
 """
 import os
+import pickle
 import sys
+import tempfile
 
 import numpy as np
 
@@ -29,6 +34,27 @@ def predictions(gru, ids):
     p1 = gru.predict_next_batch(np.array([1, 2, 3, 4]), ids[[0, 3, 5, 7]], None, batch=4)
     p2 = gru.predict_next_batch(np.array([1, 2, 9, 4]), ids[[2, 3, 1, 6]], None, batch=4)
     return p1.values.astype(np.float32), p2.values.astype(np.float32)
+
+
+def reader_record(paths):
+    """(globals as 'module name', getattr attribute names) the reference's environment resolves reading the pickles `paths`:
+    the reference's `gru4rec` module must be loaded under that name (ref_loader.load)."""
+    seen, attrs = set(), set()
+
+    def rec_getattr(obj, name, *default):
+        attrs.add(name)
+        return getattr(obj, name, *default)
+
+    class Recorder(pickle.Unpickler):
+        def find_class(self, module, name):
+            seen.add('%s %s' % (module, name))
+            if (module, name) == ('builtins', 'getattr'):
+                return rec_getattr
+            return super().find_class(module, name)
+    for p in paths:
+        with open(p, 'rb') as f:
+            Recorder(f).load()
+    return sorted(seen), sorted(attrs)
 
 
 def main():
@@ -51,14 +77,23 @@ def main():
     from gru4rec_amd.gru4rec import GRU4Rec
     sys.modules['gru4rec'] = sys.modules['gru4rec_amd.gru4rec']
     mine = GRU4Rec.loadmodel(path)
-    tmp = os.path.join('/tmp', 'g4r_product_checkpoint.pickle')
+    tmp = os.path.join(tempfile.mkdtemp(prefix='g4r_ckpt_'), 'product_checkpoint.pickle')
     mine.savemodel(tmp)                                       # the product's writer
+    tmp_opt = tmp + '.opt'                                    # ... and a file with the optimizer-state extras (test_checkpoint.py)
+    mine.optimizer_state = {'arrays': {('acc_Wy', 0): np.ones((mine.n_items, 12), dtype=np.float32)}, 'global_step': 7, 'refills': 1}
+    mine.epochs_done = 3
+    with open(tmp_opt, 'wb') as fh:
+        pickle.dump(mine, fh)
     _, ref2, _ = ref_loader.load()
     back = ref2.GRU4Rec.loadmodel(tmp)                        # the reference's own reader
     q1, q2 = predictions(back, ids)
     np.testing.assert_array_equal(q1, p1)
     np.testing.assert_array_equal(q2, p2)
+    assert ref2.GRU4Rec.loadmodel(tmp_opt).epochs_done == 3
+    seen, attrs = reader_record([tmp, tmp_opt])
+    np.savez_compressed(os.path.join(OUT, 'ref_reader.npz'), globals=np.array(seen), getattrs=np.array(attrs))
     print('reference -> product -> reference round trip reproduces the reference predictions bit for bit')
+    print('the reference resolved %d globals and %d attributes reading the product\'s files' % (len(seen), len(attrs)))
     print('wrote', path, os.path.getsize(path), 'bytes')
 
 

@@ -48,27 +48,65 @@ def test_product_pickle_names_the_reference_class(tmp_path):
     np.testing.assert_array_equal(h.Wy, g.Wy)
 
 
-def test_reference_reads_product_pickle_live(tmp_path):
-    """Only where /root/reference exists: the reference's own loadmodel + predict_next_batch on a product-written pickle."""
-    from oracle import ref_loader
-    if not ref_loader.available():
-        pytest.skip('/root/reference not present')
-    import sys
+class _ForeignReader(pickle.Unpickler):
+    """Reads a checkpoint the way a process without this package does: `gru4rec.GRU4Rec` and the classes nested in it resolve to
+    bare classes that only receive the pickled state, `getattr(obj, name)` -- how a bound method pickles -- to the name alone.
+    Records what the file asks of its reader, for comparison with what the reference's environment resolved
+    (tests/golden/checkpoint/ref_reader.npz, written by oracle/make_checkpoint_fixture.py with the reference's own loadmodel)."""
+    def __init__(self, f):
+        super().__init__(f)
+        self.globals, self.getattrs = set(), set()
+
+    def find_class(self, module, name):
+        self.globals.add('%s %s' % (module, name))
+        if module == 'gru4rec':
+            return type(name.split('.')[-1], (), {})
+        if (module, name) == ('builtins', 'getattr'):
+            return lambda obj, attr, *default: self.getattrs.add(attr) or attr
+        return super().find_class(module, name)
+
+
+def _read_as_the_reference(path):
+    """The state a reader without this package gets from `path`, after checking that the file asks no more of the reference's
+    environment than it resolved when its own loadmodel read a product-written file."""
+    with open(path, 'rb') as f:
+        r = _ForeignReader(f)
+        obj = r.load()
+    rec = np.load(os.path.join(GOLD, 'ref_reader.npz'), allow_pickle=False)
+    known = set(rec['globals'])
+    assert {g for g in r.globals if g.startswith('gru4rec ')} <= known, 'names the reference module does not provide'
+    assert r.getattrs <= set(rec['getattrs']), 'methods the reference class does not have'
+    top = {g.split('.')[0].split(' ')[0] for g in known}
+    assert {g.split('.')[0].split(' ')[0] for g in r.globals} <= top, 'modules the reference does not import'
+    assert type(obj).__name__ == 'GRU4Rec'
+    return obj.__dict__
+
+
+def test_reference_reads_product_pickle(tmp_path):
+    """A product-written pickle is what the reference's loadmodel + predict_next_batch read (gru4rec.py:665-781), without the
+    reference: the file asks the reader for nothing the reference's environment did not resolve when the fixture generator
+    loaded such a file with the reference's own loadmodel, and the reference's prediction -- restated by the NumPy oracle on the
+    state as read -- reproduces the scores the reference gave (ref_checkpoint_pred.npz)."""
+    from oracle.model import OracleGRU4Rec
     g = GRU4Rec.loadmodel(PICKLE)
     f = str(tmp_path / 'm.pickle')
     g.savemodel(f)
-    saved = sys.modules.get('gru4rec')
+    st = _read_as_the_reference(f)
+    want = np.load(PRED, allow_pickle=False)
+    assert st['final_activation'] == 'execute' and st['loss_function'] == 'bpr_max' and st['hidden_activation'] == 'tanh'
+    state = np.random.get_state()
     try:
-        _, ref, _ = ref_loader.load()
-        back = ref.GRU4Rec.loadmodel(f)
-        want = np.load(PRED, allow_pickle=False)
-        ids = np.array(list(back.itemidmap.index))
-        p1 = back.predict_next_batch(np.array([1, 2, 3, 4]), ids[[0, 3, 5, 7]], None, batch=4)
-        np.testing.assert_array_equal(p1.values.astype(np.float32), want['pred1'])
+        o = OracleGRU4Rec(n_items=st['n_items'], layers=st['layers'], batch_size=4, loss=st['loss'], final_act=st['final_act'],
+                          hidden_act=st['hidden_act'], n_sample=0, constrained_embedding=st['constrained_embedding'],
+                          embedding=st['embedding'])
     finally:
-        ref_loader.unload()
-        if saved is not None:
-            sys.modules['gru4rec'] = saved
+        np.random.set_state(state)
+    o.E, o.Wy, o.By = st['E'], st['Wy'], np.asarray(st['By']).reshape(-1)
+    o.Wx, o.Wh, o.Wrz, o.Bh = list(st['Wx']), list(st['Wh']), list(st['Wrz']), list(st['Bh'])
+    ids = np.array(list(st['itemidmap'].index))
+    in_idx = st['itemidmap'][ids[[0, 3, 5, 7]]].values
+    yhat, _ = o.predict_step([np.zeros((4, D), dtype=np.float32) for D in st['layers']], in_idx)
+    np.testing.assert_allclose(yhat.T, want['pred1'], rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.gpu
@@ -148,15 +186,6 @@ def test_checkpoint_with_optimizer_state_keeps_the_reference_layout(tmp_path):
     h = GRU4Rec.loadmodel(f)
     assert h.epochs_done == 3 and h.optimizer_state['global_step'] == 7
     np.testing.assert_array_equal(h.Wy, g.Wy)
-    from oracle import ref_loader
-    if ref_loader.available():
-        import sys
-        saved = sys.modules.get('gru4rec')
-        try:
-            _, ref, _ = ref_loader.load()
-            back = ref.GRU4Rec.loadmodel(f)      # the reference's own loader accepts the file
-            assert back.epochs_done == 3
-        finally:
-            ref_loader.unload()
-            if saved is not None:
-                sys.modules['gru4rec'] = saved
+    back = _read_as_the_reference(f)      # what the reference's loader resolves is all the file asks for
+    assert back['epochs_done'] == 3
+    np.testing.assert_array_equal(back['Wy'], g.Wy)
