@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('G4R_LIB') or os.path.join(_HERE, 'libgru4rec_hip.so')   # G4R_LIB: developer override
 
 G4R_MAX_LAYERS = 8
+G4R_TOPK_MAX = 256      # largest k of g4r_recommend_step
 LOSS_IDS = {'cross-entropy': 0, 'bpr-max': 1, 'top1-max': 2, 'bpr': 3, 'top1': 4, 'xe_logit': 5}
 ACT_IDS = {'linear': 0, 'relu': 1, 'tanh': 2, 'leaky': 3, 'elu': 4, 'selu': 5, 'softmax': 6, 'softmax_logit': 7}
 ADAPT_IDS = {'adagrad': 0, 'rmsprop': 1, 'adadelta': 2, 'adam': 3, None: 4}
@@ -42,7 +43,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -95,6 +96,7 @@ def lib():
     L.g4r_predict_begin.argtypes = [vp, i32]
     L.g4r_predict_hidden.argtypes = [vp, u8p, i32, i32p, i32]
     L.g4r_predict_step.argtypes = [vp, i32p, i32, i32p, i64, f32p]
+    L.g4r_recommend_step.argtypes = [vp, i32p, i32, i32p, i64, i32, i32p, f32p]
     L.g4r_rank_targets.argtypes = [vp, i32p, i32, i64, i32, f32p]
     L.g4r_evaluate.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32p, i32, i32,
                                C.POINTER(C.c_double), C.POINTER(C.c_double), i64p]
@@ -364,6 +366,17 @@ class Model:
         _chk(lib().g4r_predict_step(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel,
                                     None if out is None else _f32(out)))
         return out
+
+    def recommend_step(self, in_idx, item_idx=None, k=20):
+        """The k best candidates of every row of the scores predict_step would return (g4r_recommend_step; same hidden-state
+        update): (cols int32[rows, k], scores float32[rows, k]); cols are positions in item_idx (item indices without it)."""
+        ii = np.ascontiguousarray(in_idx, dtype=np.int32)
+        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
+        n_sel = self.cfg.n_items if it is None else len(it)
+        cols = np.empty((len(ii), k), dtype=np.int32)
+        scores = np.empty((len(ii), k), dtype=np.float32)
+        _chk(lib().g4r_recommend_step(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k, _i32(cols), _f32(scores)))
+        return cols, scores
 
     def rank_targets(self, target_col, col_begin=0, mode='standard'):
         t = np.ascontiguousarray(target_col, dtype=np.int32)

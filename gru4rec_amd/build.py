@@ -35,7 +35,8 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            4: "round 3's stale-register pipeline of gemm_tile2k (tied wait operands in two branches): fails the ISA audit, so it is the "
               "one library built with audit=False",
            5: 'the 1 / nranks factor of the exact-replica joint update (REDUCE / MEAN forms) x 1.01',
-           6: 'the Adagrad step of ONE item row per step (the item of score column 0) x 1.5: a single wrong row must not pass'}
+           6: 'the Adagrad step of ONE item row per step (the item of score column 0) x 1.5: a single wrong row must not pass',
+           7: 'top-k selection (g4r_recommend_step) breaks equal scores by the HIGHER column'}
 
 
 def mutant_path(k):

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "g4r_eval_kernels.cuh"
+#include "g4r_topk_kernels.cuh"
 #include "g4r_sync_kernels.cuh"
 #include "g4r_micro_kernels.cuh"
 #include "g4r_wide_kernels.cuh"

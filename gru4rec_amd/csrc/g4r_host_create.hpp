@@ -465,6 +465,8 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
     HIPCHK(hipFuncSetAttribute((const void*)k_update<2, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
     HIPCHK(hipFuncSetAttribute((const void*)k_score_store, hipFuncAttributeMaxDynamicSharedMemorySize, big));
     HIPCHK(hipFuncSetAttribute((const void*)k_score_count, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+    HIPCHK(hipFuncSetAttribute((const void*)k_topk_fused, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+    HIPCHK(hipFuncSetAttribute((const void*)k_topk_stored, hipFuncAttributeMaxDynamicSharedMemorySize, big));
 #define G4R_LOSS_ATTR(L, S)                                                                                                    \
     if (!L) HIPCHK(hipFuncSetAttribute((const void*)k_loss_rows<false, S, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, big)); \
     HIPCHK(hipFuncSetAttribute((const void*)k_loss_rows<L, S, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, big))

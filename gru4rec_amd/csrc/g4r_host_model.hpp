@@ -104,6 +104,10 @@ struct g4r_model {
     float *p_scores = nullptr, *p_ranks = nullptr;
     int* p_cnt = nullptr;                        // [pbatch][2] streamed (greater, equal) counts of the evaluation
     int64_t p_scores_cap = 0, p_items_cap = 0, p_nsel = 0, p_ldo = 0;
+    uint2* p_topk = nullptr;                     // [rows][ranges][k] per-range lists of g4r_recommend_step (k_topk_range)
+    int* p_tcols = nullptr;                      // [rows][k] its result
+    float* p_tscores = nullptr;
+    int64_t p_topk_cap = 0, p_tout_cap = 0;
     unsigned tie_ctr = 0;                        // evaluation step counter of the 'tiebreaking' noise stream
     // rccl
     ncclComm_t comm = nullptr;
@@ -154,6 +158,8 @@ static void dfree(g4r_model* m, void* p) {
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static constexpr auto k_score_store = k_score_all<32, false>;     // scores -> memory
 static constexpr auto k_score_count = k_score_all<32, true>;      // scores compared with the row's target on the fly
+static constexpr auto k_topk_fused = k_topk_range<false>;         // scores selected as they are produced (element-wise final activation)
+static constexpr auto k_topk_stored = k_topk_range<true>;         // selection over p_scores (softmax / softmax_logit)
 
 static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 // dynamic LDS of the tile-GEMM kernels (g4r_gemm.cuh)

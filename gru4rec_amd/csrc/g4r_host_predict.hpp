@@ -1,5 +1,5 @@
 // g4r_host_predict.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
-// instantiated there).  Holds: prediction and evaluation: g4r_predict_*, g4r_rank_targets, g4r_evaluate.
+// instantiated there).  Holds: prediction and evaluation: g4r_predict_*, g4r_rank_targets, g4r_recommend_step, g4r_evaluate.
 // ------------------------------------------------------------------------------------------------ prediction
 int g4r_predict_begin(g4r_model* m, int32_t batch) {
     if (!m || batch < 1) return fail("bad batch");
@@ -66,28 +66,35 @@ int g4r_predict_hidden(g4r_model* m, const uint8_t* zero_mask, int32_t n_mask, c
 struct StreamRank;
 static int predict_forward(g4r_model* m, const int* d_in_idx, int mrows, const int* d_items, int64_t n_sel, const StreamRank* stream);
 
-int g4r_predict_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
-                     float* out_scores) {
+// validation and upload shared by g4r_predict_step / g4r_recommend_step: input items -> p_in, candidates -> p_items; *n_sel is
+// set to n_items when item_idx is NULL
+static int predict_inputs(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t* n_sel) {
     if (!m || !in_idx) return fail("null argument");
     if (!m->pbatch) return fail("g4r_predict_begin first");
     if (mrows < 1 || mrows > m->pbatch) return fail("mrows out of range");
     HIPCHK(hipSetDevice(m->cfg.device));
     DevModel& d = m->dm;
-    if (!item_idx) n_sel = d.n_items;
-    if (n_sel < 1) return fail("n_sel must be positive");
+    if (!item_idx) *n_sel = d.n_items;
+    if (*n_sel < 1) return fail("n_sel must be positive");
     for (int i = 0; i < mrows; ++i)
         if (in_idx[i] < 0 || in_idx[i] >= d.n_items) return fail("input item index out of range");
     HIPCHK(hipMemcpyAsync(m->p_in, in_idx, mrows * sizeof(int), hipMemcpyHostToDevice, m->stream));
     if (item_idx) {
-        if (n_sel > m->p_items_cap) {
+        if (*n_sel > m->p_items_cap) {
             dfree(m, m->p_items);
-            if (dalloc(m, &m->p_items, (size_t)n_sel, false)) return -1;
-            m->p_items_cap = n_sel;
+            if (dalloc(m, &m->p_items, (size_t)*n_sel, false)) return -1;
+            m->p_items_cap = *n_sel;
         }
-        for (int64_t i = 0; i < n_sel; ++i)
+        for (int64_t i = 0; i < *n_sel; ++i)
             if (item_idx[i] < 0 || item_idx[i] >= d.n_items) return fail("item index out of range");
-        HIPCHK(hipMemcpyAsync(m->p_items, item_idx, n_sel * sizeof(int), hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(m->p_items, item_idx, *n_sel * sizeof(int), hipMemcpyHostToDevice, m->stream));
     }
+    return 0;
+}
+
+int g4r_predict_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
+                     float* out_scores) {
+    if (predict_inputs(m, in_idx, mrows, item_idx, &n_sel)) return -1;
     if (predict_forward(m, m->p_in, mrows, item_idx ? (const int*)m->p_items : (const int*)nullptr, n_sel, nullptr)) return -1;
     const int64_t ldo = m->p_ldo;
     if (out_scores) {
@@ -115,22 +122,10 @@ int g4r_rank_targets(g4r_model* m, const int32_t* target_col, int32_t mrows, int
     return 0;
 }
 
-// forward GRU + scores of `mrows` rows whose input items sit on the device (shared by g4r_predict_step / g4r_evaluate)
-// stream = nullptr: scores of all candidates go to p_scores (final activation applied).  Otherwise (evaluation with an
-// element-wise final activation) nothing is materialised: stream->tgt lists the target item of every row; their scores are
-// computed first (mrows x mrows tile, diagonal used), then every candidate tile is compared with them on the fly and
-// p_ranks receives the ranks (stream->mode, candidates from column stream->col_begin on).
-struct StreamRank { const int* tgt; long long col_begin; int mode; const int* tie_col; unsigned tie_ctr; };
-static int predict_forward(g4r_model* m, const int* d_in_idx, int mrows, const int* d_items, int64_t n_sel, const StreamRank* stream) {
+// forward GRU of `mrows` prediction rows (input items on the device): every layer's hidden state advances one step and the top
+// layer's output is left in phout[n_layers - 1] (shared by predict_forward / g4r_recommend_step)
+static void predict_gru(g4r_model* m, const int* d_in_idx, int mrows) {
     DevModel& d = m->dm;
-    const int64_t ldo = stream ? ((mrows + 3) & ~3) : ((n_sel + 3) & ~3LL);
-    const int64_t need = stream ? (int64_t)m->pbatch * ((m->pbatch + 3) & ~3) : (int64_t)m->pbatch * ldo;
-    if (need > m->p_scores_cap) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(m, m->p_scores);
-        if (dalloc(m, &m->p_scores, (size_t)need, false)) return -1;
-        m->p_scores_cap = need;
-    }
     for (int l = 0; l < d.n_layers; ++l) {
         GruFwdPredict pa;
         pa.in_idx = (GP(const int))d_in_idx;
@@ -156,6 +151,25 @@ static int predict_forward(g4r_model* m, const int* d_in_idx, int mrows, const i
         }
     }
     m->ppar ^= 1;
+}
+
+// forward GRU + scores of `mrows` rows whose input items sit on the device (shared by g4r_predict_step / g4r_evaluate)
+// stream = nullptr: scores of all candidates go to p_scores (final activation applied).  Otherwise (evaluation with an
+// element-wise final activation) nothing is materialised: stream->tgt lists the target item of every row; their scores are
+// computed first (mrows x mrows tile, diagonal used), then every candidate tile is compared with them on the fly and
+// p_ranks receives the ranks (stream->mode, candidates from column stream->col_begin on).
+struct StreamRank { const int* tgt; long long col_begin; int mode; const int* tie_col; unsigned tie_ctr; };
+static int predict_forward(g4r_model* m, const int* d_in_idx, int mrows, const int* d_items, int64_t n_sel, const StreamRank* stream) {
+    DevModel& d = m->dm;
+    const int64_t ldo = stream ? ((mrows + 3) & ~3) : ((n_sel + 3) & ~3LL);
+    const int64_t need = stream ? (int64_t)m->pbatch * ((m->pbatch + 3) & ~3) : (int64_t)m->pbatch * ldo;
+    if (need > m->p_scores_cap) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        dfree(m, m->p_scores);
+        if (dalloc(m, &m->p_scores, (size_t)need, false)) return -1;
+        m->p_scores_cap = need;
+    }
+    predict_gru(m, d_in_idx, mrows);
     const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);   // gru4rec.py:499-500
     const float* hsrc = (const float*)m->phout[d.n_layers - 1];
     if (stream) {
@@ -175,6 +189,59 @@ static int predict_forward(g4r_model* m, const int* d_in_idx, int mrows, const i
     if (sm) hipLaunchKernelGGL(k_softmax_rows, dim3(mrows), dim3(256), 0, m->stream, m->p_scores, (long long)n_sel, (long long)ldo);
     HIPCHK(hipGetLastError());
     m->p_nsel = n_sel; m->p_ldo = ldo;
+    return 0;
+}
+
+int g4r_recommend_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
+                       int32_t k, int32_t* out_cols, float* out_scores) {
+    if (!m || !out_cols || !out_scores) return fail("null argument");
+    const int64_t n_cand = item_idx ? n_sel : (int64_t)m->dm.n_items;
+    if (k < 1 || k > G4R_TOPK_MAX) return fail("k must be in [1, " + std::to_string(G4R_TOPK_MAX) + "]");
+    if (k > n_cand) return fail("k exceeds the number of candidates (n_sel = " + std::to_string(n_cand) + ")");
+    if (n_cand > INT32_MAX) return fail("more than 2^31 - 1 candidates");
+    if (predict_inputs(m, in_idx, mrows, item_idx, &n_sel)) return -1;
+    DevModel& d = m->dm;
+    const int* d_items = item_idx ? (const int*)m->p_items : (const int*)nullptr;
+    const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
+    // softmax needs the whole row first: the scores are materialised exactly as g4r_predict_step materialises them, then selected;
+    // an element-wise final activation is selected as the tiles are scored (nothing stored)
+    if (sm) {
+        if (predict_forward(m, m->p_in, mrows, d_items, n_sel, nullptr)) return -1;
+    } else {
+        predict_gru(m, m->p_in, mrows);
+    }
+    // column ranges: (row blocks) x (ranges) workgroups, one per compute unit (the LDS of k_topk_range admits one per CU)
+    const int row_blocks = cdiv(mrows, SC_BM);
+    const int64_t tiles = (n_sel + TK_TN - 1) / TK_TN;
+    const int64_t R0 = std::min<int64_t>(std::max(1, m->n_cu / row_blocks), tiles);
+    const int tpr = (int)((tiles + R0 - 1) / R0);
+    const int R = (int)((tiles + tpr - 1) / tpr);
+    const int64_t need = (int64_t)mrows * R * k, nout = (int64_t)mrows * k;
+    if (need > m->p_topk_cap || nout > m->p_tout_cap) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        if (need > m->p_topk_cap) {
+            dfree(m, m->p_topk);
+            if (dalloc(m, &m->p_topk, (size_t)need, false)) return -1;
+            m->p_topk_cap = need;
+        }
+        if (nout > m->p_tout_cap) {
+            dfree(m, m->p_tcols); dfree(m, m->p_tscores);
+            if (dalloc(m, &m->p_tcols, (size_t)nout, false) || dalloc(m, &m->p_tscores, (size_t)nout, false)) return -1;
+            m->p_tout_cap = nout;
+        }
+    }
+    const float* hsrc = (const float*)m->phout[d.n_layers - 1];
+    if (sm)
+        hipLaunchKernelGGL(k_topk_stored, dim3(R, row_blocks), dim3(256), TK_SMEM_STORED, m->stream, (const DevModel*)m->d_dm, hsrc,
+                           (int)mrows, d_items, (long long)n_sel, (const float*)m->p_scores, (long long)m->p_ldo, (int)k, tpr, m->p_topk);
+    else
+        hipLaunchKernelGGL(k_topk_fused, dim3(R, row_blocks), dim3(256), TK_SMEM_FUSED, m->stream, (const DevModel*)m->d_dm, hsrc,
+                           (int)mrows, d_items, (long long)n_sel, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk);
+    hipLaunchKernelGGL(k_topk_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->p_topk, R, (int)k, m->p_tcols, m->p_tscores);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_cols, m->p_tcols, nout * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(out_scores, m->p_tscores, nout * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
     return 0;
 }
 

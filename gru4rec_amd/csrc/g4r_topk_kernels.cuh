@@ -1,0 +1,273 @@
+// Top-K next-item recommendation kernels (gfx950), behind g4r_recommend_step (not in the reference).
+//   k_topk_fused   scores of a column range (the k_score_all chain) -> the range's k best per row, nothing stored
+//   k_topk_stored  the same selection over a score matrix already in memory (softmax / softmax_logit final activations)
+//   k_topk_merge   the ranges' lists of one row -> the row's k best (int32 column, float score)
+//
+// Order (the contract of g4r_recommend_step): score descending, equal scores (float ==, so -0.0 == +0.0) by the lower column,
+// NaN below every number.  topk_key() maps (score, column) to one 64-bit key whose unsigned order IS that order; the keys of one
+// row are distinct (columns are), so "the k best" is exactly the k largest keys.  Key 0 is never a real entry's: it pads.
+#pragma once
+#include "g4r_eval_kernels.cuh"
+
+#define TK_MAX G4R_TOPK_MAX      // largest k
+#define TK_Q 64          // survivor queue per row (LDS); merged into the row's list once any row holds more than TK_Q - 32
+#define TK_TN 32         // columns per tile (as k_score_all<32>): a tile adds at most 32 survivors per row
+
+__device__ __forceinline__ unsigned long long topk_key(float v, unsigned col) {
+    unsigned u = __float_as_uint(v);
+    if ((u << 1) == 0u) u = 0u;                                       // -0.0 -> +0.0
+    const unsigned s = (v != v) ? 1u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));   // NaN 1, -inf 0x007FFFFF, +inf 0xFF800000
+#if defined(G4R_MUTATE) && G4R_MUTATE == 7      // test build: equal scores broken by the HIGHER column
+    const unsigned c = col;
+#else
+    const unsigned c = ~col;
+#endif
+    return ((unsigned long long)s << 32) | c;
+}
+// (score bits, column) as stored in the lists; column 0xFFFFFFFF pads a list (columns are < 2^31) and keys 0
+__device__ __forceinline__ unsigned long long topk_key(uint2 e) { return e.y == 0xFFFFFFFFu ? 0ull : topk_key(__uint_as_float(e.x), e.y); }
+
+// LDS of the range kernels: [queues | queue counts | list lengths | thresholds | scratch (k_topk_stored) or score tile (k_topk_fused)]
+// The fused kernel's merge scratch aliases its A tile: a merge runs between the last read of one tile and the first write of the next.
+#define TK_SCRATCH_WAVE (TK_MAX * 8 + TK_Q * 8)          // bytes: a copy of the row's list + the sorted queue keys
+#define TK_SMEM_SEL (SC_BM * TK_Q * 8 + SC_BM * 4 * 2 + SC_BM * 8)
+#define TK_SMEM_STORED (TK_SMEM_SEL + 4 * TK_SCRATCH_WAVE)
+#define TK_SMEM_FUSED (TK_SMEM_SEL + ((SC_BM + TK_TN) * (SC_KC + 2) + TK_TN) * 4)
+
+// One wave merges the survivor queue of local row r into the row's sorted list L (global, length n <= k): the queue is sorted in
+// registers (bitonic over the 64 lanes), then every element's place in the union is its own index plus the number of elements of
+// the other sequence above it (binary search), and the first k places are written.  The row's threshold becomes its k-th key.
+__device__ __forceinline__ void topk_merge_row(int r, uint2* L, int k, uint2* sq, unsigned long long* skq, uint2* sl, int* s_qn,
+                                               int* s_ln, unsigned long long* s_thr) {
+    const int lane = threadIdx.x & 63;
+    const int c = s_qn[r], n = s_ln[r];
+    for (int j = lane; j < n; j += 64) sl[j] = L[j];
+    uint2 e = lane < c ? sq[lane] : make_uint2(0u, 0xFFFFFFFFu);
+    unsigned long long q = lane < c ? topk_key(e) : 0ull;
+#pragma unroll
+    for (int w = 2; w <= 64; w <<= 1)
+#pragma unroll
+        for (int j = w >> 1; j > 0; j >>= 1) {
+            const unsigned lo = __shfl_xor((unsigned)q, j), hi = __shfl_xor((unsigned)(q >> 32), j);
+            const unsigned ex = __shfl_xor(e.x, j), ey = __shfl_xor(e.y, j);
+            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+            const bool desc = (lane & w) == 0, lower = (lane & j) == 0;
+            if ((lower == desc) ? (o > q) : (o < q)) { q = o; e = make_uint2(ex, ey); }
+        }
+    skq[lane] = q;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int j = lane; j < n; j += 64) {
+        const uint2 x = sl[j];
+        const unsigned long long kx = topk_key(x);
+        int a = 0, b = c;
+        while (a < b) { const int mid = (a + b) >> 1; if (skq[mid] > kx) a = mid + 1; else b = mid; }
+        const int pos = j + a;
+        if (pos < k) L[pos] = x;
+        if (pos == k - 1) s_thr[r] = kx;
+    }
+    if (lane < c) {
+        int a = 0, b = n;
+        while (a < b) { const int mid = (a + b) >> 1; if (topk_key(sl[mid]) > q) a = mid + 1; else b = mid; }
+        const int pos = lane + a;
+        if (pos < k) L[pos] = e;
+        if (pos == k - 1) s_thr[r] = q;
+    }
+    if (lane == 0) { s_ln[r] = min(k, n + c); s_qn[r] = 0; }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Stage 1.  Workgroup (blockIdx.x, blockIdx.y) = column range x 128-row block; the range is `tpr` tiles of 32 columns.  Per tile
+// a score is pushed to its row's queue only when its key beats the row's threshold (the k-th key of the range's list so far:
+// later columns lose every tie, so an equal score never gets in).  Output: ws[(row * gridDim.x + range) * k + j], the range's
+// k best of the row in key order, entries past the range's column count padded with column 0xFFFFFFFF (key 0).
+// STORED = false: the tile is computed as k_score_all computes it (one ascending-k fp32 MFMA chain from zero, + By, then the final
+// activation), so every score is bit-identical to g4r_predict_step's.  STORED = true: the tile is read from `sc` (ldo floats per row).
+template <bool STORED>
+__global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__ mp, const float* h, int mrows, const int* item_idx,
+                                                    long long n_sel, const float* sc, long long ldo, int k, int tpr, uint2* ws) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, lg = lane >> 4;
+    uint2* s_q = reinterpret_cast<uint2*>(smem);
+    int* s_qn = reinterpret_cast<int*>(s_q + SC_BM * TK_Q);
+    int* s_ln = s_qn + SC_BM;
+    unsigned long long* s_thr = reinterpret_cast<unsigned long long*>(s_ln + SC_BM);
+    char* tail = reinterpret_cast<char*>(s_thr + SC_BM);
+    float* sA = reinterpret_cast<float*>(tail);
+    const int ldk = SC_KC + 2;
+    float* sB = sA + SC_BM * ldk;
+    int* sItem = reinterpret_cast<int*>(sB + TK_TN * ldk);
+    char* scratch = tail + wid * TK_SCRATCH_WAVE;
+    uint2* sl = reinterpret_cast<uint2*>(scratch);
+    unsigned long long* skq = reinterpret_cast<unsigned long long*>(scratch + TK_MAX * 8);
+
+    const int rbase = blockIdx.y * SC_BM, range = blockIdx.x, R = gridDim.x;
+    const long long c0 = (long long)range * tpr * TK_TN, c1 = min(n_sel, c0 + (long long)tpr * TK_TN);
+    if (tid < SC_BM) { s_qn[tid] = 0; s_ln[tid] = 0; s_thr[tid] = 0ull; }
+    __syncthreads();
+    auto list = [&](int r) { return ws + ((size_t)(rbase + r) * R + range) * k; };
+    auto merge_all = [&]() {
+        for (int r = wid; r < SC_BM; r += 4)
+            if (s_qn[r] > 0) topk_merge_row(r, list(r), k, s_q + r * TK_Q, skq, sl, s_qn, s_ln, s_thr);
+        __syncthreads();
+    };
+    for (long long n0 = c0; n0 < c1; n0 += TK_TN) {
+        float v[2][2][4];      // [ri][cj][rg]: row 32 wid + 16 ri + 4 lg + rg, column n0 + 16 cj + li (the MFMA accumulator layout)
+        if constexpr (!STORED) {
+            const DevModel& m = *mp;
+            const int D = m.Dtop;
+            if (tid < TK_TN) {
+                const long long n = n0 + tid;
+                sItem[tid] = n < c1 ? (item_idx ? item_idx[n] : (int)n) : -1;
+            }
+            __syncthreads();
+            f32x4 acc[2][2];
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int kc0 = 0; kc0 < D; kc0 += SC_KC) {
+                const int kc = min(SC_KC, D - kc0), kc4 = kc >> 2;
+                for (int e = tid; e < SC_BM * kc4; e += 256) {
+                    const int i = e / kc4, c4 = e - i * kc4, row = rbase + i;
+                    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (row < mrows) x = ld4(h + (size_t)row * D + kc0 + 4 * c4);
+                    float2* d = reinterpret_cast<float2*>(sA + i * ldk + 4 * c4);
+                    d[0] = make_float2(x.x, x.y);
+                    d[1] = make_float2(x.z, x.w);
+                }
+                for (int e = tid; e < TK_TN * kc4; e += 256) {
+                    const int j = e / kc4, c4 = e - j * kc4, item = sItem[j];
+                    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (item >= 0) x = ld4(m.Wy + (size_t)item * D + kc0 + 4 * c4);
+                    float2* d = reinterpret_cast<float2*>(sB + j * ldk + 4 * c4);
+                    d[0] = make_float2(x.x, x.y);
+                    d[1] = make_float2(x.z, x.w);
+                }
+                __syncthreads();
+                for (int kk = 0; kk < kc; kk += 4) {
+                    const float a0 = sA[(32 * wid + li) * ldk + kk + lg];
+                    const float a1 = sA[(32 * wid + 16 + li) * ldk + kk + lg];
+#pragma unroll
+                    for (int cj = 0; cj < 2; ++cj) {
+                        const float b = sB[(16 * cj + li) * ldk + kk + lg];
+                        acc[0][cj] = mfma16(a0, b, acc[0][cj]);
+                        acc[1][cj] = mfma16(a1, b, acc[1][cj]);
+                    }
+                }
+                __syncthreads();
+            }
+#pragma unroll
+            for (int cj = 0; cj < 2; ++cj) {
+                const int item = sItem[16 * cj + li];
+                const float add = item >= 0 ? m.By[item] : 0.f;
+#pragma unroll
+                for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+                    for (int rg = 0; rg < 4; ++rg) v[ri][cj][rg] = act_fwd(m.final_act, m.fa_p0, m.fa_p1, acc[ri][cj][rg] + add);
+            }
+        } else {
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg) {
+                    const int row = min(rbase + 32 * wid + 16 * ri + 4 * lg + rg, mrows - 1);
+#pragma unroll
+                    for (int cj = 0; cj < 2; ++cj) v[ri][cj][rg] = sc[(size_t)row * ldo + min(n0 + 16 * cj + li, c1 - 1)];
+                }
+        }
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const int r = 32 * wid + 16 * ri + 4 * lg + rg;
+                const unsigned long long t = s_thr[r];
+#pragma unroll
+                for (int cj = 0; cj < 2; ++cj) {
+                    const long long n = n0 + 16 * cj + li;
+                    const unsigned long long key = topk_key(v[ri][cj][rg], (unsigned)n);
+                    if (rbase + r < mrows && n < c1 && key > t) {
+                        const int p = atomicAdd(s_qn + r, 1);
+                        s_q[r * TK_Q + p] = make_uint2(__float_as_uint(v[ri][cj][rg]), (unsigned)n);
+                    }
+                }
+            }
+        __syncthreads();
+        if (__syncthreads_or(tid < SC_BM && s_qn[tid] > TK_Q - TK_TN)) merge_all();
+    }
+    merge_all();
+    for (int r = wid; r < SC_BM; r += 4)
+        if (rbase + r < mrows) {
+            uint2* L = list(r);
+            for (int j = s_ln[r] + lane; j < k; j += 64) L[j] = make_uint2(0u, 0xFFFFFFFFu);
+        }
+}
+
+// Stage 2.  One workgroup per row: the k-th largest key T of the row's nl * k entries by an MSB-first radix select (eight 8-bit
+// digits of the 64-bit key), then the k entries with key >= T (exactly k: keys are distinct), sorted in LDS, written out.
+__global__ __launch_bounds__(256) void k_topk_merge(const uint2* ws, int nl, int k, int* out_cols, float* out_scores) {
+    __shared__ int hist[256];
+    __shared__ int s_digit, s_need, s_cnt;
+    __shared__ unsigned long long sk[TK_MAX];
+    __shared__ uint2 se[TK_MAX];
+    const int tid = threadIdx.x;
+    const uint2* L = ws + (size_t)blockIdx.x * nl * k;
+    const int N = nl * k;
+    unsigned long long prefix = 0ull, mask = 0ull;
+    int need = k;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        hist[tid] = 0;
+        __syncthreads();
+        for (int i = tid; i < N; i += 256) {
+            const unsigned long long key = topk_key(L[i]);
+            if ((key & mask) == prefix) atomicAdd(hist + (int)((key >> shift) & 255u), 1);
+        }
+        __syncthreads();
+        // suffix sums: hist[d] <- number of matching entries whose digit is >= d
+        for (int o = 1; o < 256; o <<= 1) {
+            const int x = tid + o < 256 ? hist[tid + o] : 0;
+            __syncthreads();
+            hist[tid] += x;
+            __syncthreads();
+        }
+        const int ge = hist[tid], gt = tid < 255 ? hist[tid + 1] : 0;
+        if (ge >= need && gt < need) { s_digit = tid; s_need = need - gt; }
+        __syncthreads();
+        prefix |= (unsigned long long)s_digit << shift;
+        mask |= 255ull << shift;
+        need = s_need;
+        __syncthreads();
+    }
+    if (tid == 0) s_cnt = 0;
+    sk[tid] = 0ull;
+    __syncthreads();
+    for (int i = tid; i < N; i += 256) {
+        const uint2 e = L[i];
+        const unsigned long long key = topk_key(e);
+        if (key >= prefix) {
+            const int p = atomicAdd(&s_cnt, 1);
+            if (p < TK_MAX) { sk[p] = key; se[p] = e; }      // (exactly k <= TK_MAX get here)
+        }
+    }
+    __syncthreads();
+    for (int w = 2; w <= TK_MAX; w <<= 1)
+        for (int j = w >> 1; j > 0; j >>= 1) {
+            const int p = tid ^ j;
+            if (p > tid) {
+                const unsigned long long a = sk[tid], b = sk[p];
+                if (((tid & w) == 0) ? (a < b) : (a > b)) {
+                    sk[tid] = b; sk[p] = a;
+                    const uint2 t = se[tid]; se[tid] = se[p]; se[p] = t;
+                }
+            }
+            __syncthreads();
+        }
+    if (tid < k) {
+        out_cols[(size_t)blockIdx.x * k + tid] = (int)se[tid].y;
+        out_scores[(size_t)blockIdx.x * k + tid] = __uint_as_float(se[tid].x);
+    }
+}
+
+template __global__ void k_topk_range<false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
+template __global__ void k_topk_range<true>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);

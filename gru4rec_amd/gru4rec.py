@@ -719,10 +719,9 @@ class GRU4Rec:
             self._upload_weights(self._model)
         return self._model
 
-    def predict_next_batch(self, session_ids, input_item_ids, predict_for_item_ids=None, batch=100):
-        """Scores for the next item of every session in the batch.  Rows: items, columns: batch events."""
-        if self.error_during_train:
-            raise Exception
+    def _predict_rows(self, session_ids, input_item_ids, batch):
+        """Session bookkeeping of a prediction call (gru4rec.py:712-717), shared by predict_next_batch / recommend_next_batch: (re)starts
+        the prediction state for `batch`, zeroes the hidden rows of changed sessions; returns (device model, input item indices)."""
         m = self._ensure_model()
         if self.predict is None or self.predict_batch != batch:
             self.predict_batch = batch
@@ -734,13 +733,39 @@ class GRU4Rec:
         if changed.any():
             m.predict_hidden(zero_mask=changed.astype(np.uint8))
             self.current_session = session_ids.copy()
-        in_idxs = self.itemidmap[input_item_ids].values
+        return m, self.itemidmap[input_item_ids].values
+
+    def predict_next_batch(self, session_ids, input_item_ids, predict_for_item_ids=None, batch=100):
+        """Scores for the next item of every session in the batch.  Rows: items, columns: batch events."""
+        if self.error_during_train:
+            raise Exception
+        m, in_idxs = self._predict_rows(session_ids, input_item_ids, batch)
         if predict_for_item_ids is not None:
             iidx = self.itemidmap[predict_for_item_ids].values
             preds = m.predict_step(in_idxs, iidx).T
             return pd.DataFrame(data=preds, index=predict_for_item_ids)
         preds = m.predict_step(in_idxs).T
         return pd.DataFrame(data=preds, index=self.itemidmap.index)
+
+    def recommend_next_batch(self, session_ids, input_item_ids, k=20, predict_for_item_ids=None, batch=100):
+        """Top-k next items of every session: (item_ids[len(session_ids), k], scores[len(session_ids), k] float32).
+        Not in the reference.  Row r holds the k largest entries of column r of what predict_next_batch would return for the same
+        call (score descending, equal scores by the lower candidate position, NaN last), the scores bit-identical to it; the
+        candidates are all items in itemidmap order, or predict_for_item_ids in the given order.  The hidden state advances as in
+        predict_next_batch, so calls of the two may be interleaved.  Selection runs on the device: only k entries per row return."""
+        if self.error_during_train:
+            raise Exception
+        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
+        if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
+            raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        m, in_idxs = self._predict_rows(session_ids, input_item_ids, batch)
+        if predict_for_item_ids is not None:
+            cand = np.asarray(predict_for_item_ids)
+            cols, scores = m.recommend_step(in_idxs, self.itemidmap[predict_for_item_ids].values, int(k))
+        else:
+            cand = self.itemidmap.index.values
+            cols, scores = m.recommend_step(in_idxs, None, int(k))
+        return cand[cols], scores
 
     def symbolic_predict(self, X, Y, M, items, batch_size):
         raise NotImplementedError('symbolic_predict builds a Theano graph (gru4rec.py:729-741); the MI355X path '

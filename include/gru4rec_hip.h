@@ -170,6 +170,13 @@ int g4r_predict_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const i
  * scores (evaluation.py:56-65; col_begin = 0 for the all-items case, = M when `items` were given) */
 int g4r_rank_targets(g4r_model* m, const int32_t* target_col, int32_t mrows, int64_t col_begin, int32_t mode,
                      float* ranks);
+/* not in the reference: the k best of the scores g4r_predict_step would return for the same call (same hidden-state update),
+ * per row: score descending, equal scores by lower column, NaN last; scores bit-identical to g4r_predict_step's.
+ * out_cols[mrows * k] are positions in item_idx (item indices when item_idx is NULL), out_scores[mrows * k].
+ * 1 <= k <= min(n_sel, G4R_TOPK_MAX). */
+#define G4R_TOPK_MAX 256
+int g4r_recommend_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
+                       int32_t k, int32_t* out_cols, float* out_scores);
 
 /* The whole of evaluation.evaluate_gpu (evaluation.py:86-147) as ONE call with no host round trip per step: the
  * session-parallel test loop comes as a plan (g4r_build_plan on the test sessions in id order with n_sample = 1: the loop of

@@ -1,0 +1,78 @@
+"""Times g4r_recommend_step (top-k on the device) against g4r_predict_step(want_scores=False) -- the same GRU forward plus the full score
+matrix written to HBM, nothing copied back -- at the same shape and hidden state.  One JSON line per (shape, final activation):
+
+  python tools/bench_recommend.py [--shapes 10M,rsc15] [--acts linear,softmax] [--seconds 1.0] [--warmup 3]
+
+Each time is the mean of back-to-back synchronous calls over a window of at least --seconds after the warm-up.  mfma_frac: the
+scoring GEMM (2 * rows * n_items * D flop) over the call's time, as a fraction of the 157.3 TFLOP/s fp32 MFMA peak."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from gru4rec_amd import _native  # noqa: E402
+
+PEAK = 157.3e12
+SHAPES = {'10M': (10_000_000, 256, 512, 20), 'rsc15': (37_483, 100, 128, 20)}
+
+
+def timed(fn, seconds, warmup):
+    for _ in range(warmup):
+        fn()
+    n, t0 = 0, time.perf_counter()
+    while True:
+        fn()
+        n += 1
+        dt = time.perf_counter() - t0
+        if dt >= seconds:
+            return dt / n * 1e6
+
+
+def model(I, D, rows, act, rng):
+    sm = act.startswith('softmax')
+    m = _native.Model(n_items=I, layers=[D], batch_size=rows, n_sample=0, loss=_native.LOSS_IDS['cross-entropy' if sm else 'bpr-max'],
+                      final_act=_native.ACT_IDS[act], hidden_act=_native.ACT_IDS['tanh'], embed_mode=0, embedding=0, learning_rate=0.1,
+                      sample_store=0, seed=1, device=0, rank=0, nranks=1, use_graph=0)
+    blk = 4093
+    m.set_param('Wy', np.tile((rng.randn(blk, D) * 0.1).astype(np.float32), (I // blk + 1, 1))[:I])     # (a random block, repeated)
+    m.set_param('By', (rng.randn(I) * 0.1).astype(np.float32))
+    m.set_param('Wx', (rng.randn(D, 3 * D) * 0.05).astype(np.float32))
+    m.set_param('Wh', (rng.randn(D, D) * 0.05).astype(np.float32))
+    m.set_param('Wrz', (rng.randn(D, 2 * D) * 0.05).astype(np.float32))
+    m.set_param('Bh', (rng.randn(3 * D) * 0.1).astype(np.float32))
+    return m
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--shapes', default='10M,rsc15')
+    ap.add_argument('--acts', default='linear,softmax')
+    ap.add_argument('--seconds', type=float, default=1.0)
+    ap.add_argument('--warmup', type=int, default=3)
+    a = ap.parse_args()
+    for name in a.shapes.split(','):
+        I, D, rows, k = SHAPES[name]
+        for act in a.acts.split(','):
+            rng = np.random.RandomState(0)
+            m = model(I, D, rows, act, rng)
+            in_idx = rng.randint(0, I, size=rows).astype(np.int32)
+            m.predict_begin(rows)
+            # the hidden state advances every call (as in serving); both calls see the same sequence of states
+            t_rec = timed(lambda: m.recommend_step(in_idx, None, k), a.seconds, a.warmup)
+            m.predict_begin(rows)
+            t_pred = timed(lambda: m.predict_step(in_idx, want_scores=False), a.seconds, a.warmup)
+            flop = 2.0 * rows * I * D
+            print(json.dumps(dict(shape=name, n_items=I, D=D, rows=rows, k=k, final_act=act, us_recommend_step=round(t_rec, 1),
+                                  us_predict_step_no_copy=round(t_pred, 1), ratio=round(t_rec / t_pred, 3),
+                                  mfma_frac_recommend=round(flop / (t_rec * 1e-6) / PEAK, 4),
+                                  mfma_frac_predict=round(flop / (t_pred * 1e-6) / PEAK, 4))), flush=True)
+            m.close()
+
+
+if __name__ == '__main__':
+    main()
