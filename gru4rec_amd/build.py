@@ -36,7 +36,8 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
               "one library built with audit=False",
            5: 'the 1 / nranks factor of the exact-replica joint update (REDUCE / MEAN forms) x 1.01',
            6: 'the Adagrad step of ONE item row per step (the item of score column 0) x 1.5: a single wrong row must not pass',
-           7: 'top-k selection (g4r_recommend_step) breaks equal scores by the HIGHER column'}
+           7: 'top-k selection (g4r_recommend_step) breaks equal scores by the HIGHER column',
+           8: "k_update_l's owner scan skips the last id of every 1024-id slice after the first (an occurrence of a hot item lost)"}
 
 
 def mutant_path(k):

@@ -58,6 +58,14 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     }
     else if (s == "score_mt") { if (count < 1) return fail("count"); host[0] = (float)score_mt_width(d, m->n_cu); return 0; }      // macro-tile width of the scoring forward (0: 64 x 64 tiles)
     else if (s == "score_bmt") { if (count < 1) return fail("count"); host[0] = (float)score_bmt_slabs(d, m->n_cu); return 0; }      // slabs of the macro-tile scoring backward (0: k_score_bwd2)
+    else if (s == "lean") {      // the lean launches a training step takes (g4r_lean_kernels.cuh), from the predicates launch_step dispatches on:
+        if (count < 4) return fail("count");      // (bit l = lean_gru of layer l, lean_scores, lean_score_bwd, lean_update)
+        int mk = 0;
+        for (int l = 0; l < d.n_layers; ++l) mk |= lean_gru(d, l) ? 1 << l : 0;
+        host[0] = (float)mk; host[1] = lean_scores(d) ? 1.f : 0.f; host[2] = lean_score_bwd(d) ? 1.f : 0.f;
+        host[3] = (lean_update(m) && !(d.bbn[0] > 0)) ? 1.f : 0.f;
+        return 0;
+    }
     else if (s == "ksplit") { if (count < 1) return fail("count"); host[0] = (float)d.ksplit; return 0; }
     else if (s == "dev_syncs") { if (count < 1) return fail("count"); host[0] = (float)m->n_dev_syncs; return 0; }
     else if (s == "dense_count") { if (count < 1) return fail("count"); host[0] = (float)d.dense_count; return 0; }

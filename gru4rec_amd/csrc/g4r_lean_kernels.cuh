@@ -865,6 +865,11 @@ __global__ __launch_bounds__(512) void k_score_b(const LeanB* __restrict__ ap, c
 //     round trip), ballots the matches and adds their step rows in occurrence order, eight rows per round trip -- the arithmetic and the
 //     order of sparse_update_block (gru4rec.py:335-340,407-431: increments accumulate, accumulator and velocity take the last
 //     occurrence's value).  Items whose occurrences are all sampled negatives take the (count - 1) x own row shortcut as there.
+#if defined(G4R_MUTATE) && G4R_MUTATE == 8      // test build: the owner scan skips the last id of every 1024-slice after the first
+#define G4R_MUT_SLICE_SKIP(j, base0, start) ((base0) > (start) && (j) == (base0) + 1023)
+#else
+#define G4R_MUT_SLICE_SKIP(j, base0, start) false
+#endif
 template <bool MOM>
 __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* occ_idx, GAS int* occ_fl, const GAS float* dSx, const GAS float* dSy,
                                                  const GAS float* dSBy, unsigned k, unsigned R, unsigned B) {
@@ -922,7 +927,7 @@ __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* 
                     const int ids[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
                     unsigned long long mk[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) mk[e] = __ballot(ids[e] == item && j0 + e >= first_j && j0 + e < (int)k);
+                    for (int e = 0; e < 4; ++e) mk[e] = __ballot(ids[e] == item && j0 + e >= first_j && j0 + e < (int)k && !G4R_MUT_SLICE_SKIP(j0 + e, base0, first_j & ~3));
                     unsigned long long any = mk[0] | mk[1] | mk[2] | mk[3];
                     // up to eight matches per batch of row loads (wave-uniform positions in scalar registers)
                     while (any) {

@@ -141,8 +141,11 @@ class GRU4Rec:
         # over the ranks touching it) and 'sum' (every occurrence of every rank applied like a duplicate: diverges from four ranks on)
         self.sparse_exact = False
         # single GPU, Adagrad without momentum / lmbd: row updates whose item is not gathered again inside the current window of 16 steps
-        # wait for ONE flush launch per window (g4r_config::defer_updates).  Results are bit-identical; the flush launch runs at ~60 % of
-        # the HBM peak at BASELINE configs[2] -- and the step gets 2-5 % slower: off unless asked for
+        # wait for ONE flush launch per window (g4r_config::defer_updates).  Results are bit-identical to the immediate update on the same
+        # (merged k_update) kernel; where the default immediate mode takes the lean k_update_l instead (batches of <= 128 rows, item rows
+        # of <= 256 floats), it sums the dense gradients in another order, so the two modes agree to fp32 rounding, not to the bit.  The
+        # flush launch runs at ~60 % of the HBM peak at BASELINE configs[2] -- and the step gets 2-5 % slower: off
+        # unless asked for
         self.defer_updates = False
         self._model = None
         self._dist = None

@@ -68,20 +68,37 @@ def _run(case, defer):
     if not kw['constrained_embedding'] and not kw.get('embedding'):
         out['Wx0'] = m.get_param('Wx', (I, 3 * kw['layers'][0]), 0).copy()
     stats = m.get_debug('defer_stats', 4)
+    lean = m.get_debug('lean', 4)
     m.close()
-    return out, stats
+    return out, stats, lean
 
 
 @pytest.mark.parametrize('case', sorted(CASES))
 def test_deferred_updates_leave_identical_bits(case):
-    ref, st0 = _run(case, defer=False)
-    got, st1 = _run(case, defer=True)
+    ref, st0, _ = _run(case, defer=False)
+    got, st1, _ = _run(case, defer=True)
     assert st0[2] == 0 and st1[2] == 1, (st0, st1)
     assert st1[0] > 0, 'no row update was deferred: the test would prove nothing (%s)' % (st1,)
     assert np.isfinite(ref['loss']).all()
     for k in ref:
         np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
     print('%s: %d row updates (%d with a bias entry) went through flush launches' % (case, int(st1[0]), int(st1[1])))
+
+
+@pytest.mark.parametrize('case', ['cfg2_shape', 'refills_inside_the_call'])
+def test_default_immediate_mode_against_deferred(case, monkeypatch):
+    """What users get by default: the immediate mode takes k_update_l, the deferred mode the merged k_update (the override above is
+    lifted).  Their dense tiles sum the batch in different orders, so the two agree within the lean-vs-merged rounding bound of
+    test_gpu_parity.py::test_multirank_data_path_on_one_gpu, not to the bit."""
+    monkeypatch.delenv('G4R_LEAN_UPDATE', raising=False)
+    ref, st0, lean0 = _run(case, defer=False)
+    got, st1, lean1 = _run(case, defer=True)
+    assert st0[2] == 0 and st1[2] == 1, (st0, st1)
+    assert lean0[3] == 1 and lean1[3] == 0, (lean0, lean1)      # immediate: k_update_l; deferred: k_update
+    assert st1[0] > 0, st1
+    assert np.isfinite(ref['loss']).all()
+    for k in ref:
+        np.testing.assert_allclose(got[k], ref[k], rtol=2e-4, atol=2e-6, err_msg=k)
 
 
 def test_deferred_updates_without_the_step_graph():

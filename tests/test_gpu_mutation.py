@@ -8,6 +8,8 @@ mutant; every one of those runs has to come back red, and the tensor it names ha
   mutant 5  the 1 / nranks factor of the exact-replica joint update x 1.01 -> the REDUCE / MEAN oracle-as-replicas tests
   mutant 6  the Adagrad step of ONE item row per step x 1.5 (the item of score column 0) -> dWy: a single wrong row must fail, also in
             the exact-shape tests that compare the rows of kink items apart (round 5 left those rows out; now they are bounded)
+  mutant 8  k_update_l's owner scan skips the last id of every 1024-id slice after the first -> dWy of the hot-item case of
+            test_gpu_lean_edges.py (an item with > 1024 earlier occurrences in a step loses one of them)
 
 (Round 2's `atol = 1e-4` on every tensor let an accumulator that is wrong by 100 x pass.)  The same selection runs green on the
 product library in the ordinary suite."""
@@ -71,6 +73,21 @@ def test_mutant_5_turns_the_exact_replica_parity_red(mutants, tmp_path):
         r = subprocess.run([sys.executable, '-m', 'pytest', sel, '-x', '-q', '-p', 'no:cacheprovider'], cwd=ROOT, env=env,
                            capture_output=True, text=True, timeout=900)
         assert r.returncode == want_rc, 'mutant 5 on %s: rc %d\n%s' % (sel, r.returncode, (r.stdout + r.stderr)[-3000:])
+
+
+def test_mutant_8_turns_the_hot_item_case_red(mutants, tmp_path):
+    """The owner scan of k_update_l loses one occurrence per later 1024-id slice: the hot-item case must fail on dWy; a shape whose owners never reach a second slice must still pass."""
+    for i, (sel, want_rc) in enumerate([('tests/test_gpu_lean_edges.py::test_hot_item_past_1024[0.0]', 1),
+                                        ('tests/test_gpu_lean_edges.py::test_partial_16_tiles[20-17-0.0]', 0)]):
+        rep = str(tmp_path / ('hot%d.txt' % i))
+        env = dict(os.environ, G4R_LIB=mutants[8], G4R_PARITY_REPORT=rep)
+        r = subprocess.run([sys.executable, '-m', 'pytest', sel, '-x', '-q', '-p', 'no:cacheprovider'], cwd=ROOT, env=env,
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == want_rc, 'mutant 8 on %s: rc %d\n%s' % (sel, r.returncode, (r.stdout + r.stderr)[-3000:])
+        if want_rc:
+            lines = open(rep).read().splitlines()
+            state = {ln[:28].strip(): ln.rstrip().endswith('FAIL') for ln in lines if 'worst/tol' in ln}
+            assert state['hot dWy'], state
 
 
 def test_product_library_is_not_a_mutant():

@@ -75,15 +75,16 @@ def snapshot(o):
     return d
 
 
-def make_pair(I, B, ns, store_rows, seed=3, **kw):
-    """An oracle and a device model with identical weights / popularity / sample store."""
+def make_pair(I, B, ns, store_rows, seed=3, support=None, **kw):
+    """An oracle and a device model with identical weights / popularity / sample store.  support: the item supports the
+    popularity is made of (default: random integers in [1, 40))."""
     use_graph = kw.pop('use_graph', 0)
     rank, nranks = kw.pop('rank', 0), kw.pop('nranks', 1)      # a handle that is one rank of several (same weights, same sample stream)
     sparse_exact = kw.pop('sparse_exact', 0)
     o = OracleGRU4Rec(n_items=I, batch_size=B, n_sample=ns, dtype=np.float32, seed=seed, **kw)
     rng = np.random.RandomState(seed)
-    support = rng.randint(1, 40, size=I)
-    o.set_popularity(support)
+    support0 = rng.randint(1, 40, size=I)      # (drawn either way: the stream below stays as it was)
+    o.set_popularity(support0 if support is None else support)
     o.make_sample_store(store_rows * ns if ns else 0)
     fa = parse_act(kw.get('final_act', 'linear'))
     ha = parse_act(kw.get('hidden_act', 'tanh'))
@@ -414,23 +415,30 @@ def test_multirank_data_path_on_one_gpu(monkeypatch):
     I, B, ns, T = 80, 12, 24, 60
     plan = random_plan(I, B, T, seed=17)
     outs = []
-    for staged in (0, 1):
-        if staged:
+    for run in ('lean', 'merged', 'staged'):
+        if run == 'merged':
+            monkeypatch.setenv('G4R_LEAN_UPDATE', '0')      # read at create: the merged k_update, whose dense tiles sum as the staged path's do
+        if run == 'staged':
             monkeypatch.setenv('G4R_FORCE_STAGED', '1')
         _, m = make_pair(I, B, ns, store_rows=200, use_graph=0, **dict(kw))
-        if staged:
+        assert m.get_debug('lean', 4)[3] == (1 if run == 'lean' else 0), run
+        if run == 'staged':
             m.comm_init(_native.comm_unique_id(), 1, 0)
             assert m.comm_min(T) == T
         m.set_plan(plan)
         m.train_steps(0, T)
-        if staged:
+        if run == 'staged':
             m.comm_sync_sparse()
         outs.append((m.get_losses(0, T), m.get_param('Wy', (I, 16)), m.get_param('Wx', (16, 48), 0),
                      m.get_param('Bh', (48,), 0), m.get_param('acc_Wh', (16, 16), 0)))
         m.close()
-    # (the two paths run different dense-gradient tiles -- k_update_l's 16 x 64 register-fed tiles against k_dense_grad's LDS-staged
-    # 32 x 32 ones since round 6 --, i.e. different fp32 summation orders over the batch: equal to rounding, not to the bit)
-    for a, b in zip(outs[0], outs[1]):
+    lean, merged, staged = outs
+    # the merged single-GPU step and the staged path: the same arithmetic, a staged-path scale error of ~1e-4 fails
+    for a, b in zip(merged, staged):
+        np.testing.assert_allclose(a, b, rtol=1e-6, atol=1e-7)
+    # the default (k_update_l's 16 x 64 register-fed dense tiles) against the staged path (k_dense_grad's LDS-staged 32 x 32 ones):
+    # different fp32 summation orders over the batch, equal to rounding, not to the bit
+    for a, b in zip(lean, staged):
         np.testing.assert_allclose(a, b, rtol=2e-4, atol=2e-6)
 
 
