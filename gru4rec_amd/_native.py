@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get('G4R_LIB') or os.path.join(_HERE, 'libgru4rec_hip.so')
 
 G4R_MAX_LAYERS = 8
 G4R_TOPK_MAX = 256      # largest k of g4r_recommend_step
+G4R_EXCLUDE_MAX = 1024  # most distinct items one row of g4r_recommend_step_filtered may exclude
 LOSS_IDS = {'cross-entropy': 0, 'bpr-max': 1, 'top1-max': 2, 'bpr': 3, 'top1': 4, 'xe_logit': 5}
 ACT_IDS = {'linear': 0, 'relu': 1, 'tanh': 2, 'leaky': 3, 'elu': 4, 'selu': 5, 'softmax': 6, 'softmax_logit': 7}
 ADAPT_IDS = {'adagrad': 0, 'rmsprop': 1, 'adadelta': 2, 'adam': 3, None: 4}
@@ -43,7 +44,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -97,6 +98,7 @@ def lib():
     L.g4r_predict_hidden.argtypes = [vp, u8p, i32, i32p, i32]
     L.g4r_predict_step.argtypes = [vp, i32p, i32, i32p, i64, f32p]
     L.g4r_recommend_step.argtypes = [vp, i32p, i32, i32p, i64, i32, i32p, f32p]
+    L.g4r_recommend_step_filtered.argtypes = [vp, i32p, i32, i32p, i64, i32, i64p, i32p, C.POINTER(C.c_uint32), i32p, f32p]
     L.g4r_rank_targets.argtypes = [vp, i32p, i32, i64, i32, f32p]
     L.g4r_evaluate.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32p, i32, i32,
                                C.POINTER(C.c_double), C.POINTER(C.c_double), i64p]
@@ -376,6 +378,27 @@ class Model:
         cols = np.empty((len(ii), k), dtype=np.int32)
         scores = np.empty((len(ii), k), dtype=np.float32)
         _chk(lib().g4r_recommend_step(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k, _i32(cols), _f32(scores)))
+        return cols, scores
+
+    def recommend_step_filtered(self, in_idx, item_idx=None, k=20, excl_offs=None, excl_items=None, excl_mask=None):
+        """recommend_step without the excluded items (g4r_recommend_step_filtered): row r never receives a candidate whose item index
+        is in excl_items[excl_offs[r]:excl_offs[r + 1]] (excl_offs: rows + 1 offsets) or has its bit set in excl_mask (uint32 words,
+        bit i & 31 of word i >> 5).  None: no such exclusion.  Same return value as recommend_step."""
+        ii = np.ascontiguousarray(in_idx, dtype=np.int32)
+        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
+        n_sel = self.cfg.n_items if it is None else len(it)
+        offs = None if excl_offs is None else np.ascontiguousarray(excl_offs, dtype=np.int64)
+        xi = np.ascontiguousarray(np.zeros(0) if excl_items is None else excl_items, dtype=np.int32)
+        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
+        if offs is not None and (len(offs) != len(ii) + 1 or offs[-1] > len(xi) or offs[0] < 0):
+            raise ValueError('excl_offs must hold rows + 1 offsets into excl_items')
+        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
+            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
+        cols = np.empty((len(ii), k), dtype=np.int32)
+        scores = np.empty((len(ii), k), dtype=np.float32)
+        _chk(lib().g4r_recommend_step_filtered(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k,
+                                               None if offs is None else _i64(offs), _i32(xi),
+                                               None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)), _i32(cols), _f32(scores)))
         return cols, scores
 
     def rank_targets(self, target_col, col_begin=0, mode='standard'):

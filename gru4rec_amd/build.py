@@ -37,7 +37,8 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            5: 'the 1 / nranks factor of the exact-replica joint update (REDUCE / MEAN forms) x 1.01',
            6: 'the Adagrad step of ONE item row per step (the item of score column 0) x 1.5: a single wrong row must not pass',
            7: 'top-k selection (g4r_recommend_step) breaks equal scores by the HIGHER column',
-           8: "k_update_l's owner scan skips the last id of every 1024-id slice after the first (an occurrence of a hot item lost)"}
+           8: "k_update_l's owner scan skips the last id of every 1024-id slice after the first (an occurrence of a hot item lost)",
+           9: "the merge-time exclusion search of g4r_recommend_step_filtered never matches the LAST item of a row's sorted list"}
 
 
 def mutant_path(k):

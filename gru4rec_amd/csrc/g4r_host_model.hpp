@@ -108,6 +108,10 @@ struct g4r_model {
     int* p_tcols = nullptr;                      // [rows][k] its result
     float* p_tscores = nullptr;
     int64_t p_topk_cap = 0, p_tout_cap = 0;
+    long long* p_xoffs = nullptr;                // exclusions of g4r_recommend_step_filtered: [rows + 1] offsets into p_xitems,
+    int* p_xitems = nullptr;                     // the rows' sorted item lists,
+    unsigned* p_xmask = nullptr;                 // the global item bit mask
+    int64_t p_xoffs_cap = 0, p_xitems_cap = 0, p_xmask_cap = 0;
     unsigned tie_ctr = 0;                        // evaluation step counter of the 'tiebreaking' noise stream
     // rccl
     ncclComm_t comm = nullptr;
@@ -158,8 +162,10 @@ static void dfree(g4r_model* m, void* p) {
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static constexpr auto k_score_store = k_score_all<32, false>;     // scores -> memory
 static constexpr auto k_score_count = k_score_all<32, true>;      // scores compared with the row's target on the fly
-static constexpr auto k_topk_fused = k_topk_range<false>;         // scores selected as they are produced (element-wise final activation)
-static constexpr auto k_topk_stored = k_topk_range<true>;         // selection over p_scores (softmax / softmax_logit)
+static constexpr auto k_topk_fused = k_topk_range<false, false>;         // scores selected as they are produced (element-wise final activation)
+static constexpr auto k_topk_stored = k_topk_range<true, false>;         // selection over p_scores (softmax / softmax_logit)
+static constexpr auto k_topk_fused_x = k_topk_range<false, true, TkExcl>;        // the same two with exclusions (g4r_recommend_step_filtered)
+static constexpr auto k_topk_stored_x = k_topk_range<true, true, TkExcl>;
 
 static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 // dynamic LDS of the tile-GEMM kernels (g4r_gemm.cuh)

@@ -1,5 +1,6 @@
 // g4r_host_predict.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
-// instantiated there).  Holds: prediction and evaluation: g4r_predict_*, g4r_rank_targets, g4r_recommend_step, g4r_evaluate.
+// instantiated there).  Holds: prediction and evaluation: g4r_predict_*, g4r_rank_targets, g4r_recommend_step(_filtered),
+// g4r_evaluate.
 // ------------------------------------------------------------------------------------------------ prediction
 int g4r_predict_begin(g4r_model* m, int32_t batch) {
     if (!m || batch < 1) return fail("bad batch");
@@ -192,14 +193,19 @@ static int predict_forward(g4r_model* m, const int* d_in_idx, int mrows, const i
     return 0;
 }
 
-int g4r_recommend_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
-                       int32_t k, int32_t* out_cols, float* out_scores) {
+// the k checks shared by g4r_recommend_step / g4r_recommend_step_filtered
+static int recommend_check(g4r_model* m, const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t* out_cols, float* out_scores) {
     if (!m || !out_cols || !out_scores) return fail("null argument");
     const int64_t n_cand = item_idx ? n_sel : (int64_t)m->dm.n_items;
     if (k < 1 || k > G4R_TOPK_MAX) return fail("k must be in [1, " + std::to_string(G4R_TOPK_MAX) + "]");
     if (k > n_cand) return fail("k exceeds the number of candidates (n_sel = " + std::to_string(n_cand) + ")");
     if (n_cand > INT32_MAX) return fail("more than 2^31 - 1 candidates");
-    if (predict_inputs(m, in_idx, mrows, item_idx, &n_sel)) return -1;
+    return 0;
+}
+
+// GRU step + selection of a checked call whose inputs predict_inputs has uploaded; ex (device exclusions) NULL: the unfiltered kernels
+static int recommend_run(g4r_model* m, int32_t mrows, const int32_t* item_idx, int64_t n_sel, int32_t k, const TkExcl* ex,
+                         int32_t* out_cols, float* out_scores) {
     DevModel& d = m->dm;
     const int* d_items = item_idx ? (const int*)m->p_items : (const int*)nullptr;
     const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
@@ -231,18 +237,130 @@ int g4r_recommend_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const
         }
     }
     const float* hsrc = (const float*)m->phout[d.n_layers - 1];
-    if (sm)
-        hipLaunchKernelGGL(k_topk_stored, dim3(R, row_blocks), dim3(256), TK_SMEM_STORED, m->stream, (const DevModel*)m->d_dm, hsrc,
+    const dim3 grid(R, row_blocks);
+    if (sm && !ex)
+        hipLaunchKernelGGL(k_topk_stored, grid, dim3(256), TK_SMEM_STORED, m->stream, (const DevModel*)m->d_dm, hsrc,
                            (int)mrows, d_items, (long long)n_sel, (const float*)m->p_scores, (long long)m->p_ldo, (int)k, tpr, m->p_topk);
-    else
-        hipLaunchKernelGGL(k_topk_fused, dim3(R, row_blocks), dim3(256), TK_SMEM_FUSED, m->stream, (const DevModel*)m->d_dm, hsrc,
+    else if (sm)
+        hipLaunchKernelGGL(k_topk_stored_x, grid, dim3(256), TK_SMEM_STORED_X, m->stream, (const DevModel*)m->d_dm, hsrc,
+                           (int)mrows, d_items, (long long)n_sel, (const float*)m->p_scores, (long long)m->p_ldo, (int)k, tpr, m->p_topk, *ex);
+    else if (!ex)
+        hipLaunchKernelGGL(k_topk_fused, grid, dim3(256), TK_SMEM_FUSED, m->stream, (const DevModel*)m->d_dm, hsrc,
                            (int)mrows, d_items, (long long)n_sel, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk);
+    else
+        hipLaunchKernelGGL(k_topk_fused_x, grid, dim3(256), TK_SMEM_FUSED_X, m->stream, (const DevModel*)m->d_dm, hsrc,
+                           (int)mrows, d_items, (long long)n_sel, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk, *ex);
     hipLaunchKernelGGL(k_topk_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->p_topk, R, (int)k, m->p_tcols, m->p_tscores);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_cols, m->p_tcols, nout * sizeof(int), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipMemcpyAsync(out_scores, m->p_tscores, nout * sizeof(float), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return 0;
+}
+
+int g4r_recommend_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
+                       int32_t k, int32_t* out_cols, float* out_scores) {
+    if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores)) return -1;
+    if (predict_inputs(m, in_idx, mrows, item_idx, &n_sel)) return -1;
+    return recommend_run(m, mrows, item_idx, n_sel, k, nullptr, out_cols, out_scores);
+}
+
+int g4r_recommend_step_filtered(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
+                                int32_t k, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
+                                int32_t* out_cols, float* out_scores) {
+    if (!excl_offs && !excl_mask) return g4r_recommend_step(m, in_idx, mrows, item_idx, n_sel, k, out_cols, out_scores);
+    if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores)) return -1;
+    if (predict_inputs(m, in_idx, mrows, item_idx, &n_sel)) return -1;      // (uploads only: the state advances in recommend_run)
+    const int64_t I = m->dm.n_items, nw = (I + 31) / 32;
+    // every row's list: checked, sorted, de-duplicated
+    std::vector<long long> offs;
+    std::vector<int32_t> items;
+    if (excl_offs) {
+        if (excl_offs[0] < 0) return fail("excl_offs[0] is negative");
+        for (int r = 0; r < mrows; ++r)
+            if (excl_offs[r + 1] < excl_offs[r]) return fail("excl_offs is not monotone at row " + std::to_string(r));
+        if (excl_offs[mrows] > excl_offs[0] && !excl_items) return fail("null argument (excl_items)");
+        offs.resize((size_t)mrows + 1, 0);
+        items.reserve((size_t)std::min<int64_t>(excl_offs[mrows] - excl_offs[0], (int64_t)mrows * G4R_EXCLUDE_MAX));
+        for (int r = 0; r < mrows; ++r) {
+            const size_t b = items.size();
+            for (int64_t j = excl_offs[r]; j < excl_offs[r + 1]; ++j) {
+                if (excl_items[j] < 0 || excl_items[j] >= I) return fail("excluded item index out of range in row " + std::to_string(r));
+                items.push_back(excl_items[j]);
+            }
+            std::sort(items.begin() + b, items.end());
+            items.erase(std::unique(items.begin() + b, items.end()), items.end());
+            if (items.size() - b > G4R_EXCLUDE_MAX)
+                return fail("row " + std::to_string(r) + " excludes " + std::to_string(items.size() - b) + " distinct items, more than G4R_EXCLUDE_MAX = " +
+                            std::to_string(G4R_EXCLUDE_MAX));
+            offs[r + 1] = (long long)items.size();
+        }
+    }
+    auto masked = [&](int32_t i) { return excl_mask && ((excl_mask[i >> 5] >> (i & 31)) & 1u); };
+    // eligible candidate positions per row: n_cand - (positions of masked items) - (positions of the row's unmasked items)
+    const int64_t n_cand = item_idx ? n_sel : I;
+    int64_t n_masked = 0;
+    std::vector<int32_t> uni;                 // with item_idx: the items of all rows' lists, sorted, and their position counts
+    std::vector<int64_t> cnt;
+    if (excl_offs && item_idx) {
+        uni = items;
+        std::sort(uni.begin(), uni.end());
+        uni.erase(std::unique(uni.begin(), uni.end()), uni.end());
+        cnt.assign(uni.size(), 0);
+    }
+    if (item_idx) {
+        std::vector<uint32_t> in_uni((size_t)nw, 0u);
+        for (int32_t i : uni) in_uni[i >> 5] |= 1u << (i & 31);
+        for (int64_t p = 0; p < n_sel; ++p) {
+            const int32_t i = item_idx[p];
+            if (masked(i)) ++n_masked;
+            else if ((in_uni[i >> 5] >> (i & 31)) & 1u) ++cnt[std::lower_bound(uni.begin(), uni.end(), i) - uni.begin()];
+        }
+    } else if (excl_mask) {
+        for (int64_t w = 0; w < nw; ++w) {
+            const uint32_t valid = (w == nw - 1 && (I & 31)) ? ((1u << (I & 31)) - 1u) : 0xFFFFFFFFu;
+            n_masked += __builtin_popcount(excl_mask[w] & valid);
+        }
+    }
+    for (int r = 0; r < mrows; ++r) {
+        int64_t gone = n_masked;
+        if (excl_offs)
+            for (long long j = offs[r]; j < offs[r + 1]; ++j)
+                if (!masked(items[j])) gone += item_idx ? cnt[std::lower_bound(uni.begin(), uni.end(), items[j]) - uni.begin()] : 1;
+        if (n_cand - gone < k)
+            return fail("row " + std::to_string(r) + " has " + std::to_string(n_cand - gone) + " eligible candidate positions, fewer than k = " +
+                        std::to_string(k));
+    }
+    // upload (into buffers that only grow), then the filtered selection
+    if (excl_offs) {
+        if ((int64_t)offs.size() > m->p_xoffs_cap || (int64_t)items.size() > m->p_xitems_cap) {
+            HIPCHK(hipStreamSynchronize(m->stream));
+            if ((int64_t)offs.size() > m->p_xoffs_cap) {
+                dfree(m, m->p_xoffs);
+                if (dalloc(m, &m->p_xoffs, offs.size(), false)) return -1;
+                m->p_xoffs_cap = (int64_t)offs.size();
+            }
+            if ((int64_t)items.size() > m->p_xitems_cap) {
+                dfree(m, m->p_xitems);
+                if (dalloc(m, &m->p_xitems, items.size(), false)) return -1;
+                m->p_xitems_cap = (int64_t)items.size();
+            }
+        }
+        HIPCHK(hipMemcpyAsync(m->p_xoffs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, m->stream));
+        if (!items.empty()) HIPCHK(hipMemcpyAsync(m->p_xitems, items.data(), items.size() * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+    }
+    if (excl_mask) {
+        if (nw > m->p_xmask_cap) {
+            HIPCHK(hipStreamSynchronize(m->stream));
+            dfree(m, m->p_xmask);
+            if (dalloc(m, &m->p_xmask, (size_t)nw, false)) return -1;
+            m->p_xmask_cap = nw;
+        }
+        HIPCHK(hipMemcpyAsync(m->p_xmask, excl_mask, (size_t)nw * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+    }
+    const TkExcl ex = {excl_offs ? (const long long*)m->p_xoffs : nullptr, excl_offs ? (const int*)m->p_xitems : nullptr,
+                       excl_mask ? (const unsigned*)m->p_xmask : nullptr};
+    return recommend_run(m, mrows, item_idx, n_sel, k, &ex, out_cols, out_scores);
 }
 
 int g4r_evaluate(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, const uint8_t* reset, const int32_t* M, int64_t T,

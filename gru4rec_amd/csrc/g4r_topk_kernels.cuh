@@ -2,6 +2,9 @@
 //   k_topk_fused   scores of a column range (the k_score_all chain) -> the range's k best per row, nothing stored
 //   k_topk_stored  the same selection over a score matrix already in memory (softmax / softmax_logit final activations)
 //   k_topk_merge   the ranges' lists of one row -> the row's k best (int32 column, float score)
+// The EXCL = true instantiations of k_topk_range (behind g4r_recommend_step_filtered) drop excluded items where a survivor queue is
+// merged into its row's list (topk_merge_row): a global bit mask over item indices and a sorted per-row list (at most
+// G4R_EXCLUDE_MAX items).  The EXCL = false instantiations are the unfiltered kernels, instruction for instruction.
 //
 // Order (the contract of g4r_recommend_step): score descending, equal scores (float ==, so -0.0 == +0.0) by the lower column,
 // NaN below every number.  topk_key() maps (score, column) to one 64-bit key whose unsigned order IS that order; the keys of one
@@ -31,19 +34,67 @@ __device__ __forceinline__ unsigned long long topk_key(uint2 e) { return e.y == 
 // The fused kernel's merge scratch aliases its A tile: a merge runs between the last read of one tile and the first write of the next.
 #define TK_SCRATCH_WAVE (TK_MAX * 8 + TK_Q * 8)          // bytes: a copy of the row's list + the sorted queue keys
 #define TK_SMEM_SEL (SC_BM * TK_Q * 8 + SC_BM * 4 * 2 + SC_BM * 8)
+#define TK_SCRATCH_WAVE_X (TK_SCRATCH_WAVE + G4R_EXCLUDE_MAX * 4)   // EXCL: + the row's sorted exclusion list
 #define TK_SMEM_STORED (TK_SMEM_SEL + 4 * TK_SCRATCH_WAVE)
 #define TK_SMEM_FUSED (TK_SMEM_SEL + ((SC_BM + TK_TN) * (SC_KC + 2) + TK_TN) * 4)
+#define TK_SEL_X (SC_BM * 12)           // EXCL: + every row's list start (8 B) and length (4 B), staged once per workgroup
+#define TK_SMEM_STORED_X (TK_SMEM_STORED + TK_SEL_X + 4 * (TK_SCRATCH_WAVE_X - TK_SCRATCH_WAVE))
+#define TK_SMEM_FUSED_X (TK_SMEM_FUSED + TK_SEL_X)
+// LDS budget (160 KiB per CU): k_topk_stored 77,824 B, 95,744 B with EXCL; k_topk_fused 150,912 B, 152,448 B with EXCL, the four
+// waves' merge scratch (4 x 2,560 B, 4 x 6,656 B = 26,624 B with EXCL) aliasing its 66,560 B A tile
+static_assert(4 * TK_SCRATCH_WAVE_X <= SC_BM * (SC_KC + 2) * 4, "the EXCL merge scratch must fit in the fused kernel's A tile");
+static_assert(TK_SMEM_STORED_X <= 156 * 1024 && TK_SMEM_FUSED_X <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
+
+// Exclusions of one g4r_recommend_step_filtered call (device pointers, NULL = none): row r's sorted, duplicate-free item indices are
+// items[offs[r] .. offs[r + 1]), at most G4R_EXCLUDE_MAX of them; bit (i & 31) of mask[i >> 5] excludes item index i in every row.
+struct TkExcl { const long long* offs; const int* items; const unsigned* mask; };
+__device__ __forceinline__ TkExcl tk_excl() { return TkExcl{}; }
+__device__ __forceinline__ TkExcl tk_excl(TkExcl e) { return e; }
 
 // One wave merges the survivor queue of local row r into the row's sorted list L (global, length n <= k): the queue is sorted in
 // registers (bitonic over the 64 lanes), then every element's place in the union is its own index plus the number of elements of
 // the other sequence above it (binary search), and the first k places are written.  The row's threshold becomes its k-th key.
+// EXCL: every queue entry whose item (item_idx[column], or the column) is excluded -- its bit in ex.mask, or found by binary search
+// in the row's list (staged in sx, loaded together with the list copy) -- becomes the pad (key 0) before the sort and is not
+// counted in c.  The list then only ever holds eligible entries, so the threshold is an eligible key; an excluded item can still
+// beat it, but enters the range's queue at most once (a range visits each column once): the queue bound (<= 32 per tile) holds.
+// (xb, nx: the row's list is ex.items[xb .. xb + nx), read from LDS so that its load goes out together with the list copy)
+template <bool EXCL>
 __device__ __forceinline__ void topk_merge_row(int r, uint2* L, int k, uint2* sq, unsigned long long* skq, uint2* sl, int* s_qn,
-                                               int* s_ln, unsigned long long* s_thr) {
+                                               int* s_ln, unsigned long long* s_thr, long long xb = 0, int nx = 0,
+                                               const int* item_idx = nullptr, TkExcl ex = TkExcl{}, int* sx = nullptr) {
     const int lane = threadIdx.x & 63;
-    const int c = s_qn[r], n = s_ln[r];
-    for (int j = lane; j < n; j += 64) sl[j] = L[j];
-    uint2 e = lane < c ? sq[lane] : make_uint2(0u, 0xFFFFFFFFu);
-    unsigned long long q = lane < c ? topk_key(e) : 0ull;
+    int c = s_qn[r];
+    const int n = s_ln[r];
+    uint2 e;
+    unsigned long long q;
+    if constexpr (!EXCL) {
+        for (int j = lane; j < n; j += 64) sl[j] = L[j];
+        e = lane < c ? sq[lane] : make_uint2(0u, 0xFFFFFFFFu);
+        q = lane < c ? topk_key(e) : 0ull;
+    } else {
+        e = lane < c ? sq[lane] : make_uint2(0u, 0xFFFFFFFFu);
+        const int item = lane < c ? (item_idx ? item_idx[e.y] : (int)e.y) : 0;
+        bool drop = lane < c && ex.mask && ((ex.mask[item >> 5] >> (item & 31)) & 1u);
+        for (int j = lane; j < n; j += 64) sl[j] = L[j];
+        for (int j = lane; j < nx; j += 64) sx[j] = ex.items[xb + j];
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (lane < c && !drop && nx > 0) {
+#if defined(G4R_MUTATE) && G4R_MUTATE == 9      // test build: the search never matches the LAST item of the row's list
+            const int hi = nx - 1;
+#else
+            const int hi = nx;
+#endif
+            int a = 0, b = hi;
+            while (a < b) { const int mid = (a + b) >> 1; if (sx[mid] < item) a = mid + 1; else b = mid; }
+            drop = a < hi && sx[a] == item;
+        }
+        const bool keep = lane < c && !drop;
+        c = __popcll(__ballot(keep));
+        if (!keep) e = make_uint2(0u, 0xFFFFFFFFu);
+        q = keep ? topk_key(e) : 0ull;
+    }
 #pragma unroll
     for (int w = 2; w <= 64; w <<= 1)
 #pragma unroll
@@ -84,32 +135,51 @@ __device__ __forceinline__ void topk_merge_row(int r, uint2* L, int k, uint2* sq
 // k best of the row in key order, entries past the range's column count padded with column 0xFFFFFFFF (key 0).
 // STORED = false: the tile is computed as k_score_all computes it (one ascending-k fp32 MFMA chain from zero, + By, then the final
 // activation), so every score is bit-identical to g4r_predict_step's.  STORED = true: the tile is read from `sc` (ldo floats per row).
-template <bool STORED>
+// EXCL: the exclusions (one trailing TkExcl argument) apply at every merge (topk_merge_row), the per-wave scratch grows by the
+// row's list (TK_SCRATCH_WAVE_X).  EXCL = false takes no trailing argument, so its kernel arguments -- and with them its code --
+// are those of the unfiltered kernel.
+template <bool STORED, bool EXCL, typename... X>
 __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__ mp, const float* h, int mrows, const int* item_idx,
-                                                    long long n_sel, const float* sc, long long ldo, int k, int tpr, uint2* ws) {
+                                                    long long n_sel, const float* sc, long long ldo, int k, int tpr, uint2* ws,
+                                                    X... xs) {
+    static_assert(sizeof...(X) == (EXCL ? 1 : 0), "EXCL takes one TkExcl");
+    const TkExcl ex = tk_excl(xs...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, lg = lane >> 4;
     uint2* s_q = reinterpret_cast<uint2*>(smem);
     int* s_qn = reinterpret_cast<int*>(s_q + SC_BM * TK_Q);
     int* s_ln = s_qn + SC_BM;
     unsigned long long* s_thr = reinterpret_cast<unsigned long long*>(s_ln + SC_BM);
-    char* tail = reinterpret_cast<char*>(s_thr + SC_BM);
+    long long* s_xb = reinterpret_cast<long long*>(s_thr + SC_BM);      // (EXCL only)
+    int* s_xn = reinterpret_cast<int*>(s_xb + SC_BM);
+    char* tail = EXCL ? reinterpret_cast<char*>(s_xn + SC_BM) : reinterpret_cast<char*>(s_thr + SC_BM);
     float* sA = reinterpret_cast<float*>(tail);
     const int ldk = SC_KC + 2;
     float* sB = sA + SC_BM * ldk;
     int* sItem = reinterpret_cast<int*>(sB + TK_TN * ldk);
-    char* scratch = tail + wid * TK_SCRATCH_WAVE;
+    char* scratch = tail + wid * (EXCL ? TK_SCRATCH_WAVE_X : TK_SCRATCH_WAVE);
     uint2* sl = reinterpret_cast<uint2*>(scratch);
     unsigned long long* skq = reinterpret_cast<unsigned long long*>(scratch + TK_MAX * 8);
+    int* sx = reinterpret_cast<int*>(scratch + TK_SCRATCH_WAVE);
 
     const int rbase = blockIdx.y * SC_BM, range = blockIdx.x, R = gridDim.x;
     const long long c0 = (long long)range * tpr * TK_TN, c1 = min(n_sel, c0 + (long long)tpr * TK_TN);
     if (tid < SC_BM) { s_qn[tid] = 0; s_ln[tid] = 0; s_thr[tid] = 0ull; }
+    if constexpr (EXCL)
+        if (tid < SC_BM) {
+            const bool on = ex.offs && rbase + tid < mrows;
+            const long long b = on ? ex.offs[rbase + tid] : 0ll;
+            s_xb[tid] = b;
+            s_xn[tid] = on ? (int)(ex.offs[rbase + tid + 1] - b) : 0;
+        }
     __syncthreads();
     auto list = [&](int r) { return ws + ((size_t)(rbase + r) * R + range) * k; };
     auto merge_all = [&]() {
         for (int r = wid; r < SC_BM; r += 4)
-            if (s_qn[r] > 0) topk_merge_row(r, list(r), k, s_q + r * TK_Q, skq, sl, s_qn, s_ln, s_thr);
+            if (s_qn[r] > 0) {
+                if constexpr (EXCL) topk_merge_row<true>(r, list(r), k, s_q + r * TK_Q, skq, sl, s_qn, s_ln, s_thr, s_xb[r], s_xn[r], item_idx, ex, sx);
+                else topk_merge_row<false>(r, list(r), k, s_q + r * TK_Q, skq, sl, s_qn, s_ln, s_thr);
+            }
         __syncthreads();
     };
     for (long long n0 = c0; n0 < c1; n0 += TK_TN) {
@@ -206,6 +276,9 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
 
 // Stage 2.  One workgroup per row: the k-th largest key T of the row's nl * k entries by an MSB-first radix select (eight 8-bit
 // digits of the 64-bit key), then the k entries with key >= T (exactly k: keys are distinct), sorted in LDS, written out.
+// With exclusions (EXCL range kernels) the lists hold eligible entries and pads only; g4r_recommend_step_filtered refuses a row with
+// fewer than k eligible candidate positions, so the union of the row's lists still holds at least k real keys (every eligible
+// position is kept unless k better eligible ones of its range are) and "exactly k at or above T" still holds.
 __global__ __launch_bounds__(256) void k_topk_merge(const uint2* ws, int nl, int k, int* out_cols, float* out_scores) {
     __shared__ int hist[256];
     __shared__ int s_digit, s_need, s_cnt;
@@ -269,5 +342,7 @@ __global__ __launch_bounds__(256) void k_topk_merge(const uint2* ws, int nl, int
     }
 }
 
-template __global__ void k_topk_range<false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
-template __global__ void k_topk_range<true>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
+template __global__ void k_topk_range<false, false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
+template __global__ void k_topk_range<true, false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
+template __global__ void k_topk_range<false, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);
+template __global__ void k_topk_range<true, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);

@@ -722,21 +722,145 @@ class GRU4Rec:
             self._upload_weights(self._model)
         return self._model
 
-    def _predict_rows(self, session_ids, input_item_ids, batch):
+    def _predict_plan(self, session_ids, input_item_ids, batch):
+        """What _predict_rows will do for this call, computed without changing anything: (restart, session ids, changed, input item
+        indices).  restart: the prediction state starts over (first call, new `batch`, or reset by fit / loadmodel / evaluate_gpu)."""
+        in_idxs = self.itemidmap[input_item_ids].values
+        session_ids = np.asarray(session_ids)
+        restart = getattr(self, 'predict', None) is None or self.predict_batch != batch
+        changed = session_ids != (np.ones(batch) * -1 if restart else self.current_session)
+        return restart, session_ids, changed, in_idxs
+
+    def _predict_rows(self, session_ids, input_item_ids, batch, plan=None):
         """Session bookkeeping of a prediction call (gru4rec.py:712-717), shared by predict_next_batch / recommend_next_batch: (re)starts
-        the prediction state for `batch`, zeroes the hidden rows of changed sessions; returns (device model, input item indices)."""
+        the prediction state for `batch`, zeroes the hidden rows of changed sessions, records the inputs in the seen-history;
+        returns (device model, input item indices).  plan: this call's _predict_plan, when the caller has made it already."""
+        restart, session_ids, changed, in_idxs = plan if plan is not None else self._predict_plan(session_ids, input_item_ids, batch)
         m = self._ensure_model()
-        if self.predict is None or self.predict_batch != batch:
+        if restart:
             self.predict_batch = batch
             m.predict_begin(batch)
             self.current_session = np.ones(batch) * -1
             self.predict = True
-        session_ids = np.asarray(session_ids)
-        changed = session_ids != self.current_session
+            self._seen_start(batch)
         if changed.any():
             m.predict_hidden(zero_mask=changed.astype(np.uint8))
             self.current_session = session_ids.copy()
-        return m, self.itemidmap[input_item_ids].values
+        self._seen_record(changed, in_idxs)
+        return m, in_idxs
+
+    # seen-history of recommend_next_batch(exclude_seen=True): the item indices input to every slot since its session began, in a
+    # [batch, _SEEN_CAP] buffer with fill counts.  A slot that fills its row is compacted (sorted, de-duplicated) in one vectorised pass;
+    # a slot with more than G4R_EXCLUDE_MAX distinct items is marked overflowed (only its later exclude_seen calls refuse).
+    _SEEN_CAP = 2 * _native.G4R_EXCLUDE_MAX
+
+    @staticmethod
+    def _row_mask(changed, batch):
+        out = np.zeros(batch, dtype=bool)
+        v = np.ravel(changed)[:batch]
+        out[:len(v)] = v
+        return out
+
+    def _seen_start(self, batch):
+        self._seen = np.zeros((batch, self._SEEN_CAP), dtype=np.int32)
+        self._seen_n = np.zeros(batch, dtype=np.int32)
+        self._seen_over = np.zeros(batch, dtype=bool)
+
+    def _seen_record(self, changed, in_idxs):
+        if getattr(self, '_seen', None) is None or len(self._seen) != self.predict_batch:
+            self._seen_start(self.predict_batch)
+        reset = self._row_mask(changed, self.predict_batch)
+        self._seen_n[reset] = 0
+        self._seen_over[reset] = False
+        x = np.asarray(in_idxs, dtype=np.int32).ravel()[:self.predict_batch]
+        r = len(x)
+        if (self._seen_n[:r] >= self._SEEN_CAP).any():
+            self._seen_compact()
+        self._seen[np.arange(r), self._seen_n[:r]] = x
+        self._seen_n[:r] += 1
+
+    def _seen_compact(self):
+        pad = np.iinfo(np.int32).max
+        s = np.where(np.arange(self._SEEN_CAP) < self._seen_n[:, None], self._seen, pad)
+        s.sort(axis=1)
+        tail = s[:, 1:]
+        tail[tail == s[:, :-1]] = pad
+        s.sort(axis=1)
+        n = (s != pad).sum(axis=1)
+        over = n > _native.G4R_EXCLUDE_MAX
+        self._seen_over |= over
+        n[over] = 0
+        self._seen, self._seen_n = s, n.astype(np.int32)
+
+    def _seen_after(self, plan):
+        """(rows, item indices) the seen-history will hold for this call's rows once the call is made (its inputs included)."""
+        restart, _, changed, in_idxs = plan
+        x = np.asarray(in_idxs, dtype=np.int64).ravel()
+        r = len(x)
+        rows, items = [np.arange(r)], [x]
+        if not restart and getattr(self, '_seen', None) is not None and len(self._seen) >= r:
+            fresh = self._row_mask(changed, len(self._seen))[:r]
+            over = np.flatnonzero(self._seen_over[:r] & ~fresh)
+            if len(over):
+                raise ValueError('exclude_seen: row %d has seen more than G4R_EXCLUDE_MAX = %d distinct items in its session'
+                                 % (over[0], _native.G4R_EXCLUDE_MAX))
+            keep = (np.arange(self._SEEN_CAP) < self._seen_n[:r, None]) & ~fresh[:, None]
+            rr, cc = np.nonzero(keep)
+            rows.append(rr)
+            items.append(self._seen[rr, cc].astype(np.int64))
+        return np.concatenate(rows), np.concatenate(items)
+
+    def _exclusions(self, plan, k, cand_idx, exclude_seen, exclude, exclude_per_row):
+        """Checks and packs the exclusions of a recommend_next_batch call: (excl_offs, excl_items, excl_mask) of
+        g4r_recommend_step_filtered (None where there is nothing to exclude).  Raises before anything changes."""
+        rows = len(np.ravel(plan[3]))
+        n_items = len(self.itemidmap)
+        pr, pi = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
+        if exclude_per_row is not None:
+            if len(exclude_per_row) != rows:
+                raise ValueError('exclude_per_row holds %d lists, one per row (%d) is needed' % (len(exclude_per_row), rows))
+            lists = [x if isinstance(x, np.ndarray) else list(x) for x in exclude_per_row]
+            lens = np.array([len(x) for x in lists], dtype=np.int64)
+            if lens.sum():
+                pr.append(np.repeat(np.arange(rows), lens))
+                pi.append(self.itemidmap[np.concatenate([np.ravel(x) for x in lists if len(x)])].values.astype(np.int64))
+        if exclude_seen:
+            r, i = self._seen_after(plan)
+            pr.append(r)
+            pi.append(i)
+        gidx = np.zeros(0, dtype=np.int64)
+        if exclude is not None:
+            ex = exclude if isinstance(exclude, np.ndarray) else list(exclude)
+            if len(ex):
+                gidx = np.unique(self.itemidmap[np.ravel(ex)].values.astype(np.int64))
+        key = np.unique(np.concatenate(pr) * n_items + np.concatenate(pi))
+        r, it = key // n_items, key % n_items
+        counts = np.bincount(r, minlength=rows)
+        big = np.flatnonzero(counts > _native.G4R_EXCLUDE_MAX)
+        if len(big):
+            raise ValueError('row %d excludes %d distinct items (exclude_per_row and the items seen), more than G4R_EXCLUDE_MAX = %d'
+                             % (big[0], counts[big[0]], _native.G4R_EXCLUDE_MAX))
+        # eligible candidate positions per row (duplicate positions count): all - masked positions - positions of the row's other items
+        if cand_idx is None:
+            n_cand, n_masked, per_item = n_items, len(gidx), np.ones(len(it))
+        else:
+            n_cand, n_masked = len(cand_idx), int(np.isin(cand_idx, gidx).sum())
+            uc, cc = np.unique(cand_idx, return_counts=True)
+            pos = np.minimum(np.searchsorted(uc, it), max(len(uc) - 1, 0))
+            per_item = np.where(uc[pos] == it, cc[pos], 0) if len(uc) else np.zeros(len(it))
+        own = ~np.isin(it, gidx)
+        elig = n_cand - n_masked - np.bincount(r[own], weights=per_item[own], minlength=rows).astype(np.int64)
+        short = np.flatnonzero(elig < k)
+        if len(short):
+            raise ValueError('row %d has %d eligible candidate positions, fewer than k = %d' % (short[0], elig[short[0]], k))
+        offs = items = mask = None
+        if exclude_seen or exclude_per_row is not None:
+            offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            items = it.astype(np.int32)
+        if len(gidx):
+            mask = np.zeros((n_items + 31) // 32, dtype=np.uint32)
+            np.bitwise_or.at(mask, gidx >> 5, np.left_shift(1, gidx & 31).astype(np.uint32))
+        return offs, items, mask
 
     def predict_next_batch(self, session_ids, input_item_ids, predict_for_item_ids=None, batch=100):
         """Scores for the next item of every session in the batch.  Rows: items, columns: batch events."""
@@ -750,24 +874,40 @@ class GRU4Rec:
         preds = m.predict_step(in_idxs).T
         return pd.DataFrame(data=preds, index=self.itemidmap.index)
 
-    def recommend_next_batch(self, session_ids, input_item_ids, k=20, predict_for_item_ids=None, batch=100):
+    def recommend_next_batch(self, session_ids, input_item_ids, k=20, predict_for_item_ids=None, batch=100,
+                             exclude_seen=False, exclude=None, exclude_per_row=None):
         """Top-k next items of every session: (item_ids[len(session_ids), k], scores[len(session_ids), k] float32).
         Not in the reference.  Row r holds the k largest entries of column r of what predict_next_batch would return for the same
         call (score descending, equal scores by the lower candidate position, NaN last), the scores bit-identical to it; the
         candidates are all items in itemidmap order, or predict_for_item_ids in the given order.  The hidden state advances as in
-        predict_next_batch, so calls of the two may be interleaved.  Selection runs on the device: only k entries per row return."""
+        predict_next_batch, so calls of the two may be interleaved.  Selection runs on the device: only k entries per row return.
+
+        Exclusions (the union of the three; by item: every candidate position holding an excluded item is skipped):
+          exclude_seen     row r never receives an item input to slot r since that slot's session began (a new session id at that
+                           position, a new prediction state: first call, new `batch`, fit / loadmodel / evaluate_gpu), this call's
+                           input and inputs of predict_next_batch calls included;
+          exclude          item ids excluded in every row;
+          exclude_per_row  len(session_ids) iterables of item ids, one per row.
+        The rest keep their order and their predict_next_batch scores: softmax / softmax_logit scores are NOT renormalised over them.
+        A call is checked before anything changes (hidden state, current_session, seen-history): an unknown item id raises
+        KeyError; a row with more than G4R_EXCLUDE_MAX = 1024 distinct items in exclude_per_row plus the items seen, or with fewer
+        than k eligible candidate positions (duplicates count), raises ValueError."""
         if self.error_during_train:
             raise Exception
         n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
         if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
             raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
-        m, in_idxs = self._predict_rows(session_ids, input_item_ids, batch)
-        if predict_for_item_ids is not None:
-            cand = np.asarray(predict_for_item_ids)
-            cols, scores = m.recommend_step(in_idxs, self.itemidmap[predict_for_item_ids].values, int(k))
+        plan = self._predict_plan(session_ids, input_item_ids, batch)
+        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
+        filtered = exclude_seen or exclude is not None or exclude_per_row is not None
+        if filtered:
+            offs, items, mask = self._exclusions(plan, int(k), iidx, exclude_seen, exclude, exclude_per_row)
+        m, in_idxs = self._predict_rows(session_ids, input_item_ids, batch, plan=plan)
+        if filtered:
+            cols, scores = m.recommend_step_filtered(in_idxs, iidx, int(k), offs, items, mask)
         else:
-            cand = self.itemidmap.index.values
-            cols, scores = m.recommend_step(in_idxs, None, int(k))
+            cols, scores = m.recommend_step(in_idxs, iidx, int(k))
+        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
         return cand[cols], scores
 
     def symbolic_predict(self, X, Y, M, items, batch_size):
@@ -779,7 +919,7 @@ class GRU4Rec:
 
     def __getstate__(self):
         st = dict(self.__dict__)
-        for k in ('_model', '_plan', '_plan_key', '_data_items', '_offsets', '_base_order', '_dist', '_loss_id', '_final', '_hidden', '_pop64', '_cpu_store'):
+        for k in ('_model', '_plan', '_plan_key', '_data_items', '_offsets', '_base_order', '_dist', '_loss_id', '_final', '_hidden', '_pop64', '_cpu_store', '_seen', '_seen_n', '_seen_over'):
             st.pop(k, None)
         st['predict'] = None
         return st

@@ -178,6 +178,18 @@ int g4r_rank_targets(g4r_model* m, const int32_t* target_col, int32_t mrows, int
 int g4r_recommend_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
                        int32_t k, int32_t* out_cols, float* out_scores);
 
+/* not in the reference: g4r_recommend_step with excluded items.  Candidate positions whose item is excluded for a row are never
+ * returned for it; the order and the scores of the rest are g4r_recommend_step's (softmax is NOT renormalised over them).
+ * excl_offs[mrows + 1]: row r excludes the item indices excl_items[excl_offs[r] .. excl_offs[r + 1]) (any order, duplicates
+ * allowed, at most G4R_EXCLUDE_MAX distinct per row); NULL = no per-row lists.  excl_mask[ceil(n_items / 32)]: bit (i & 31) of
+ * word i >> 5 excludes item index i in every row; NULL = no mask.  Everything is checked before any launch (the hidden state is
+ * not advanced by a refused call): offsets monotone, items in range, and at least k eligible candidate positions in every row
+ * (duplicate positions count).  With both NULL this is g4r_recommend_step. */
+#define G4R_EXCLUDE_MAX 1024
+int g4r_recommend_step_filtered(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
+                                int32_t k, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
+                                int32_t* out_cols, float* out_scores);
+
 /* The whole of evaluation.evaluate_gpu (evaluation.py:86-147) as ONE call with no host round trip per step: the
  * session-parallel test loop comes as a plan (g4r_build_plan on the test sessions in id order with n_sample = 1: the loop of
  * evaluation.py:96-139 is the loop of fit), every step runs the GRU forward, scores all items (items == NULL) or
