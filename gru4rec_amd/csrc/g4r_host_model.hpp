@@ -112,7 +112,18 @@ struct g4r_model {
     int* p_xitems = nullptr;                     // the rows' sorted item lists,
     unsigned* p_xmask = nullptr;                 // the global item bit mask
     int64_t p_xoffs_cap = 0, p_xitems_cap = 0, p_xmask_cap = 0;
-    unsigned tie_ctr = 0;                        // evaluation step counter of the 'tiebreaking' noise stream
+    // stateless replay of g4r_recommend_sessions, apart from the prediction state above: per layer a hidden ping-pong, the output,
+    // the GRU scratch and the staging of the supplied initial / the final rows (chunk order), all for r_cap rows; the step-major
+    // input items, the sort map and lengths of a chunk; its own score matrix (softmax / softmax_logit)
+    int r_cap = 0;
+    float* rH[G4R_MAX_LAYERS][2] = {{nullptr}};
+    float* rhout[G4R_MAX_LAYERS] = {nullptr};
+    float *rVc[G4R_MAX_LAYERS] = {nullptr}, *rz[G4R_MAX_LAYERS] = {nullptr}, *rHr[G4R_MAX_LAYERS] = {nullptr};
+    float* rio[G4R_MAX_LAYERS] = {nullptr};
+    int *r_in = nullptr, *r_perm = nullptr, *r_len = nullptr;
+    float* r_scores = nullptr;
+    int64_t r_in_cap = 0, r_scores_cap = 0;
+    unsigned tie_ctr = 0;                       // evaluation step counter of the 'tiebreaking' noise stream
     // rccl
     ncclComm_t comm = nullptr;
     bool comm_ready = false;

@@ -1,6 +1,6 @@
 // g4r_host_predict.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
 // instantiated there).  Holds: prediction and evaluation: g4r_predict_*, g4r_rank_targets, g4r_recommend_step(_filtered),
-// g4r_evaluate.
+// g4r_recommend_sessions, g4r_evaluate.
 // ------------------------------------------------------------------------------------------------ prediction
 int g4r_predict_begin(g4r_model* m, int32_t batch) {
     if (!m || batch < 1) return fail("bad batch");
@@ -123,18 +123,25 @@ int g4r_rank_targets(g4r_model* m, const int32_t* target_col, int32_t mrows, int
     return 0;
 }
 
-// forward GRU of `mrows` prediction rows (input items on the device): every layer's hidden state advances one step and the top
-// layer's output is left in phout[n_layers - 1] (shared by predict_forward / g4r_recommend_step)
-static void predict_gru(g4r_model* m, const int* d_in_idx, int mrows) {
+// the buffers one forward GRU step works on: per layer the hidden ping-pong, the output and the scratch (the prediction state's,
+// or the replay's of g4r_recommend_sessions)
+struct GruBufs { float* (*H)[2]; float** hout; float** Vc; float** z; float** Hr; };
+static GruBufs predict_bufs(g4r_model* m) { return GruBufs{m->pH, m->phout, m->pVc, m->pz, m->pHr}; }
+static GruBufs replay_bufs(g4r_model* m) { return GruBufs{m->rH, m->rhout, m->rVc, m->rz, m->rHr}; }
+
+// forward GRU of rows [0, mrows) (input items on the device): every layer reads H[l][par], writes H[l][par ^ 1] and hout[l].  Rows
+// from mrows on are neither read nor written: every load of k_gru_p1 / k_gru_p2 is clamped to or masked by row < M, and both
+// epilogues return for row >= M (the replay relies on it: a finished row keeps its last state and output)
+static void gru_step(g4r_model* m, const GruBufs& b, int par, const int* d_in_idx, int mrows) {
     DevModel& d = m->dm;
     for (int l = 0; l < d.n_layers; ++l) {
         GruFwdPredict pa;
         pa.in_idx = (GP(const int))d_in_idx;
-        pa.ysrc = (GP(const float))(l > 0 ? m->phout[l - 1] : nullptr);
-        pa.Hcur = (GP(const float))m->pH[l][m->ppar];
-        pa.Hnext = (GP(float))m->pH[l][m->ppar ^ 1];
-        pa.hout = (GP(float))m->phout[l];
-        pa.Vc = (GP(float))m->pVc[l]; pa.z = (GP(float))m->pz[l]; pa.Hr = (GP(float))m->pHr[l];
+        pa.ysrc = (GP(const float))(l > 0 ? b.hout[l - 1] : nullptr);
+        pa.Hcur = (GP(const float))b.H[l][par];
+        pa.Hnext = (GP(float))b.H[l][par ^ 1];
+        pa.hout = (GP(float))b.hout[l];
+        pa.Vc = (GP(float))b.Vc[l]; pa.z = (GP(float))b.z[l]; pa.Hr = (GP(float))b.Hr[l];
         pa.M = mrows;
         if (wide_layer(d.D[l]))
             hipLaunchKernelGGL(k_gru_p1_n64, dim3(cdiv(3 * d.D[l], 64), cdiv(mrows, GT_BM)), dim3(GT_NTH_FEW), SMEM_P1_N64, m->stream,
@@ -151,7 +158,22 @@ static void predict_gru(g4r_model* m, const int* d_in_idx, int mrows) {
             else hipLaunchKernelGGL(k_gru_p2_w4, g2, dim3(GT_NTH), SMEM_NN, m->stream, (const DevModel*)m->d_dm, (StepState*)nullptr, l, 0, pa);
         }
     }
+}
+
+// one step of the prediction state: the top layer's output is left in phout[n_layers - 1] (shared by predict_forward /
+// g4r_recommend_step)
+static void predict_gru(g4r_model* m, const int* d_in_idx, int mrows) {
+    gru_step(m, predict_bufs(m), m->ppar, d_in_idx, mrows);
     m->ppar ^= 1;
+}
+
+// scores of rows [0, mrows) of hsrc against the candidates -> out (row stride ldo), final activation applied (softmax per row)
+static void score_rows(g4r_model* m, const float* hsrc, int mrows, const int* d_items, int64_t n_sel, float* out, int64_t ldo) {
+    const DevModel& d = m->dm;
+    const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);   // gru4rec.py:499-500
+    hipLaunchKernelGGL(k_score_store, dim3(cdiv(n_sel, 32), cdiv(mrows, SC_BM)), dim3(256), m->smem_score, m->stream, (const DevModel*)m->d_dm,
+                       hsrc, (int)mrows, d_items, (long long)n_sel, out, (long long)ldo, sm ? 0 : 1, (int*)nullptr, 0LL, (const int*)nullptr, 0u);
+    if (sm) hipLaunchKernelGGL(k_softmax_rows, dim3(mrows), dim3(256), 0, m->stream, out, (long long)n_sel, (long long)ldo);
 }
 
 // forward GRU + scores of `mrows` rows whose input items sit on the device (shared by g4r_predict_step / g4r_evaluate)
@@ -185,9 +207,7 @@ static int predict_forward(g4r_model* m, const int* d_in_idx, int mrows, const i
         m->p_nsel = 0; m->p_ldo = ldo;        // no score matrix to read back
         return 0;
     }
-    hipLaunchKernelGGL(k_score_store, dim3(cdiv(n_sel, 32), cdiv(mrows, SC_BM)), dim3(256), m->smem_score, m->stream, (const DevModel*)m->d_dm,
-                       hsrc, (int)mrows, d_items, (long long)n_sel, m->p_scores, (long long)ldo, sm ? 0 : 1, (int*)nullptr, 0LL, (const int*)nullptr, 0u);
-    if (sm) hipLaunchKernelGGL(k_softmax_rows, dim3(mrows), dim3(256), 0, m->stream, m->p_scores, (long long)n_sel, (long long)ldo);
+    score_rows(m, hsrc, mrows, d_items, n_sel, m->p_scores, ldo);
     HIPCHK(hipGetLastError());
     m->p_nsel = n_sel; m->p_ldo = ldo;
     return 0;
@@ -203,19 +223,12 @@ static int recommend_check(g4r_model* m, const int32_t* item_idx, int64_t n_sel,
     return 0;
 }
 
-// GRU step + selection of a checked call whose inputs predict_inputs has uploaded; ex (device exclusions) NULL: the unfiltered kernels
-static int recommend_run(g4r_model* m, int32_t mrows, const int32_t* item_idx, int64_t n_sel, int32_t k, const TkExcl* ex,
-                         int32_t* out_cols, float* out_scores) {
-    DevModel& d = m->dm;
-    const int* d_items = item_idx ? (const int*)m->p_items : (const int*)nullptr;
+// selection of rows [0, mrows) of hsrc (the top layer's output) into p_tcols / p_tscores, enqueued only.  scores / ldo: the same
+// rows' materialised scores (softmax / softmax_logit), unused otherwise.  ex (device exclusions) NULL: the unfiltered kernels
+static int topk_select(g4r_model* m, const float* hsrc, int32_t mrows, const int* d_items, int64_t n_sel, int32_t k, const TkExcl* ex,
+                       const float* scores, int64_t ldo) {
+    const DevModel& d = m->dm;
     const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
-    // softmax needs the whole row first: the scores are materialised exactly as g4r_predict_step materialises them, then selected;
-    // an element-wise final activation is selected as the tiles are scored (nothing stored)
-    if (sm) {
-        if (predict_forward(m, m->p_in, mrows, d_items, n_sel, nullptr)) return -1;
-    } else {
-        predict_gru(m, m->p_in, mrows);
-    }
     // column ranges: (row blocks) x (ranges) workgroups, one per compute unit (the LDS of k_topk_range admits one per CU)
     const int row_blocks = cdiv(mrows, SC_BM);
     const int64_t tiles = (n_sel + TK_TN - 1) / TK_TN;
@@ -236,14 +249,13 @@ static int recommend_run(g4r_model* m, int32_t mrows, const int32_t* item_idx, i
             m->p_tout_cap = nout;
         }
     }
-    const float* hsrc = (const float*)m->phout[d.n_layers - 1];
     const dim3 grid(R, row_blocks);
     if (sm && !ex)
         hipLaunchKernelGGL(k_topk_stored, grid, dim3(256), TK_SMEM_STORED, m->stream, (const DevModel*)m->d_dm, hsrc,
-                           (int)mrows, d_items, (long long)n_sel, (const float*)m->p_scores, (long long)m->p_ldo, (int)k, tpr, m->p_topk);
+                           (int)mrows, d_items, (long long)n_sel, scores, (long long)ldo, (int)k, tpr, m->p_topk);
     else if (sm)
         hipLaunchKernelGGL(k_topk_stored_x, grid, dim3(256), TK_SMEM_STORED_X, m->stream, (const DevModel*)m->d_dm, hsrc,
-                           (int)mrows, d_items, (long long)n_sel, (const float*)m->p_scores, (long long)m->p_ldo, (int)k, tpr, m->p_topk, *ex);
+                           (int)mrows, d_items, (long long)n_sel, scores, (long long)ldo, (int)k, tpr, m->p_topk, *ex);
     else if (!ex)
         hipLaunchKernelGGL(k_topk_fused, grid, dim3(256), TK_SMEM_FUSED, m->stream, (const DevModel*)m->d_dm, hsrc,
                            (int)mrows, d_items, (long long)n_sel, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk);
@@ -252,6 +264,24 @@ static int recommend_run(g4r_model* m, int32_t mrows, const int32_t* item_idx, i
                            (int)mrows, d_items, (long long)n_sel, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk, *ex);
     hipLaunchKernelGGL(k_topk_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->p_topk, R, (int)k, m->p_tcols, m->p_tscores);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// GRU step + selection of a checked call whose inputs predict_inputs has uploaded; ex (device exclusions) NULL: the unfiltered kernels
+static int recommend_run(g4r_model* m, int32_t mrows, const int32_t* item_idx, int64_t n_sel, int32_t k, const TkExcl* ex,
+                         int32_t* out_cols, float* out_scores) {
+    DevModel& d = m->dm;
+    const int* d_items = item_idx ? (const int*)m->p_items : (const int*)nullptr;
+    const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
+    // softmax needs the whole row first: the scores are materialised exactly as g4r_predict_step materialises them, then selected;
+    // an element-wise final activation is selected as the tiles are scored (nothing stored)
+    if (sm) {
+        if (predict_forward(m, m->p_in, mrows, d_items, n_sel, nullptr)) return -1;
+    } else {
+        predict_gru(m, m->p_in, mrows);
+    }
+    if (topk_select(m, (const float*)m->phout[d.n_layers - 1], mrows, d_items, n_sel, k, ex, (const float*)m->p_scores, m->p_ldo)) return -1;
+    const int64_t nout = (int64_t)mrows * k;
     HIPCHK(hipMemcpyAsync(out_cols, m->p_tcols, nout * sizeof(int), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipMemcpyAsync(out_scores, m->p_tscores, nout * sizeof(float), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -265,16 +295,13 @@ int g4r_recommend_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const
     return recommend_run(m, mrows, item_idx, n_sel, k, nullptr, out_cols, out_scores);
 }
 
-int g4r_recommend_step_filtered(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
-                                int32_t k, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
-                                int32_t* out_cols, float* out_scores) {
-    if (!excl_offs && !excl_mask) return g4r_recommend_step(m, in_idx, mrows, item_idx, n_sel, k, out_cols, out_scores);
-    if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores)) return -1;
-    if (predict_inputs(m, in_idx, mrows, item_idx, &n_sel)) return -1;      // (uploads only: the state advances in recommend_run)
+// the exclusion checks shared by g4r_recommend_step_filtered / g4r_recommend_sessions: every row's list is checked, sorted and
+// de-duplicated into offs / items (left empty without excl_offs); a row with fewer than k eligible candidate positions is refused
+static int excl_pack(g4r_model* m, int32_t mrows, const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs,
+                     const int32_t* excl_items, const uint32_t* excl_mask, std::vector<long long>& offs, std::vector<int32_t>& items) {
     const int64_t I = m->dm.n_items, nw = (I + 31) / 32;
-    // every row's list: checked, sorted, de-duplicated
-    std::vector<long long> offs;
-    std::vector<int32_t> items;
+    offs.clear();
+    items.clear();
     if (excl_offs) {
         if (excl_offs[0] < 0) return fail("excl_offs[0] is negative");
         for (int r = 0; r < mrows; ++r)
@@ -331,8 +358,15 @@ int g4r_recommend_step_filtered(g4r_model* m, const int32_t* in_idx, int32_t mro
             return fail("row " + std::to_string(r) + " has " + std::to_string(n_cand - gone) + " eligible candidate positions, fewer than k = " +
                         std::to_string(k));
     }
-    // upload (into buffers that only grow), then the filtered selection
-    if (excl_offs) {
+    return 0;
+}
+
+// upload of packed exclusions (into buffers that only grow, stream-ordered) -> *ex, the device view; has_lists: offs / items hold
+// per-row lists
+static int excl_upload(g4r_model* m, bool has_lists, const std::vector<long long>& offs, const std::vector<int32_t>& items,
+                       const uint32_t* excl_mask, TkExcl* ex) {
+    const int64_t nw = ((int64_t)m->dm.n_items + 31) / 32;
+    if (has_lists) {
         if ((int64_t)offs.size() > m->p_xoffs_cap || (int64_t)items.size() > m->p_xitems_cap) {
             HIPCHK(hipStreamSynchronize(m->stream));
             if ((int64_t)offs.size() > m->p_xoffs_cap) {
@@ -358,9 +392,185 @@ int g4r_recommend_step_filtered(g4r_model* m, const int32_t* in_idx, int32_t mro
         }
         HIPCHK(hipMemcpyAsync(m->p_xmask, excl_mask, (size_t)nw * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
     }
-    const TkExcl ex = {excl_offs ? (const long long*)m->p_xoffs : nullptr, excl_offs ? (const int*)m->p_xitems : nullptr,
-                       excl_mask ? (const unsigned*)m->p_xmask : nullptr};
+    *ex = TkExcl{has_lists ? (const long long*)m->p_xoffs : nullptr, has_lists ? (const int*)m->p_xitems : nullptr,
+                 excl_mask ? (const unsigned*)m->p_xmask : nullptr};
+    return 0;
+}
+
+int g4r_recommend_step_filtered(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
+                                int32_t k, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
+                                int32_t* out_cols, float* out_scores) {
+    if (!excl_offs && !excl_mask) return g4r_recommend_step(m, in_idx, mrows, item_idx, n_sel, k, out_cols, out_scores);
+    if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores)) return -1;
+    if (predict_inputs(m, in_idx, mrows, item_idx, &n_sel)) return -1;      // (uploads only: the state advances in recommend_run)
+    std::vector<long long> offs;
+    std::vector<int32_t> items;
+    if (excl_pack(m, mrows, item_idx, n_sel, k, excl_offs, excl_items, excl_mask, offs, items)) return -1;
+    TkExcl ex;
+    if (excl_upload(m, excl_offs != nullptr, offs, items, excl_mask, &ex)) return -1;
     return recommend_run(m, mrows, item_idx, n_sel, k, &ex, out_cols, out_scores);
+}
+
+// ------------------------------------------------------------------------------------------------ stateless session replay
+// Rows per chunk of g4r_recommend_sessions: its score matrix (softmax / softmax_logit) is then never larger than g4r_recommend_step's
+// at 512 rows.  G4R_SESSIONS_CHUNK > 0 (read per call) forces a smaller chunk: tests show the results do not depend on it.
+#define G4R_REPLAY_CHUNK 512
+
+// the replay buffers for chunks of `rows` rows and n_in step-major input items (grow only)
+static int replay_reserve(g4r_model* m, int rows, int64_t n_in) {
+    const DevModel& d = m->dm;
+    if (rows > m->r_cap) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        m->r_cap = 0;
+        for (int l = 0; l < d.n_layers; ++l) {
+            float** bufs[] = {&m->rH[l][0], &m->rH[l][1], &m->rhout[l], &m->rVc[l], &m->rz[l], &m->rHr[l], &m->rio[l]};
+            for (float** b : bufs) {
+                dfree(m, *b);
+                *b = nullptr;
+                if (dalloc(m, b, (size_t)rows * d.D[l])) return -1;
+            }
+        }
+        dfree(m, m->r_perm); dfree(m, m->r_len);
+        m->r_perm = m->r_len = nullptr;
+        if (dalloc(m, &m->r_perm, (size_t)rows, false) || dalloc(m, &m->r_len, (size_t)rows, false)) return -1;
+        m->r_cap = rows;
+    }
+    if (n_in > m->r_in_cap) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        dfree(m, m->r_in);
+        m->r_in = nullptr;
+        m->r_in_cap = 0;
+        if (dalloc(m, &m->r_in, (size_t)n_in, false)) return -1;
+        m->r_in_cap = n_in;
+    }
+    return 0;
+}
+
+int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                           const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs, const int32_t* excl_items,
+                           const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, float* const* out_hidden) {
+    // ---- every check before any device work (nothing here has state to advance, but a refused call launches nothing)
+    if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores)) return -1;
+    if (!hist_offs || !hist_items) return fail("null argument");
+    if (n < 1) return fail("n must be positive");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    const DevModel& d = m->dm;
+    const int L = d.n_layers;
+    if (hist_offs[0] < 0) return fail("hist_offs[0] is negative");
+    for (int i = 0; i < n; ++i)
+        if (hist_offs[i + 1] <= hist_offs[i]) return fail("history " + std::to_string(i) + " is empty (hist_offs must rise strictly)");
+    for (int64_t j = hist_offs[0]; j < hist_offs[n]; ++j)
+        if (hist_items[j] < 0 || hist_items[j] >= d.n_items) return fail("history item index out of range");
+    if (!item_idx) n_sel = d.n_items;
+    for (int64_t p = 0; item_idx && p < n_sel; ++p)
+        if (item_idx[p] < 0 || item_idx[p] >= d.n_items) return fail("item index out of range");
+    for (int l = 0; l < L; ++l) {
+        if (h0 && !h0[l]) return fail("null argument (h0[" + std::to_string(l) + "])");
+        if (out_hidden && !out_hidden[l]) return fail("null argument (out_hidden[" + std::to_string(l) + "])");
+    }
+    std::vector<long long> xoffs;
+    std::vector<int32_t> xitems;
+    if ((excl_offs || excl_mask) && excl_pack(m, n, item_idx, n_sel, k, excl_offs, excl_items, excl_mask, xoffs, xitems)) return -1;
+    const bool excl = excl_offs || excl_mask;
+    // ---- buffers and the call-wide uploads
+    const int env_c = env_int("G4R_SESSIONS_CHUNK", 0);
+    const int C = std::min<int>(n, env_c > 0 ? std::min(env_c, G4R_REPLAY_CHUNK) : G4R_REPLAY_CHUNK);
+    const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
+    const int64_t ldo = (n_sel + 3) & ~3LL;
+    if (sm && (int64_t)C * ldo > m->r_scores_cap) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        dfree(m, m->r_scores);
+        m->r_scores = nullptr;
+        m->r_scores_cap = 0;
+        if (dalloc(m, &m->r_scores, (size_t)C * ldo, false)) return -1;
+        m->r_scores_cap = (int64_t)C * ldo;
+    }
+    if (item_idx) {
+        if (n_sel > m->p_items_cap) {
+            HIPCHK(hipStreamSynchronize(m->stream));
+            dfree(m, m->p_items);
+            m->p_items = nullptr;
+            m->p_items_cap = 0;
+            if (dalloc(m, &m->p_items, (size_t)n_sel, false)) return -1;
+            m->p_items_cap = n_sel;
+        }
+        HIPCHK(hipMemcpyAsync(m->p_items, item_idx, n_sel * sizeof(int), hipMemcpyHostToDevice, m->stream));
+    }
+    const int* d_items = item_idx ? (const int*)m->p_items : (const int*)nullptr;
+    const GruBufs rb = replay_bufs(m);
+    std::vector<int> perm, len;
+    std::vector<int32_t> steps, tcols((size_t)C * k);
+    std::vector<float> tscores((size_t)C * k);
+    std::vector<long long> coffs;
+    std::vector<int32_t> citems;
+    // ---- chunk by chunk: enqueue the replay of every step and the selection, then synchronise once
+    for (int c0 = 0; c0 < n; c0 += C) {
+        const int Cc = std::min(C, n - c0);
+        // rows sorted by history length, descending (stable): step t runs on the prefix of rows still active
+        perm.resize(Cc);
+        for (int r = 0; r < Cc; ++r) perm[r] = r;
+        auto hlen = [&](int r) { return hist_offs[c0 + r + 1] - hist_offs[c0 + r]; };
+        std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return hlen(a) > hlen(b); });
+        len.resize(Cc);
+        for (int r = 0; r < Cc; ++r) len[r] = (int)hlen(perm[r]);
+        const int T = len[0];
+        // input items of every step, step-major [T][Cc] (rows that have finished by step t: 0, never read)
+        steps.assign((size_t)T * Cc, 0);
+        for (int r = 0; r < Cc; ++r) {
+            const int32_t* h = hist_items + hist_offs[c0 + perm[r]];
+            for (int t = 0; t < len[r]; ++t) steps[(size_t)t * Cc + r] = h[t];
+        }
+        if (replay_reserve(m, Cc, (int64_t)T * Cc)) return -1;
+        HIPCHK(hipMemcpyAsync(m->r_in, steps.data(), steps.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(m->r_perm, perm.data(), Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(m->r_len, len.data(), Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
+        for (int l = 0; l < L; ++l) {
+            if (h0) HIPCHK(hipMemcpyAsync(m->rio[l], h0[l] + (size_t)c0 * d.D[l], (size_t)Cc * d.D[l] * sizeof(float), hipMemcpyHostToDevice, m->stream));
+            hipLaunchKernelGGL(k_replay_begin, dim3(cdiv((long long)Cc * d.D[l], 256)), dim3(256), 0, m->stream, m->rH[l][0],
+                               h0 ? (const float*)m->rio[l] : (const float*)nullptr, (const int*)m->r_perm, Cc, d.D[l]);
+        }
+        // step t: sorted rows [0, M_t) (M_t = rows with len > t), H[t & 1] -> H[(t + 1) & 1].  A row that has finished is never
+        // written again (gru_step), so the top layer's rhout row keeps its last output and its state stays in H[len & 1]
+        int Mt = Cc;
+        for (int t = 0; t < T; ++t) {
+            while (Mt > 0 && len[Mt - 1] <= t) --Mt;
+            gru_step(m, rb, t & 1, (const int*)m->r_in + (size_t)t * Cc, Mt);
+        }
+        const float* hsrc = (const float*)m->rhout[L - 1];
+        if (sm) score_rows(m, hsrc, Cc, d_items, n_sel, m->r_scores, ldo);
+        TkExcl ex;
+        if (excl) {
+            // the chunk's lists in sorted row order (each already sorted and de-duplicated by excl_pack)
+            coffs.assign(1, 0);
+            citems.clear();
+            if (excl_offs)
+                for (int r = 0; r < Cc; ++r) {
+                    const int i = c0 + perm[r];
+                    citems.insert(citems.end(), xitems.begin() + xoffs[i], xitems.begin() + xoffs[i + 1]);
+                    coffs.push_back((long long)citems.size());
+                }
+            if (excl_upload(m, excl_offs != nullptr, coffs, citems, excl_mask, &ex)) return -1;
+        }
+        if (topk_select(m, hsrc, Cc, d_items, n_sel, k, excl ? &ex : nullptr, (const float*)m->r_scores, ldo)) return -1;
+        HIPCHK(hipMemcpyAsync(tcols.data(), m->p_tcols, (size_t)Cc * k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(tscores.data(), m->p_tscores, (size_t)Cc * k * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        if (out_hidden)
+            for (int l = 0; l < L; ++l) {
+                hipLaunchKernelGGL(k_replay_final, dim3(cdiv((long long)Cc * d.D[l], 256)), dim3(256), 0, m->stream, m->rio[l],
+                                   (const float*)m->rH[l][0], (const float*)m->rH[l][1], (const int*)m->r_perm, (const int*)m->r_len,
+                                   Cc, d.D[l], T);
+                HIPCHK(hipMemcpyAsync(out_hidden[l] + (size_t)c0 * d.D[l], m->rio[l], (size_t)Cc * d.D[l] * sizeof(float),
+                                      hipMemcpyDeviceToHost, m->stream));
+            }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(m->stream));
+        // sorted row r is session c0 + perm[r]
+        for (int r = 0; r < Cc; ++r) {
+            memcpy(out_cols + (size_t)(c0 + perm[r]) * k, tcols.data() + (size_t)r * k, (size_t)k * sizeof(int32_t));
+            memcpy(out_scores + (size_t)(c0 + perm[r]) * k, tscores.data() + (size_t)r * k, (size_t)k * sizeof(float));
+        }
+    }
+    return 0;
 }
 
 int g4r_evaluate(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, const uint8_t* reset, const int32_t* M, int64_t T,

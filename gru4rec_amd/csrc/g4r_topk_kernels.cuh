@@ -346,3 +346,30 @@ template __global__ void k_topk_range<false, false>(const DevModel*, const float
 template __global__ void k_topk_range<true, false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
 template __global__ void k_topk_range<false, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);
 template __global__ void k_topk_range<true, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);
+
+// ---- stateless replay of session histories (g4r_recommend_sessions) ---------------------------------------------------------
+// A chunk's rows are sorted by history length, descending; perm[r] is the chunk row (caller's order) of sorted row r, len[r] its
+// length.  Step t runs the prediction GRU kernels on sorted rows [0, M_t), reading the ping-pong buffer H[t & 1] and writing
+// H[(t + 1) & 1], so a row's state after its last step lies in H[len & 1].
+// k_replay_begin: sorted row r of one layer's H[0] <- the supplied initial row perm[r] (src: [rows][W], chunk order), or zeros
+__global__ __launch_bounds__(256) void k_replay_begin(float* H0, const float* src, const int* perm, int rows, int W) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)rows * W) return;
+    const int r = (int)(e / W), j = (int)(e - (long long)r * W);
+    H0[e] = src ? src[(size_t)perm[r] * W + j] : 0.f;
+}
+// k_replay_final: dst[perm[r]] (chunk order) <- sorted row r's final state, taken from the buffer its own length's parity picks.
+// tmax: the chunk's longest history (len[0])
+__global__ __launch_bounds__(256) void k_replay_final(float* dst, const float* H0, const float* H1, const int* perm, const int* len,
+                                                      int rows, int W, int tmax) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)rows * W) return;
+    const int r = (int)(e / W), j = (int)(e - (long long)r * W);
+#if defined(G4R_MUTATE) && G4R_MUTATE == 10      // test build: every row read from the buffer of the chunk's longest history
+    const int par = tmax & 1;
+#else
+    const int par = len[r] & 1;
+    (void)tmax;
+#endif
+    dst[(size_t)perm[r] * W + j] = (par ? H1 : H0)[e];
+}

@@ -813,7 +813,12 @@ class GRU4Rec:
     def _exclusions(self, plan, k, cand_idx, exclude_seen, exclude, exclude_per_row):
         """Checks and packs the exclusions of a recommend_next_batch call: (excl_offs, excl_items, excl_mask) of
         g4r_recommend_step_filtered (None where there is nothing to exclude).  Raises before anything changes."""
-        rows = len(np.ravel(plan[3]))
+        seen = self._seen_after(plan) if exclude_seen else None
+        return self._pack_exclusions(len(np.ravel(plan[3])), k, cand_idx, seen, 'the items seen', exclude, exclude_per_row)
+
+    def _pack_exclusions(self, rows, k, cand_idx, extra, extra_name, exclude, exclude_per_row):
+        """_exclusions for `rows` rows; extra: (rows, item indices) the call adds to the per-row lists (the items seen, the
+        histories) or None; extra_name names them in the G4R_EXCLUDE_MAX error."""
         n_items = len(self.itemidmap)
         pr, pi = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
         if exclude_per_row is not None:
@@ -824,10 +829,9 @@ class GRU4Rec:
             if lens.sum():
                 pr.append(np.repeat(np.arange(rows), lens))
                 pi.append(self.itemidmap[np.concatenate([np.ravel(x) for x in lists if len(x)])].values.astype(np.int64))
-        if exclude_seen:
-            r, i = self._seen_after(plan)
-            pr.append(r)
-            pi.append(i)
+        if extra is not None:
+            pr.append(np.asarray(extra[0], dtype=np.int64))
+            pi.append(np.asarray(extra[1], dtype=np.int64))
         gidx = np.zeros(0, dtype=np.int64)
         if exclude is not None:
             ex = exclude if isinstance(exclude, np.ndarray) else list(exclude)
@@ -838,8 +842,8 @@ class GRU4Rec:
         counts = np.bincount(r, minlength=rows)
         big = np.flatnonzero(counts > _native.G4R_EXCLUDE_MAX)
         if len(big):
-            raise ValueError('row %d excludes %d distinct items (exclude_per_row and the items seen), more than G4R_EXCLUDE_MAX = %d'
-                             % (big[0], counts[big[0]], _native.G4R_EXCLUDE_MAX))
+            raise ValueError('row %d excludes %d distinct items (exclude_per_row and %s), more than G4R_EXCLUDE_MAX = %d'
+                             % (big[0], counts[big[0]], extra_name, _native.G4R_EXCLUDE_MAX))
         # eligible candidate positions per row (duplicate positions count): all - masked positions - positions of the row's other items
         if cand_idx is None:
             n_cand, n_masked, per_item = n_items, len(gidx), np.ones(len(it))
@@ -854,7 +858,7 @@ class GRU4Rec:
         if len(short):
             raise ValueError('row %d has %d eligible candidate positions, fewer than k = %d' % (short[0], elig[short[0]], k))
         offs = items = mask = None
-        if exclude_seen or exclude_per_row is not None:
+        if extra is not None or exclude_per_row is not None:
             offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
             items = it.astype(np.int32)
         if len(gidx):
@@ -909,6 +913,62 @@ class GRU4Rec:
             cols, scores = m.recommend_step(in_idxs, iidx, int(k))
         cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
         return cand[cols], scores
+
+    def recommend_sessions(self, histories, k=20, predict_for_item_ids=None, exclude_history=False, exclude=None, exclude_per_row=None,
+                           hidden=None, return_hidden=False):
+        """Top-k next items of N whole sessions in one stateless call: (item_ids[N, k], scores[N, k] float32), plus the new hidden
+        state with return_hidden=True.  Not in the reference.
+
+          histories        N >= 1 non-empty sequences of item ids; row i belongs to histories[i].  Any N, independent of batch_size.
+          hidden           None: every session starts from zero (a new session).  Otherwise a list with one float32 array
+                           [N, layers[l]] per layer (the layout of H[l]): history i is replayed from row i.
+          return_hidden    also return that list after the last item of every history (to be passed back as `hidden` later).
+          exclude_history  row i never receives an item of histories[i].  Items seen before a supplied `hidden` are unknown to the
+                           call: pass them in exclude_per_row.
+          predict_for_item_ids, exclude, exclude_per_row, k: as in recommend_next_batch (exclude_per_row: N lists).
+
+        Row i equals, items and score bits, what recommend_next_batch returns for a session whose first T - 1 items went through
+        predict_next_batch from a fresh prediction state and whose last item is the recommend_next_batch input (exclude_history as
+        exclude_seen); the returned state is the one that stepping leaves.  So recommend_sessions(a + b) equals
+        recommend_sessions(b, hidden=<state after a>).  The history is replayed on the device and the catalogue scored once per
+        session.  The prediction state (predict_next_batch / recommend_next_batch, current_session, their seen-history) is neither
+        read nor changed.  Everything is checked before any device work: an empty history or a bad `hidden` (layer count, shape,
+        dtype) raises ValueError, an unknown item id KeyError, and the k / exclusion checks are those of recommend_next_batch."""
+        if self.error_during_train:
+            raise Exception
+        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
+        if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
+            raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        hist = [np.ravel(h) if isinstance(h, np.ndarray) else list(h) for h in histories]
+        N = len(hist)
+        if N < 1:
+            raise ValueError('histories is empty: at least one session is needed')
+        lens = np.array([len(h) for h in hist], dtype=np.int64)
+        if (lens == 0).any():
+            raise ValueError('history %d is empty' % np.flatnonzero(lens == 0)[0])
+        hidx = self.itemidmap[np.concatenate(hist)].values.astype(np.int32)
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        h0 = None
+        if hidden is not None:
+            if not isinstance(hidden, (list, tuple)) or len(hidden) != len(self.layers):
+                raise ValueError('hidden must be a list of %d arrays, one per layer' % len(self.layers))
+            h0 = []
+            for l, (h, D) in enumerate(zip(hidden, self.layers)):
+                if not isinstance(h, np.ndarray) or h.dtype != np.float32 or h.shape != (N, D):
+                    raise ValueError('hidden[%d] must be a float32 array of shape (%d, %d), not %s %s' % (
+                        l, N, D, getattr(h, 'dtype', type(h).__name__), getattr(h, 'shape', '')))
+                h0.append(_pad_cols(h, 1, D, _pad4(D)))
+        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
+        xoffs = xitems = mask = None
+        if exclude_history or exclude is not None or exclude_per_row is not None:
+            hist_rows = (np.repeat(np.arange(N), lens), hidx) if exclude_history else None
+            xoffs, xitems, mask = self._pack_exclusions(N, int(k), iidx, hist_rows, 'the history', exclude, exclude_per_row)
+        m = self._ensure_model()
+        out = m.recommend_sessions(offs, hidx, iidx, int(k), xoffs, xitems, mask, hidden=h0, return_hidden=return_hidden)
+        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
+        if not return_hidden:
+            return cand[out[0]], out[1]
+        return cand[out[0]], out[1], [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(out[2], self.layers)]
 
     def symbolic_predict(self, X, Y, M, items, batch_size):
         raise NotImplementedError('symbolic_predict builds a Theano graph (gru4rec.py:729-741); the MI355X path '

@@ -190,6 +190,18 @@ int g4r_recommend_step_filtered(g4r_model* m, const int32_t* in_idx, int32_t mro
                                 int32_t k, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
                                 int32_t* out_cols, float* out_scores);
 
+/* not in the reference: stateless top-k from whole session histories.  Session i (0 <= i < n) is the item indices
+ * hist_items[hist_offs[i] .. hist_offs[i + 1]) (at least one; hist_offs rises strictly); its hidden state starts from h0 (one
+ * pointer per layer to float[n][layers[l]], row i = session i; h0 NULL = zeros) and steps through the history on buffers of the
+ * call's own.  out_cols / out_scores[n * k] are what g4r_recommend_step_filtered returns for the last item of the history after
+ * g4r_predict_step has been fed the others, bit for bit (same item_idx / n_sel / k / exclusions, with excl_offs[n + 1] per
+ * session).  out_hidden (one pointer per layer to float[n][layers[l]]; NULL = not wanted) receives the state after the last item.
+ * The prediction state (g4r_predict_begin / _hidden / _step, g4r_recommend_step*) is neither read nor changed.  Everything is
+ * checked before any launch, as in g4r_recommend_step_filtered; any n >= 1 works (processed in chunks of rows). */
+int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                           const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs, const int32_t* excl_items,
+                           const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, float* const* out_hidden);
+
 /* The whole of evaluation.evaluate_gpu (evaluation.py:86-147) as ONE call with no host round trip per step: the
  * session-parallel test loop comes as a plan (g4r_build_plan on the test sessions in id order with n_sample = 1: the loop of
  * evaluation.py:96-139 is the loop of fit), every step runs the GRU forward, scores all items (items == NULL) or
