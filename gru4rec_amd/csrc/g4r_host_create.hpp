@@ -15,17 +15,18 @@ const char* g4r_last_error(void) { return g_err.c_str(); }
 const char* g4r_version(void) { return "gru4rec_hip 0.4 (gfx950; hipcc " G4R_HIPCC_VERSION "; isa-audited)"; }
 int g4r_sizeof_config(void) { return (int)sizeof(g4r_config); }
 
-// argument blocks of the narrow-layer kernels (g4r_lean_kernels.cuh): everything they read from the model, from pointers that are final here
+// argument blocks of the lean kernels the step runs (g4r_lean_kernels.cuh): everything they read from the model, from pointers that are
+// final here.  Those of k_score_s and k_update_l also carry the device descriptor's address: g4r_create uploads them once that exists.
 static int build_lean_args(g4r_model* m) {
     DevModel& d = m->dm;
+    const StepKernels& k = m->kern;
     const int L = d.n_layers;
     std::vector<LeanV> av(L); std::vector<LeanH> ah(L); std::vector<LeanDa> aa(L); std::vector<LeanDy> ay(L);
-    bool any = false;
-    const bool constrained_all = d.embed_mode == G4R_EMBED_CONSTRAINED;
+    const bool constrained = d.embed_mode == G4R_EMBED_CONSTRAINED;
+    bool any_layer = false;
     for (int l = 0; l < L; ++l) {
-        if (!lean_gru(d, l)) continue;
-        any = true;
-        const bool constrained = d.embed_mode == G4R_EMBED_CONSTRAINED;
+        if (k.fwd[l] != FWD_LEAN) continue;
+        any_layer = true;
         LeanV& v = av[l]; memset(&v, 0, sizeof(v));
         v.Wx = d.dense_p + d.offWx[l]; v.Wrz = d.dense_p + d.offWrz[l]; v.Bh = d.dense_p + d.offBh[l];
         v.H0 = d.H[l][0]; v.H1 = d.H[l][1];
@@ -51,69 +52,59 @@ static int build_lean_args(g4r_model* m) {
         y.st = d.st; y.seed = d.seed; y.dSx_stride = d.dSx_stride; y.B = d.B; y.D = d.D[l]; y.IN = d.IN[l]; y.layer0 = (l == 0) ? 1 : 0;
         y.generic = d.generic; y.defer_mask = d.defer_mask; y.lr = d.lr; y.drop_e = d.drop_e; y.dbg = d.dbgclk; y.dbgtile = d.dbgtile; y.n_items = d.n_items;
     }
-    if (lean_scores(d)) {
+    m->h_leanV = av; m->h_leanH = ah; m->h_leanDa = aa; m->h_leanDy = ay;      // (host copies: launch_step passes their hot fields as kernel arguments)
+    if (any_layer) {
+        if (dalloc(m, &m->d_leanV, (size_t)L) || dalloc(m, &m->d_leanH, (size_t)L) || dalloc(m, &m->d_leanDa, (size_t)L) || dalloc(m, &m->d_leanDy, (size_t)L)) return -1;
+        HIPCHK(hipMemcpyAsync(m->d_leanV, av.data(), L * sizeof(LeanV), hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(m->d_leanH, ah.data(), L * sizeof(LeanH), hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(m->d_leanDa, aa.data(), L * sizeof(LeanDa), hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(m->d_leanDy, ay.data(), L * sizeof(LeanDy), hipMemcpyHostToDevice, m->stream));
+    }
+    if (k.score_fwd == SF_LEAN) {
         LeanS q; memset(&q, 0, sizeof(q));
         q.col_item = d.col_item; q.occ_idx = d.occ_idx + d.B; q.occ_fl = d.occ_fl; q.mp = nullptr; q.dbg = d.dbgclk; q.dbgtile = d.dbgtile; q.R = d.R; q.pub_fl = d.xmode == 0 ? 1 : 0; q.logq = d.logq;
         m->h_leanS = q;
-        any = true;
+        if (dalloc(m, &m->d_leanS, (size_t)1)) return -1;
     }
-    if (lean_score_bwd(d)) {
+    if (k.score_bwd == SB_LEAN) {
         LeanB q; memset(&q, 0, sizeof(q));
         q.accBy = d.accBy; q.occ_fl = d.occ_fl; q.dSy = d.dSy; q.dAy = d.dAy; q.dSBy = d.dSBy; q.dABy = d.dABy; q.dhpart = d.dhpart; q.dbg = d.dbgclk; q.dbgtile = d.dbgtile;
         q.dSy_stride = d.dSy_stride; q.dSBy_stride = d.dSBy_stride; q.defer_mask = d.defer_mask; q.generic = d.generic;
         q.ndh = cdiv(d.Dtop + 1, 64); q.nA = cdiv(d.ldSc, 16) * q.ndh; q.nrb = cdiv(d.B, 16); q.ndb = cdiv(d.Dtop, 64); q.lr = d.lr;
         m->h_leanB = q;
+        if (dalloc(m, &m->d_leanB, (size_t)1)) return -1;
+        HIPCHK(hipMemcpyAsync(m->d_leanB, &m->h_leanB, sizeof(LeanB), hipMemcpyHostToDevice, m->stream));
     }
-    if (d.apply_dense_inplace && d.B <= 128 && std::max(d.Dtop, d.Ein) <= 256 && !d.generic) {
+    if (k.update == UP_LEAN) {
         // k_update_l: argument block + its table of 16 x 64 dense tiles
         LeanU u; memset(&u, 0, sizeof(u));
         u.mp = nullptr; u.st = d.st; u.Wy = d.Wy; u.E = d.E; u.accWy = d.accWy; u.accE = d.accE; u.velWy = d.velWy; u.velE = d.velE;
         u.By = d.By; u.accBy = d.accBy; u.velBy = d.velBy; u.dAx = d.dAx; u.dAy = d.dAy; u.dABy = d.dABy;
         u.dense_p = d.dense_p; u.dense_acc = d.dense_acc; u.dense_vel = d.dense_vel; u.yin0 = d.yin0; u.meta = d.cur_in + 2 * d.B;
-        u.dbg = d.dbgclk; u.dbgtile = d.dbgtile; u.n_items = d.n_items; u.constrained = constrained_all ? 1 : 0; u.wE = d.Ein; u.wY = d.Dtop;
+        u.dbg = d.dbgclk; u.dbgtile = d.dbgtile; u.n_items = d.n_items; u.constrained = constrained ? 1 : 0; u.wE = d.Ein; u.wY = d.Dtop;
         u.lr = d.lr; u.mom = d.mom; u.lmbd = d.lmbd;
         m->h_leanU = u;
-        std::vector<DenseTile> tiles;
-        for (int l = 0; l < L; ++l) {
-            const int D = d.D[l], IN = d.IN[l];
-            auto add = [&](const float* x0, const float* x1, int ldx, int nrows, int ncols, int coff, int ldo, long long base) {
-                for (int r = 0; r < nrows; r += 16)
-                    for (int c = 0; c < ncols; c += 64) {
-                        DenseTile t;
-                        t.X0 = x0; t.X1 = x1; t.dV = d.dV[l]; t.base = base; t.ldx = ldx; t.ldv = 3 * D; t.nrows = nrows;
-                        t.ncols = ncols; t.coff = coff; t.ldo = ldo; t.r0 = r; t.c0 = c; t.gather = (x0 == nullptr && nrows > 1) ? 1 : 0; t.pad = 0;
-                        tiles.push_back(t);
-                    }
-            };
-            const float* yin = (l == 0) ? nullptr : d.hd[l - 1];
-            if (!(l == 0 && d.embed_mode == G4R_EMBED_ONEHOT)) add(yin, yin, IN, IN, 3 * D, 0, 3 * D, d.offWx[l]);
-            add(d.Hr[l], d.Hr[l], D, D, D, 0, D, d.offWh[l]);
-            add(d.H[l][0], d.H[l][1], D, D, 2 * D, D, 2 * D, d.offWrz[l]);
-            add(nullptr, nullptr, 0, 1, 3 * D, 0, 3 * D, d.offBh[l]);
-        }
+        const std::vector<DenseTile> tiles = dense_tiles(d, 16, 64);
         m->ntiles16 = (int)tiles.size();
         if (dalloc(m, &m->d_tiles16, tiles.size()) || dalloc(m, &m->d_leanU, (size_t)1)) return -1;
         HIPCHK(hipMemcpyAsync(m->d_tiles16, tiles.data(), tiles.size() * sizeof(DenseTile), hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-        any = true;
+        HIPCHK(hipStreamSynchronize(m->stream));      // (before `tiles` goes out of scope)
     }
-    m->h_leanV = av; m->h_leanH = ah; m->h_leanDa = aa; m->h_leanDy = ay;      // (host copies: launch_step passes their hot fields as kernel arguments)
-    if (!any) return 0;
-    if (lean_score_bwd(d)) {
-        if (dalloc(m, &m->d_leanB, (size_t)1)) return -1;
-        HIPCHK(hipMemcpyAsync(m->d_leanB, &m->h_leanB, sizeof(LeanB), hipMemcpyHostToDevice, m->stream));
-    }
-    if (lean_scores(d)) {
-        if (dalloc(m, &m->d_leanS, (size_t)1)) return -1;
-        m->h_leanS.mp = nullptr;      // (set below: the descriptor is allocated after this function)
-    }
-    if (dalloc(m, &m->d_leanV, (size_t)L) || dalloc(m, &m->d_leanH, (size_t)L) || dalloc(m, &m->d_leanDa, (size_t)L) || dalloc(m, &m->d_leanDy, (size_t)L)) return -1;
-    HIPCHK(hipMemcpyAsync(m->d_leanV, av.data(), L * sizeof(LeanV), hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_leanH, ah.data(), L * sizeof(LeanH), hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_leanDa, aa.data(), L * sizeof(LeanDa), hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_leanDy, ay.data(), L * sizeof(LeanDy), hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return 0;
+}
+
+// the environment switches of the kernel choice (KernelSwitches), read once per model
+static KernelSwitches read_switches(const g4r_config& cfg) {
+    KernelSwitches w;
+    w.no_lean = getenv("G4R_NO_LEAN") != nullptr; w.no_mt = getenv("G4R_NO_MT") != nullptr; w.no_bmt = getenv("G4R_NO_BMT") != nullptr;
+    w.no_merge = getenv("G4R_NO_MERGE") != nullptr;
+    w.allow_lean_update = env_int("G4R_LEAN_UPDATE", 1) != 0; w.defer = env_int("G4R_DEFER", cfg.defer_updates) != 0;
+    w.p2_geo = env_int("G4R_P2_GEO", -1); w.ba_geo = env_int("G4R_BA_GEO", -1);
+    w.wide2 = env_int("G4R_WIDE2", -1); w.p1_ks = env_int("G4R_P1_KS", 128); w.bb_ks = env_int("G4R_BB_KS", 0);
+    const char* skip = getenv("G4R_SKIP_KN");
+    w.skip_kn = skip ? strtoull(skip, nullptr, 0) : 0ull;
+    return w;
 }
 
 int g4r_create(const g4r_config* cfg, g4r_model** out) {
@@ -144,12 +135,8 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
     g4r_model* m = new g4r_model();
     m->cfg = *cfg;
     m->n_cu = std::max(n_cu, 1);
-    m->p2_geo_env = env_int("G4R_P2_GEO", -1);
-    m->ba_geo_env = env_int("G4R_BA_GEO", -1);
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; return fail("stream create"); }
-    if (hipStreamCreateWithFlags(&m->comm_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming) != hipSuccess) { g4r_destroy(m); return fail("stream create"); }
+    // ---- 1. the shape scalars of the model
     DevModel& d = m->dm;
     memset(&d, 0, sizeof(d));
     const int L = cfg->n_layers, B = cfg->batch_size;
@@ -194,6 +181,24 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
     // G4R_FORCE_STAGED=1: exercise the multi-rank data path (gradient staging -> RCCL -> k_dense_apply) on one GPU
     d.apply_dense_inplace = (cfg->nranks <= 1 && !getenv("G4R_FORCE_STAGED") && !d.generic) ? 1 : 0;
     d.grad_scale = 1.0f / (float)std::max(cfg->nranks, 1);
+    d.xn = exact ? cfg->nranks : 1;      // exact-replica mode: ranks in the exchanged block, and the form of its update list
+    d.xmode = exact ? std::min(std::max(cfg->sparse_exact, 1), 3) : 0;
+    // ---- 2. the kernels of the training step
+    m->sw = read_switches(*cfg);
+    if (m->sw.skip_kn)
+        fprintf(stderr, "[g4r] G4R_SKIP_KN=0x%llx: launches are left out of every training step -- its results are invalid (a measurement aid)\n", m->sw.skip_kn);
+    // Deferred row updates (g4r_step_kernels.cuh: k_defer_scan / k_sparse_flush): the single-GPU Adagrad step without momentum / L2 term, replayed
+    // from the step graph.  The step planes become rings of G4R_GRAPH_STEPS slots (one window = one graph replay).  OPT-IN (G4R_DEFER=1;
+    // GRU4Rec.defer_updates, bench.py --defer): bit-identical results and a flush launch at 59 % of the HBM peak on the bytes it
+    // moves at BASELINE configs[2] -- but the step gets 2-5 % SLOWER, because the update launch it relieves is at its latency floor
+    // (cfg3: k_sparse_update 7.5 -> 6.2 us with 90 % of the rows gone) or bound by its dense-gradient tiles (cfg4), and the flush
+    // (2.9 / 7.4 us per step) and scan (0.7 / 1.1) come on top (profiles/r05_experiments.md #7).
+    m->defer_on = d.apply_dense_inplace && !d.generic && cfg->momentum <= 0.f && cfg->lmbd == 0.f && m->sw.defer;
+    m->kern = choose_kernels(d, m->n_cu, m->sw, m->defer_on);
+    const StepKernels& k = m->kern;
+    d.kch = k.kch; d.ksplit = k.ksplit;
+    for (int l = 0; l < L; ++l) d.bbn[l] = (k.wg[l].use & 8) ? k.wg[l].bbn : 0;
+    // ---- 3. the memory plan: every buffer of the step, sized for the kernels chosen
     const size_t I = cfg->n_items;
 #define DA(p, n) if (dalloc(m, &(p), (n))) { g4r_destroy(m); return -1; }
     DA(d.dense_p, off); DA(d.dense_acc, off); DA(d.dense_vel, off); DA(d.dense_g, off);
@@ -224,7 +229,7 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
     DA(m->d_tmpH, (size_t)B * maxD);
     {      // narrow layers: the K-slice partial planes of dr' (k_gru_da -> k_gru_dy)
         size_t drp_floats = 0;
-        for (int l = 0; l < L; ++l) if (lean_gru(d, l)) drp_floats = std::max(drp_floats, (size_t)cdiv(d.D[l], 16) * B * d.D[l]);
+        for (int l = 0; l < L; ++l) if (k.fwd[l] == FWD_LEAN) drp_floats = std::max(drp_floats, (size_t)cdiv(d.D[l], 16) * B * d.D[l]);
         if (drp_floats) DA(d.drp, drp_floats);
     }
     DA(d.yin0, (size_t)B * std::max(d.IN[0], 4));
@@ -241,8 +246,6 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
         // replaces the all-reduce, every rank adds the ranks' gradients up itself, in rank order -- dense_apply_elem)
         d.xoffDg = (int)(d.xoffSBy + up64((size_t)d.ldSc));
         d.xstride = (long long)(d.xoffDg + (exact ? up64((size_t)d.dense_count) : 0));
-        d.xn = exact ? cfg->nranks : 1;
-        d.xmode = exact ? std::min(std::max(cfg->sparse_exact, 1), 3) : 0;
         float* xb = nullptr;
         DA(xb, (size_t)d.xn * (size_t)d.xstride);
         d.xbase = xb;
@@ -251,15 +254,7 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
         if (exact) d.dense_g = own + d.xoffDg;      // (the buffer allocated above stays unused)
     }
     DA(d.dAx, (size_t)B * d.Ein); DA(d.dAy, (size_t)d.ldSc * d.Dtop); DA(d.dABy, d.ldSc);
-    // Deferred row updates (g4r_step_kernels.cuh: k_defer_scan / k_sparse_flush): the single-GPU Adagrad step without momentum / L2 term, replayed
-    // from the step graph.  The step planes become rings of G4R_GRAPH_STEPS slots (one window = one graph replay).  OPT-IN (G4R_DEFER=1;
-    // GRU4Rec.defer_updates, bench.py --defer): bit-identical results and a flush launch at 59 % of the HBM peak on the bytes it
-    // moves at BASELINE configs[2] -- but the step gets 2-5 % SLOWER, because the update launch it relieves is at its latency floor
-    // (cfg3: k_sparse_update 7.5 -> 6.2 us with 90 % of the rows gone) or bound by its dense-gradient tiles (cfg4), and the flush
-    // (2.9 / 7.4 us per step) and scan (0.7 / 1.1) come on top (profiles/r05_experiments.md #7).
-    m->lean_upd = env_int("G4R_LEAN_UPDATE", 1) != 0;
-    m->defer_on = d.apply_dense_inplace && !d.generic && cfg->momentum <= 0.f && cfg->lmbd == 0.f && env_int("G4R_DEFER", cfg->defer_updates) != 0;
-    if (m->defer_on) {
+    if (m->defer_on) {      // (the deferred mode's step planes: rings of G4R_DEFER_SLOTS slots)
         const size_t W = G4R_DEFER_SLOTS;
         d.defer_mask = (int)W - 1;
         d.dRcap = cdiv(d.R, SP_WAVES) * SP_WAVES;
@@ -278,158 +273,35 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
     DA(d.col_item, d.ldSc); DA(d.cur_in, 2 * (size_t)B + 8); DA(d.cur_col, d.ldSc);
     DA(d.occ_fl, (size_t)(cfg->embed_mode != G4R_EMBED_CONSTRAINED ? 2 : 1) * I * 4);
     DA(d.st, 1);
-    // scoring backward geometry: role A tiles (n x d, one spare d column for dSBy), role B tiles (b x d x k-chunk)
-    {
-        // k_gru_bwd_fused sums the slabs next to everything else it loads: half as many, twice as deep (k_score_bwd +0.4 us at cfg2)
-        const int slabs_target = (fused_bwd(d, d.n_layers - 1) || lean_gru(d, d.n_layers - 1)) ? 9 : 17;
-        d.kch = GT_BK * std::max(1, (cdiv(d.ldSc, GT_BK) + slabs_target / 2) / slabs_target);      // ~17 slabs whatever the number of negatives
-        if (score_bwd2(d)) {
-            // k_score_bwd2: its 64 x 64 tiles cost microseconds of MFMA each and all of them are resident at once, so the launch
-            // lasts as long as the CU with one tile more than the others.  The number of dh slabs is free: take the one (12..24)
-            // that makes role A + role B tiles fill whole rounds of CUs best (B = 512, N = 8704, D = 256: 17 slabs = 1088 tiles
-            // 64.2 us, 15 slabs = 1024 tiles 60.6 us).  Slab depth only needs the 16-byte alignment of the row loads.
-            const int ndt = d.Dtop / 64, nrt = cdiv(B, 64), nA = cdiv(d.ldSc, 64) * ndt;
-            double best = 2.0;
-            for (int ks = 12; ks <= 24; ++ks) {
-                const int kch = (cdiv(d.ldSc, ks) + 7) & ~7;
-                if (cdiv(d.ldSc, kch) != ks) continue;
-                const double rounds = (double)(nA + ks * nrt * ndt) / m->n_cu;
-                const double waste = (std::ceil(rounds) - rounds) / std::ceil(rounds) + 1e-3 * std::abs(ks - 17);
-                if (waste < best) { best = waste; d.kch = kch; }
-            }
-        }
-        if (score_bmt_slabs(d, m->n_cu)) d.kch = d.ldSc / score_bmt_slabs(d, m->n_cu);      // k_score_bmt: as many role-B as role-A tiles
-        if (lean_score_bwd(d)) d.kch = 128;      // k_score_b: slabs of 128 score columns (eight waves x 16)
-        d.ksplit = cdiv(d.ldSc, d.kch);
-        DA(d.dhpart, (size_t)d.ksplit * B * d.Dtop);
-        const int TB = wide_scores(d) ? 64 : 32;      // tile edge of k_score_bwd
-        m->ndtA = cdiv(d.Dtop + 1, TB);
-        m->nblkA = cdiv(d.ldSc, TB) * m->ndtA;
-        m->ndtB = cdiv(d.Dtop, TB);
-        m->nrtB = cdiv(B, TB);
-        m->nblkB = d.ksplit * m->nrtB * m->ndtB;
-        m->nblk_occ = cdiv(d.R, SP_WAVES);
-        m->nblk_occ_g = m->nblk_occ;      // generic optimizer path (one occurrence per wave; exact-replica mode: sized at launch)
-        m->smem_sparse = (size_t)(((d.R + 255) & ~255) + 256) * sizeof(int) + (2 + 64) * SP_WAVES * sizeof(int) +
-                         (size_t)SP_WAVES * (std::max(d.Dtop, d.Ein) + 4) * sizeof(float);
-    }
+    DA(d.dhpart, (size_t)d.ksplit * B * d.Dtop);      // dh of the scoring backward, one plane per slab
+    m->nblk_occ = cdiv(d.R, SP_WAVES);
+    m->nblk_occ_g = m->nblk_occ;      // generic optimizer path (one occurrence per wave; exact-replica mode: sized at launch)
+    m->smem_sparse = (size_t)(((d.R + 255) & ~255) + 256) * sizeof(int) + (2 + 64) * SP_WAVES * sizeof(int) +
+                     (size_t)SP_WAVES * (std::max(d.Dtop, d.Ein) + 4) * sizeof(float);
     if (ns > 0) DA(m->d_ST, (size_t)gl * ns);
     d.ST = m->d_ST;
-    // dense-gradient tile table
-    {
-        std::vector<DenseTile> tiles;
-        const int DTE = 32;
-        for (int l = 0; l < L; ++l) {
-            const int D = d.D[l], IN = d.IN[l];
-            auto add = [&](const float* x0, const float* x1, int ldx, int nrows, int ncols, int coff, int ldo, long long base) {
-                for (int r = 0; r < nrows; r += DTE)
-                    for (int c = 0; c < ncols; c += DTE) {
-                        DenseTile t;
-                        t.X0 = x0; t.X1 = x1; t.dV = d.dV[l]; t.base = base; t.ldx = ldx; t.ldv = 3 * D; t.nrows = nrows;
-                        t.ncols = ncols; t.coff = coff; t.ldo = ldo; t.r0 = r; t.c0 = c; t.gather = (x0 == nullptr && nrows > 1) ? 1 : 0; t.pad = 0;
-                        tiles.push_back(t);
-                    }
-            };
-            const float* yin = (l == 0) ? nullptr : d.hd[l - 1];     // layer 0: gathered in the kernel
-            add(yin, yin, IN, IN, 3 * D, 0, 3 * D, d.offWx[l]);                   // dWx  = yin^T dV
-            add(d.Hr[l], d.Hr[l], D, D, D, 0, D, d.offWh[l]);                     // dWh  = (H r)^T dV[:, :D]
-            add(d.H[l][0], d.H[l][1], D, D, 2 * D, D, 2 * D, d.offWrz[l]);        // dWrz = H^T dV[:, D:]
-            add(nullptr, nullptr, 0, 1, 3 * D, 0, 3 * D, d.offBh[l]);             // dBh  = colsum(dV)
-        }
-        m->ntiles = (int)tiles.size();
-        DA(m->d_tiles, tiles.size());
-        if (hipMemcpyAsync(m->d_tiles, tiles.data(), tiles.size() * sizeof(DenseTile), hipMemcpyHostToDevice, m->stream) != hipSuccess) {
-            g4r_destroy(m); return fail("tile upload");
-        }
-        if (hipStreamSynchronize(m->stream) != hipSuccess) { g4r_destroy(m); return fail("sync"); }
-    }
-    // wide layers: the K-sliced kernels of g4r_wide_kernels.cuh.  G4R_WIDE2 (read per model: tests and A/B runs toggle it between
-    // models) is a bit mask -- 1 k_gru_p1s + k_gru_gate, 8 k_gru_bwd_bw, 16 k_dense_grad2; 0 = the round-1 kernels -- default: the policy
-    // below, from the A/B runs of round 5 (profiles/r05_experiments.md):
-    //   16  the 64 x 64 dense-gradient tiles as a launch of their own where the dense gradients outweigh the sparse rows
-    //       (6 D >= 2 B + n_sample: BASELINE configs[2] yes -- k_update 24.4 us as one launch, 17.7 + 7.5 as two; configs[3] shape no --
-    //       20.6 merged, 20.3 + 13.4 apart: there the merged launch overlaps its two roles)
-    //    8  dy as K-slice partial sums wherever a consumer adds them up: the lower layer's k_gru_bwd_pre (any layer above an unfused
-    //       one); for layer 0 the row-finishing workgroups of k_dense_grad2 (17.5 -> 7.0 us at configs[2]) or, with the merged k_update,
-    //       k_finish_rows as a small launch in front of it (configs[3] shape: 10.8 -> 5.0 + 4.2 us, step 170.3 -> 167.7)
-    //    1  phase 1 as partial sums + k_gru_gate from D = 512 on (25.0 -> 18.3 + 4.5 us at configs[2]; D = 256: 13.9 -> 12.9 + 4.3, off)
-    // K-slice lengths for A/B runs: G4R_P1_KS (<= 128), G4R_BB_KS.
-    {
-        const int mask_env = env_int("G4R_WIDE2", -1);
-        int dmax_ = 0;
-        for (int l = 0; l < L; ++l) dmax_ = std::max(dmax_, d.D[l]);
-        const bool automask = mask_env < 0;
-        const int mask = automask ? (1 | 8 | (6 * dmax_ >= d.R ? 16 : 0)) : mask_env;
-        const int nrt = cdiv(B, 64);
-        const bool wdense = (mask & 16) && wide_layer(dmax_) && !(cfg->embed_mode == G4R_EMBED_ONEHOT);
+    // dense-gradient tile tables: 32 x 32 (k_dense_grad, k_update), 64 x 64 (k_dense_grad2)
+    auto tile_table = [&](int edge, DenseTile** dst, int* n) {
+        const std::vector<DenseTile> tiles = dense_tiles(d, edge, edge);
+        *n = (int)tiles.size();
+        return dalloc(m, dst, tiles.size()) == 0 && hipMemcpyAsync(*dst, tiles.data(), tiles.size() * sizeof(DenseTile), hipMemcpyHostToDevice, m->stream) == hipSuccess &&
+               hipStreamSynchronize(m->stream) == hipSuccess;
+    };
+    if (!tile_table(32, &m->d_tiles, &m->ntiles) || (k.wide_dense && !tile_table(64, &m->d_tiles64, &m->ntiles64))) { g4r_destroy(m); return fail("tile upload"); }
+    {      // wide layers: the K-slice partial planes of phase 1 (k_gru_p1s -> k_gru_gate) and of dy (k_gru_bwd_bw -> its consumer)
         size_t dyp_floats = 0, vp_floats = 0;
         for (int l = 0; l < L; ++l) {
-            const int D = d.D[l], IN = d.IN[l];
-            g4r_model::WideGeo& G = m->wg[l];
-            const bool ok = wide_layer(D) && D % 64 == 0 && IN % 16 == 0 && IN >= 64 && !(l == 0 && cfg->embed_mode == G4R_EMBED_ONEHOT);
-            if (!ok) continue;
-            // phase 1: slices of <= 128 units (the whole slice of a workgroup is in flight at once: gemm_tile2k_full); k_gru_gate adds
-            // up <= 8 input slices / <= 16 slices in all
-            if ((mask & 1) && (!automask || D >= 512)) {
-                int ks = std::min(128, std::max(16, env_int("G4R_P1_KS", 128) / 16 * 16));
-                G.ny = cdiv(IN, ks); G.kys = ((cdiv(IN, G.ny) + 15) / 16) * 16; G.ny = cdiv(IN, G.kys);
-                G.nh = cdiv(D, ks); G.khs = ((cdiv(D, G.nh) + 15) / 16) * 16; G.nh = cdiv(D, G.khs);
-                if (G.ny <= 8 && G.ny + G.nh <= 16) {
-                    G.use |= 1;
-                    vp_floats = std::max(vp_floats, (size_t)(G.ny + G.nh) * B * 3 * D);
-                }
-            }
-            // dy: enough slices of >= 128 (multiples of 32) to give every CU a workgroup, <= 16 (what the consumers add up in one round trip)
-            const bool consumer = (l == 0) ? true : (!fused_bwd(d, l - 1) || lean_gru(d, l - 1));      // (layer 0: the row-finishing workgroups of k_dense_grad2, or k_finish_rows in front of the merged k_update)
-            if ((mask & 8) && consumer) {
-                const int K = 3 * D, tiles = cdiv(IN, 64) * nrt, forced = env_int("G4R_BB_KS", 0);
-                int n = std::min(std::max(1, cdiv(m->n_cu, std::max(tiles, 1))), std::max(1, K / 128));
-                int ks = ((cdiv(K, n) + 31) / 32) * 32;
-                if (forced > 0) ks = std::max(32, forced / 32 * 32);
-                if (cdiv(K, ks) <= 16) {
-                    G.use |= 8; G.bbk = ks; G.bbn = cdiv(K, ks);
-                    d.bbn[l] = G.bbn;
-                    dyp_floats = std::max(dyp_floats, (size_t)G.bbn * B * IN);
-                }
-            }
+            const WideGeo& G = k.wg[l];
+            if (G.use & 1) vp_floats = std::max(vp_floats, (size_t)(G.ny + G.nh) * B * 3 * d.D[l]);
+            if (G.use & 8) dyp_floats = std::max(dyp_floats, (size_t)G.bbn * B * d.IN[l]);
         }
         if (dyp_floats) DA(d.dyp, dyp_floats);
         if (vp_floats) DA(d.vp, vp_floats);
-        m->wide_dense = wdense;
-        if (m->wide_dense) {
-            std::vector<DenseTile> tiles;
-            for (int l = 0; l < L; ++l) {
-                const int D = d.D[l], IN = d.IN[l];
-                auto add = [&](const float* x0, const float* x1, int ldx, int nrows, int ncols, int coff, int ldo, long long base) {
-                    for (int r = 0; r < nrows; r += 64)
-                        for (int c = 0; c < ncols; c += 64) {
-                            DenseTile t;
-                            t.X0 = x0; t.X1 = x1; t.dV = d.dV[l]; t.base = base; t.ldx = ldx; t.ldv = 3 * D; t.nrows = nrows;
-                            t.ncols = ncols; t.coff = coff; t.ldo = ldo; t.r0 = r; t.c0 = c; t.gather = (x0 == nullptr && nrows > 1) ? 1 : 0; t.pad = 0;
-                            tiles.push_back(t);
-                        }
-                };
-                const float* yin = (l == 0) ? nullptr : d.hd[l - 1];
-                add(yin, yin, IN, IN, 3 * D, 0, 3 * D, d.offWx[l]);
-                add(d.Hr[l], d.Hr[l], D, D, D, 0, D, d.offWh[l]);
-                add(d.H[l][0], d.H[l][1], D, D, 2 * D, D, 2 * D, d.offWrz[l]);
-                add(nullptr, nullptr, 0, 1, 3 * D, 0, 3 * D, d.offBh[l]);      // nrows == 1: the column-sum role
-            }
-            m->ntiles64 = (int)tiles.size();
-            DA(m->d_tiles64, tiles.size());
-            if (hipMemcpyAsync(m->d_tiles64, tiles.data(), tiles.size() * sizeof(DenseTile), hipMemcpyHostToDevice, m->stream) != hipSuccess ||
-                hipStreamSynchronize(m->stream) != hipSuccess) { g4r_destroy(m); return fail("tile upload"); }
-        }
     }
 #undef DA
     // LDS opt-in
     m->smem_score = ((size_t)(SC_BM + 32) * (SC_KC + 2) + 32) * sizeof(float);
-    m->smem_loss = (size_t)(2 * d.ldSc + 18 * LOSS_NW) * sizeof(float);
-    m->loss_long = m->smem_loss > (size_t)(156 * 1024);      // one row copy in LDS, the other in the score row itself (k_loss_rows<true>)
-    if (m->loss_long) m->smem_loss = (size_t)(d.ldSc + 18 * LOSS_NW) * sizeof(float);
-    // four columns per thread and trip from 4 columns per thread on (measured, round 5: B = 512 with 8192 negatives 15.2 -> 13.0 us;
-    // 2176 / 2528 columns: 4.7 / 4.4 us either way)
-    m->loss_quads = d.ldSc >= 4 * LOSS_T;
+    m->smem_loss = (size_t)((k.loss_long ? 1 : 2) * d.ldSc + 18 * LOSS_NW) * sizeof(float);
     const int big = 156 * 1024;      // leaves room for the few bytes of static LDS some kernels use (__syncthreads_or)
     HIPCHK(hipFuncSetAttribute((const void*)k_gru_p1_n32, hipFuncAttributeMaxDynamicSharedMemorySize, big));
     HIPCHK(hipFuncSetAttribute((const void*)k_gru_p1_n64, hipFuncAttributeMaxDynamicSharedMemorySize, big));
@@ -507,7 +379,6 @@ void g4r_destroy(g4r_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->cfg.device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    if (m->comm_stream) (void)hipStreamSynchronize(m->comm_stream);
     if (m->gexec) (void)hipGraphExecDestroy(m->gexec);
     if (m->gexec_small) (void)hipGraphExecDestroy(m->gexec_small);
     if (m->gexec_head) (void)hipGraphExecDestroy(m->gexec_head);
@@ -521,9 +392,6 @@ void g4r_destroy(g4r_model* m) {
         sc->p = nullptr; sc->cap = 0;
     }
     for (void* p : m->allocs) (void)hipFree(p);
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    if (m->ev_join) (void)hipEventDestroy(m->ev_join);
-    if (m->comm_stream) (void)hipStreamDestroy(m->comm_stream);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
 }

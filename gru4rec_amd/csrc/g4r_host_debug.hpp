@@ -5,6 +5,7 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     if (!m || !name || !host) return fail("null argument");
     HIPCHK(hipSetDevice(m->cfg.device));
     DevModel& d = m->dm;
+    const StepKernels& k = m->kern;
     std::string s(name);
     const float* p = nullptr; int64_t n = 0;
     int l = 0;
@@ -46,26 +47,40 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     else if (s == "dbgtile") { if (!d.dbgtile) return fail("G4R_CLK not set"); p = (const float*)d.dbgtile; n = 2 * 8 * (int64_t)8192; }      // [0, 4096): dense tiles, [4096, 8192): k_score_fwd tiles
     else if (s == "ntiles") { if (count < 1) return fail("count"); host[0] = (float)m->ntiles; return 0; }
     else if (s == "ldSc") { if (count < 1) return fail("count"); host[0] = (float)d.ldSc; return 0; }
-    else if (s == "wide_mask") {      // which wide-layer kernels run (bits 1 / 2 / 4 / 8 per layer OR-ed, 16 = k_dense_grad2)
+    // ---- the kernel choice of the training step (m->kern, choose_kernels)
+    else if (s == "wide_mask") {      // which wide-layer kernels run (bits 1 / 8 per layer OR-ed, 16 = k_dense_grad2)
         if (count < 1) return fail("count");
-        int mk = m->wide_dense ? 16 : 0;
-        for (int l = 0; l < d.n_layers; ++l) mk |= m->wg[l].use;
+        int mk = k.wide_dense ? 16 : 0;
+        for (int l = 0; l < d.n_layers; ++l) mk |= k.wg[l].use;
         host[0] = (float)mk; return 0;
     }
-    else if (s == "deep_geo") {      // layer 0 at the training batch: 1 = k_gru_p2 on 8 waves x 256-deep chunks, 2 = k_gru_bwd_a (deep_geometry)
+    else if (s == "deep_geo") {      // layer 0 at the training batch: 1 = k_gru_p2 on 8 waves x 256-deep chunks, 2 = k_gru_bwd_a
         if (count < 1) return fail("count");
-        host[0] = (float)(deep_geometry(m->p2_geo_env, m->n_cu, d.D[0], d.B) + 2 * deep_geometry(m->ba_geo_env, m->n_cu, d.D[0], d.B)); return 0;
+        host[0] = (float)(k.p2_deep[0] + 2 * k.ba_deep[0]); return 0;
     }
-    else if (s == "score_mt") { if (count < 1) return fail("count"); host[0] = (float)score_mt_width(d, m->n_cu); return 0; }      // macro-tile width of the scoring forward (0: 64 x 64 tiles)
-    else if (s == "score_bmt") { if (count < 1) return fail("count"); host[0] = (float)score_bmt_slabs(d, m->n_cu); return 0; }      // slabs of the macro-tile scoring backward (0: k_score_bwd2)
-    else if (s == "lean") {      // the lean launches a training step takes (g4r_lean_kernels.cuh), from the predicates launch_step dispatches on:
-        if (count < 4) return fail("count");      // (bit l = lean_gru of layer l, lean_scores, lean_score_bwd, lean_update)
+    else if (s == "score_mt") { if (count < 1) return fail("count"); host[0] = k.score_fwd == SF_MT ? 272.f : 0.f; return 0; }      // macro-tile width of the scoring forward (0: 64 x 64 tiles)
+    else if (s == "score_bmt") { if (count < 1) return fail("count"); host[0] = (float)k.bmt_slabs; return 0; }      // slabs of the macro-tile scoring backward (0: not chosen)
+    else if (s == "lean") {      // the lean launches a training step takes (g4r_lean_kernels.cuh):
+        if (count < 4) return fail("count");      // (bit l = layer l's GRU, the scoring forward, the scoring backward, the update)
         int mk = 0;
-        for (int l = 0; l < d.n_layers; ++l) mk |= lean_gru(d, l) ? 1 << l : 0;
-        host[0] = (float)mk; host[1] = lean_scores(d) ? 1.f : 0.f; host[2] = lean_score_bwd(d) ? 1.f : 0.f;
-        host[3] = (lean_update(m) && !(d.bbn[0] > 0)) ? 1.f : 0.f;
+        for (int l = 0; l < d.n_layers; ++l) mk |= k.fwd[l] == FWD_LEAN ? 1 << l : 0;
+        host[0] = (float)mk; host[1] = k.score_fwd == SF_LEAN ? 1.f : 0.f; host[2] = k.score_bwd == SB_LEAN ? 1.f : 0.f;
+        host[3] = k.update == UP_LEAN ? 1.f : 0.f;
         return 0;
     }
+    else if (s == "kernels") {      // the kinds, flags and slab counts of the choice (not its tile / K-slice geometries), 4 ML + 12 floats:
+        // per layer (ML = G4R_MAX_LAYERS slots each, 0 past n_layers) GruFwdKind, GruBwdKind, p2_deep + 2 ba_deep, WideGeo::use; then
+        // score_fwd, loss_spec, loss_long, loss_quads, score_bwd, kch, ksplit, bmt_slabs, update, chunks, wide_dense, finish_rows
+        const int ML = G4R_MAX_LAYERS;
+        const int tail[] = {k.score_fwd, k.loss_spec, k.loss_long, k.loss_quads, k.score_bwd, k.kch, k.ksplit, k.bmt_slabs, k.update, k.chunks, k.wide_dense, k.finish_rows};
+        if (count < 4 * ML + 12) return fail("count");
+        for (int i = 0; i < 4 * ML + 12; ++i) host[i] = i < 4 * ML ? 0.f : (float)tail[i - 4 * ML];
+        for (int l = 0; l < d.n_layers; ++l) {
+            host[l] = (float)k.fwd[l]; host[ML + l] = (float)k.bwd[l]; host[2 * ML + l] = (float)(k.p2_deep[l] + 2 * k.ba_deep[l]); host[3 * ML + l] = (float)k.wg[l].use;
+        }
+        return 0;
+    }
+    else if (s == "n_cu") { if (count < 1) return fail("count"); host[0] = (float)m->n_cu; return 0; }      // the CU count the choice was made for
     else if (s == "ksplit") { if (count < 1) return fail("count"); host[0] = (float)d.ksplit; return 0; }
     else if (s == "dev_syncs") { if (count < 1) return fail("count"); host[0] = (float)m->n_dev_syncs; return 0; }
     else if (s == "dense_count") { if (count < 1) return fail("count"); host[0] = (float)d.dense_count; return 0; }

@@ -32,15 +32,53 @@ static const char* KN_NAMES[KN_COUNT] = {"k_gru_p1", "k_gru_p2", "k_score_fwd", 
 
 struct EvRec { int kn; hipEvent_t a, b; };
 
+// ---- the kernels of a training step: chosen once per model (choose_kernels, at g4r_create), dispatched on by launch_step
+// The environment switches that steer the choice, read at g4r_create (tests and A/B runs toggle them between models)
+struct KernelSwitches {
+    bool no_lean = false;                 // G4R_NO_LEAN: the fused / LDS-staged kernels the lean launches replaced (tests/test_gpu_lean.py)
+    bool no_mt = false, no_bmt = false;   // G4R_NO_MT / G4R_NO_BMT: the 64 x 64 scoring tiles instead of k_score_mt / k_score_bmt
+    bool no_merge = false;                // G4R_NO_MERGE: dense gradients and sparse rows as two launches, never the merged k_update
+    bool allow_lean_update = true;        // G4R_LEAN_UPDATE=0: the merged k_update where k_update_l would run, as the deferred mode runs it
+    bool defer = false;                   // G4R_DEFER (default: g4r_config::defer_updates)
+    int p2_geo = -1, ba_geo = -1;         // G4R_P2_GEO / G4R_BA_GEO = 0 / 1: the 4-wave / 8-wave geometry of k_gru_p2 / k_gru_bwd_a (-1: the policy)
+    int wide2 = -1, p1_ks = 128, bb_ks = 0;      // G4R_WIDE2 (wide-layer kernel mask, -1: the policy), G4R_P1_KS / G4R_BB_KS (their K slices)
+    unsigned long long skip_kn = 0;       // G4R_SKIP_KN: measurement aid, bit k = leave the launches of slot k (KN_*) out of the step
+};
+// What choose_kernels decided; the debug key `kernels` reports these values.  Tile forms: k_gru_p1* then k_gru_p2; k_gru_bwd_pre,
+// k_gru_bwd_a, then k_onehot_step (layer 0 of a one-hot input) / k_gru_bwd_bw (dy as K-slice partial sums) / k_gru_bwd_b.
+enum GruFwdKind { FWD_LEAN = 0 /* k_gru_v + k_gru_h */, FWD_FUSED = 1 /* k_gru_fwd_fused */, FWD_P1S = 2 /* k_gru_p1s + k_gru_gate */,
+                  FWD_P1_N64 = 3, FWD_P1_N32 = 4 };
+enum GruBwdKind { BWD_LEAN = 0 /* k_gru_da + k_gru_dy */, BWD_FUSED = 1 /* k_gru_bwd_fused */, BWD_ONEHOT = 2, BWD_BW = 3, BWD_B = 4 };
+enum ScoreFwdKind { SF_LEAN = 0 /* k_score_s */, SF_MT = 1 /* k_score_mt_4s */, SF_T3 = 2, SF_T2 = 3, SF_K64 = 4, SF_K128 = 5 /* k_score_fwd_* */ };
+enum ScoreBwdKind { SB_LEAN = 0 /* k_score_b */, SB_BMT = 1 /* k_score_bmt */, SB_BWD2 = 2 /* k_score_bwd2 */, SB_W = 3, SB_N = 4 /* k_score_bwd_w / _n */ };
+// UP_MERGED: dense-gradient tiles and sparse rows in one launch; UP_SPLIT: k_dense_grad[2], (staged: all-reduce, k_dense_apply), k_sparse_update*
+enum UpdateKind { UP_LEAN = 0 /* k_update_l */, UP_MERGED = 1 /* k_update */, UP_SPLIT = 2 };
+// wide layers (g4r_wide_kernels.cuh): which kernels run (bit 1 k_gru_p1s + k_gru_gate, 8 k_gru_bwd_bw) and their K-slice geometry
+struct WideGeo { int use = 0, ny = 1, nh = 1, kys = 0, khs = 0, bbn = 1, bbk = 0; };
+struct StepKernels {
+    int fwd[G4R_MAX_LAYERS], bwd[G4R_MAX_LAYERS];
+    int p2_deep[G4R_MAX_LAYERS], ba_deep[G4R_MAX_LAYERS];      // k_gru_p2 / k_gru_bwd_a on 8 waves x 256-deep chunks
+    WideGeo wg[G4R_MAX_LAYERS];
+    int score_fwd;
+    int loss_spec, loss_long, loss_quads;      // k_loss_rows<loss_long, loss_spec, loss_long || loss_quads ? 4 : 1>
+    int score_bwd;
+    int kch, ksplit;                      // slabs of the scoring backward: kch score columns each, ksplit of them (-> DevModel)
+    int bmt_slabs;                        // k_score_bmt's role-B slabs (0: not chosen)
+    int nblkA, nblkB, ndtA, ndtB, nrtB;   // k_score_bwd_w / _n: role A tiles (n x d, one spare d column for dSBy), role B tiles (b x d x slab)
+    int update;
+    int chunks;                           // float4 chunks per lane of a gathered row in the sparse update (rows of <= 256 / 512 / 1024 floats)
+    int wide_dense;                       // k_dense_grad2 (64 x 64 dense-gradient tiles) as a launch of its own
+    int finish_rows;                      // k_finish_rows: layer 0's dy from K-slice partial sums, ahead of k_update / k_dense_grad
+};
+
 struct g4r_model {
     g4r_config cfg;
     DevModel dm;                 // host master copy of the device-resident model descriptor
     DevModel* d_dm = nullptr;    // what the kernels read (passed by pointer: 8-byte kernarg)
     int n_cu = 256;              // compute units of the device (tile-count heuristics)
-    int p2_geo_env = -1, ba_geo_env = -1;      // G4R_P2_GEO / G4R_BA_GEO at g4r_create (-1: deep_geometry's policy)
+    KernelSwitches sw;           // the environment switches of the kernel choice, as g4r_create read them
+    StepKernels kern;            // the kernels a training step runs (choose_kernels)
     hipStream_t stream = nullptr;
-    hipStream_t comm_stream = nullptr;           // all-reduce + dense Adagrad next to the sparse update (nranks > 1)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<void*> allocs;
     // plan
     int *d_in = nullptr, *d_out = nullptr, *d_M = nullptr, *d_cmaps = nullptr;
@@ -57,16 +95,8 @@ struct g4r_model {
     int64_t gstep = 0;
     // launch geometry
     DenseTile* d_tiles = nullptr;
-    int ntiles = 0, nblkA = 0, nblkB = 0, ndtA = 0, ndtB = 0, nrtB = 0, nblk_occ = 0, nblk_occ_g = 0;
+    int ntiles = 0, nblk_occ = 0, nblk_occ_g = 0;
     size_t smem_score = 0, smem_loss = 0, smem_sparse = 0;
-    bool loss_long = false;      // k_loss_rows<true>: score rows too long for two LDS copies
-    bool loss_quads = false;     // k_loss_rows<., ., 4>: four columns per thread and trip (long score rows)
-    // wide layers (g4r_wide_kernels.cuh): per layer which kernels run (bit 1 k_gru_p1s + k_gru_gate, 8 k_gru_bwd_bw) and their K-slice
-    // geometry; wide_dense: the 64 x 64 dense-gradient tiles (k_dense_grad2, mask bit 16) as a launch of their own for the whole model
-    struct WideGeo { int use = 0, ny = 1, nh = 1, kys = 0, khs = 0, bbn = 1, bbk = 0; };
-    WideGeo wg[G4R_MAX_LAYERS];
-    bool wide_dense = false;
-    bool lean_upd = true;        // k_update_l allowed (G4R_LEAN_UPDATE=0 at create: the merged k_update, as the deferred mode runs it -- the reference run of tests/test_gpu_defer.py)
     bool defer_on = false;       // deferred row updates (k_defer_scan / k_sparse_flush around every replay of the step graph)
     bool defer_broken = false;   // a call failed between a window's scan and its flush: pending row updates were lost, the handle refuses to go on
     hipEvent_t ev_df[4] = {nullptr, nullptr, nullptr, nullptr};      // profiling: scan / flush launches of a window
@@ -190,23 +220,7 @@ static const size_t SMEM_TN = tile_smem<GT_BM, GT_BN, GT_BK, true, false>();    
 static constexpr auto k_gru_p1_n32 = k_gru_p1<GT_BN, P1_BK>;
 static constexpr auto k_gru_p1_n64 = k_gru_p1<64, 256>;
 static const size_t SMEM_P1_N64 = tile_smem<GT_BM, 64, 256, false, false>() + GT_BM * sizeof(int);
-// GRU forward / backward of a narrow layer as the four lean launches of g4r_lean_kernels.cuh (k_gru_v, k_gru_h / k_gru_da, k_gru_dy): training,
-// in and D up to LN_MAXD.  G4R_NO_LEAN=1 (read once): the fused single-launch kernels of round 2 instead (A/B runs, tests of both forms).
-static inline bool lean_gru(const DevModel& d, int l) {
-    static const bool off = getenv("G4R_NO_LEAN") != nullptr;
-    return !off && d.D[l] <= LN_MAXD && d.IN[l] <= LN_MAXD && d.D[l] % 4 == 0 && d.IN[l] % 4 == 0 && d.IN[l] >= 4 &&
-           !(l == 0 && d.embed_mode == G4R_EMBED_ONEHOT);
-}
-// GRU backward in one launch (k_gru_bwd_fused) for layers whose operands fit its LDS plan
-static inline bool fused_bwd(const DevModel& d, int l) {
-    return d.D[l] <= BF_MAXD && d.D[l] % 4 == 0 && d.IN[l] % 4 == 0 && !(l == 0 && d.embed_mode == G4R_EMBED_ONEHOT);
-}
-// GRU forward in one launch (k_gru_fwd_fused) for layers whose weights fit its LDS plan (in + D up to ~200)
-static inline bool fused_fwd(const DevModel& d, int l) {
-    return d.D[l] <= FF_LDR && d.IN[l] <= FF_LDR && d.D[l] % 4 == 0 && d.IN[l] % 4 == 0 && d.IN[l] >= 4 &&      // its load maps cover 112 rows / columns
-           !(l == 0 && d.embed_mode == G4R_EMBED_ONEHOT) && (size_t)fwd_fused_lds(d.IN[l], d.D[l]).total * sizeof(float) <= 156 * 1024;
-}
-static inline size_t smem_fused_bwd(int D) { return (size_t)((((BF_ROWS + 32) * (3 * D + 2) + D * (D + 2) + 32 + 3) & ~3) + 4 * 6 * 64) * sizeof(float); }
+static inline size_t smem_bwd_fused(int D) { return (size_t)((((BF_ROWS + 32) * (3 * D + 2) + D * (D + 2) + 32 + 3) & ~3) + 4 * 6 * 64) * sizeof(float); }
 static inline bool wide_layer(int D) { return D >= 256; }
 static const size_t SMEM_P1 = tile_smem<GT_BM, GT_BN, P1_BK, false, false>() + GT_BM * sizeof(int);
 // k_gru_p2 / k_gru_bwd_a (32 x 32 tiles over K = D): 4 waves and 128-deep chunks; where the launch leaves CUs idle and K is longer than
@@ -220,10 +234,6 @@ static const size_t SMEM_P2_256 = tile_smem<GT_BM, GT_BN, 256, false, false>() +
 static constexpr auto k_gru_bwd_a_w4 = k_gru_bwd_a<GT_NTH, GT_BK>;
 static constexpr auto k_gru_bwd_a_w8d = k_gru_bwd_a<512, 256>;
 static const size_t SMEM_BA_256 = tile_smem<GT_BM, GT_BN, 256, false, true>();
-static inline int deep_geometry(int forced, int n_cu, int D, int rows) {
-    if (forced >= 0) return forced != 0;
-    return D >= 384 && cdiv(D, GT_BN) * cdiv(rows, GT_BM) <= n_cu;
-}
 static const size_t SMEM_BB = tile_smem<GT_BM, GT_BN, BB_BK, false, true>() + GT_BM * sizeof(int);
 static constexpr auto k_score_fwd_k128 = k_score_fwd<GT_BN, GT_BK>;
 // long score rows: 64-deep K chunks (more resident workgroups).  Measured at B = 512, N = 8704, D = 256 (us): 64 x 32 tiles
@@ -235,68 +245,168 @@ static constexpr auto k_score_fwd_t2 = k_score_fwd<64, 32, T2_BK>;      // gemm_
 static const size_t SMEM_SF2 = (size_t)Tile2Cfg<T2_BK>::SMEM_FLOATS * sizeof(float);
 static constexpr auto k_score_fwd_t3 = k_score_fwd<64, 32, 3>;          // gemm_tile3: the same tile fed by LDS-DMA through a ring of stages
 static const size_t SMEM_SF3 = (size_t)Tile3Cfg<T3_NST, T3_BKS>::SMEM_FLOATS * sizeof(float);
-static inline bool score_tile2() { return true; }
-static inline bool wide_scores(const DevModel& d);
-// gemm_tile2k scoring backward (k_score_bwd2): long score rows / big batches and D a multiple of 64
-static inline bool score_bwd2(const DevModel& d) { return wide_scores(d) && score_tile2() && d.Dtop % 64 == 0; }
-// macro-tile scoring backward (k_score_bmt, g4r_score_bmt.cuh): role A in 272 x 32 tiles, role B in 64 x 128 tiles x `ks` slabs, as many
-// of each and together two per CU.  Returns ks (0: k_score_bwd2).  G4R_NO_BMT=1: off (A/B runs).
-static inline int score_bmt_slabs(const DevModel& d, int n_cu) {
-    static const bool off = getenv("G4R_NO_BMT") != nullptr;
-    if (off || !score_bwd2(d) || d.Dtop % 128 != 0 || d.Dtop > 512 || d.ldSc % BMT_WA != 0 || d.ldSc > 0xFFFF || d.B > 0xFFFF) return 0;
-    if (lean_gru(d, d.n_layers - 1) || fused_bwd(d, d.n_layers - 1)) return 0;      // (the Adagrad rule of the item rows rides on the top layer's k_gru_bwd_a)
-    const int ntA = d.ldSc / BMT_WA * (d.Dtop / 32), den = cdiv(d.B, 64) * (d.Dtop / 128);
-    if (ntA % den != 0 || ntA % 8 != 0 || ntA > n_cu || ntA * 8 < n_cu * 7 || BMT_WA % (d.Dtop / 32) != 0 || 4 * (BMT_WA / (d.Dtop / 32)) > 256) return 0;      // (bias columns: 272 / (D / 32) per tile, four threads each)
-    const int ks = ntA / den;
-    if (ks < 2 || ks > 24 || d.ldSc % ks != 0 || (d.ldSc / ks) % 32 != 0 || d.ldSc / ks > 2048) return 0;
-    return ks;
-}
 static const size_t SMEM_BMT = std::max((size_t)BMT_NST_A * BMT_STAGE_A * sizeof(float), (size_t)BMT_NST_B * BMT_STAGE_B * sizeof(float) + 2048 * sizeof(int));
 static const size_t SMEM_SF64 = tile_smem<SF_BM, SFW_BN, SFW_BK, false, true>() + SFW_BN * sizeof(int);
 static constexpr auto k_score_bwd_n = k_score_bwd<32, GT_BK>;
 static constexpr auto k_score_bwd_w = k_score_bwd<64, 64>;
 static const size_t SMEM_SBW = std::max(tile_smem<64, 64, 64, true, false>(), tile_smem<64, 64, 64, false, false>());
-static inline bool wide_scores(const DevModel& d) {
-    const bool off = false;
-    const int minB = 256, minN = 4096;
-    // (a top layer that is a multiple of 64 takes the 64 x 64 tiles of k_score_bwd2 from B = 192, 2048 columns on: B = 240, N = 2288,
-    // D = 512 measured 22.2 vs 25.1 us against the 32 x 32 tiles)
-    const int d64 = 1;
-    return !off && ((d.B >= minB && d.ldSc >= minN) || (d64 && d.Dtop % 64 == 0 && d.B >= std::min(minB, 192) && d.ldSc >= std::min(minN, 2048)));
-}
-// LDS-DMA tiles (gemm_tile3, k_score_fwd_t3), D a multiple of 32: where gemm_tile2 served (long score rows / big batches), and
-// for a wide top layer (D >= 256) whenever the batch fills 64-row tiles -- there the launch is a few hundred tiles, fewer than
-// the chip holds at once, and only the ring's depth hides a stage's memory round trip (B = 240, N = 2288, D = 512: 18.7 -> 15.0 us)
 #define ZROW_FLOATS 8192      // DevModel::zrow: an LDS-DMA tile walks K floats along it
 #define G4R_DEFER_SLOTS 16    // ring slots of the step planes = steps of a deferral window (= G4R_GRAPH_STEPS; a power of two)
-static inline bool score_fwd_dma(const DevModel& d) {
-    if (d.Dtop % 32 != 0) return false;
-    return wide_scores(d) || (d.Dtop >= 256 && d.B >= 64 && d.ldSc >= 1024);
-}
 static const size_t SMEM_SF = tile_smem<SF_BM, GT_BN, GT_BK, false, true>() + GT_BN * sizeof(int);
-// macro-tile scoring forward (k_score_mt, g4r_score_mt.cuh): the score matrix cut into at most n_cu tiles of 64 rows x W = 64 NB + 16
-// columns, one per compute unit.  Applies when that W is one of the instantiated widths: returns W (0: the 64 x 64 tiles).
-// G4R_NO_MT=1: off (A/B runs).
 static constexpr auto k_score_mt_4s = k_score_mt<4, true>;       // W = 272: B = 512, N = 8704 on 256 CUs
 static const size_t SMEM_MT_4S = (size_t)MtCfg<4, true>::SMEM_FLOATS * sizeof(float);
-static inline int score_mt_width(const DevModel& d, int n_cu) {
-    static const bool off = getenv("G4R_NO_MT") != nullptr;
-    if (off || !score_fwd_dma(d) || d.Dtop % 16 != 0) return 0;
-    const int nrb = cdiv(d.B, 64), G = n_cu / nrb;
-    if (G < 1) return 0;
-    const int W = 16 * cdiv(d.ldSc, 16 * G);
-    return (W == 272 && nrb * cdiv(d.ldSc, W) * 8 >= n_cu * 7) ? W : 0;      // (tiles for >= 7/8 of the CUs)
-}
-// scoring forward as register-fed 32 x 32 tiles (k_score_s, g4r_lean_kernels.cuh): narrow top layers at RSC15-like sizes, i.e. where the
-// LDS-staged 64 x 32 tiles of k_score_fwd ran (neither the wide-score nor the LDS-DMA tiles apply).  G4R_NO_LEAN=1: off.
-static inline bool lean_scores(const DevModel& d) {
-    static const bool off = getenv("G4R_NO_LEAN") != nullptr;
-    return !off && d.Dtop <= LN_MAXD && d.Dtop % 4 == 0 && !wide_scores(d) && !score_fwd_dma(d) && d.B < 65536 && d.ldSc < 65536;
-}
-// ... and the scoring backward as k_score_b (eight waves over a K of <= 128 batch rows / 128-column slabs)
-static inline bool lean_score_bwd(const DevModel& d) { return lean_scores(d) && d.B <= 128; }
 static const size_t SMEM_T2K = (size_t)(4 * 64 * 16) * sizeof(float);                               // gemm_tile2k: two 16-deep buffers per operand
 static const size_t SMEM_T3 = (size_t)Tile3Cfg<3, 32>::SMEM_FLOATS * sizeof(float);                 // gemm_tile3: ring of three 32-deep stages
+
+// the dense-gradient tiles of the model's GRU weights, TR x TC each (k_dense_grad: 32 x 32, k_dense_grad2: 64 x 64, k_update_l: 16 x 64)
+static std::vector<DenseTile> dense_tiles(const DevModel& d, int TR, int TC) {
+    std::vector<DenseTile> tiles;
+    for (int l = 0; l < d.n_layers; ++l) {
+        const int D = d.D[l], IN = d.IN[l];
+        auto add = [&](const float* x0, const float* x1, int ldx, int nrows, int ncols, int coff, int ldo, long long base) {
+            for (int r = 0; r < nrows; r += TR)
+                for (int c = 0; c < ncols; c += TC) {
+                    DenseTile t;
+                    t.X0 = x0; t.X1 = x1; t.dV = d.dV[l]; t.base = base; t.ldx = ldx; t.ldv = 3 * D; t.nrows = nrows;
+                    t.ncols = ncols; t.coff = coff; t.ldo = ldo; t.r0 = r; t.c0 = c; t.gather = (x0 == nullptr && nrows > 1) ? 1 : 0; t.pad = 0;
+                    tiles.push_back(t);
+                }
+        };
+        const float* yin = (l == 0) ? nullptr : d.hd[l - 1];     // layer 0: gathered in the kernel (a one-hot input has IN = 0: no tiles)
+        add(yin, yin, IN, IN, 3 * D, 0, 3 * D, d.offWx[l]);                   // dWx  = yin^T dV
+        add(d.Hr[l], d.Hr[l], D, D, D, 0, D, d.offWh[l]);                     // dWh  = (H r)^T dV[:, :D]
+        add(d.H[l][0], d.H[l][1], D, D, 2 * D, D, 2 * D, d.offWrz[l]);        // dWrz = H^T dV[:, D:]
+        add(nullptr, nullptr, 0, 1, 3 * D, 0, 3 * D, d.offBh[l]);             // dBh  = colsum(dV) (nrows == 1: the column-sum role)
+    }
+    return tiles;
+}
+
+// Which kernel runs each stage of the training step, from the shapes in `d` (d.touched included), the CU count and the switches: every
+// precedence rule written once, for launch_step, the memory plan of g4r_create, the prediction GRU and the debug keys.
+static StepKernels choose_kernels(const DevModel& d, int n_cu, const KernelSwitches& sw, bool defer_on) {
+    StepKernels k = {};
+    const int L = d.n_layers, B = d.B, top = L - 1;
+    const bool onehot = d.embed_mode == G4R_EMBED_ONEHOT;
+    auto deep = [&](int forced, int D) { return forced >= 0 ? forced != 0 : (D >= 384 && cdiv(D, GT_BN) * cdiv(B, GT_BM) <= n_cu); };
+    // Wide layers: the K-sliced kernels of g4r_wide_kernels.cuh.  G4R_WIDE2 is a bit mask -- 1 k_gru_p1s + k_gru_gate, 8 k_gru_bwd_bw,
+    // 16 k_dense_grad2; 0 = the round-1 kernels -- default: the policy below, from the A/B runs of round 5 (profiles/r05_experiments.md):
+    //   16  the 64 x 64 dense-gradient tiles as a launch of their own where the dense gradients outweigh the sparse rows
+    //       (6 D >= 2 B + n_sample: BASELINE configs[2] yes -- k_update 24.4 us as one launch, 17.7 + 7.5 as two; configs[3] shape no --
+    //       20.6 merged, 20.3 + 13.4 apart: there the merged launch runs its two roles side by side)
+    //    8  dy as K-slice partial sums wherever a consumer adds them up: the lower layer's k_gru_bwd_pre (any layer above an unfused
+    //       one); for layer 0 the row-finishing workgroups of k_dense_grad2 (17.5 -> 7.0 us at configs[2]) or, with the merged k_update,
+    //       k_finish_rows as a small launch in front of it (configs[3] shape: 10.8 -> 5.0 + 4.2 us, step 170.3 -> 167.7)
+    //    1  phase 1 as partial sums + k_gru_gate from D = 512 on (25.0 -> 18.3 + 4.5 us at configs[2]; D = 256: 13.9 -> 12.9 + 4.3, off)
+    // K-slice lengths for A/B runs: G4R_P1_KS (<= 128), G4R_BB_KS.
+    int dmax = 0;
+    for (int l = 0; l < L; ++l) dmax = std::max(dmax, d.D[l]);
+    const bool automask = sw.wide2 < 0;
+    const int mask = automask ? (1 | 8 | (6 * dmax >= d.R ? 16 : 0)) : sw.wide2;
+    k.wide_dense = (mask & 16) && wide_layer(dmax) && !onehot;
+    for (int l = 0; l < L; ++l) {
+        const int D = d.D[l], IN = d.IN[l];
+        const bool onehot0 = l == 0 && onehot;      // (no input rows: layer 0 reads rows of Wx[0])
+        // narrow layers: the lean launches, in and D up to LN_MAXD.  Else (G4R_NO_LEAN=1) the fused kernels of round 2 where their LDS
+        // plans hold the operands (k_gru_fwd_fused: load maps of 112 rows / columns; k_gru_bwd_fused: D up to BF_MAXD)
+        const bool lean = !sw.no_lean && D <= LN_MAXD && IN <= LN_MAXD && D % 4 == 0 && IN % 4 == 0 && IN >= 4 && !onehot0;
+        const bool ffwd = D <= FF_LDR && IN <= FF_LDR && D % 4 == 0 && IN % 4 == 0 && IN >= 4 && !onehot0 &&
+                          (size_t)fwd_fused_lds(IN, D).total * sizeof(float) <= 156 * 1024;
+        const bool fbwd = D <= BF_MAXD && D % 4 == 0 && IN % 4 == 0 && !onehot0;
+        WideGeo& G = k.wg[l];
+        G = WideGeo();
+        if (wide_layer(D) && D % 64 == 0 && IN % 16 == 0 && IN >= 64 && !onehot0) {
+            // phase 1: slices of <= 128 units (all in flight at once: gemm_tile2k_full); k_gru_gate adds <= 8 input / <= 16 slices in all
+            if ((mask & 1) && (!automask || D >= 512)) {
+                const int ks = std::min(128, std::max(16, sw.p1_ks / 16 * 16));
+                G.ny = cdiv(IN, ks); G.kys = ((cdiv(IN, G.ny) + 15) / 16) * 16; G.ny = cdiv(IN, G.kys);
+                G.nh = cdiv(D, ks); G.khs = ((cdiv(D, G.nh) + 15) / 16) * 16; G.nh = cdiv(D, G.khs);
+                if (G.ny <= 8 && G.ny + G.nh <= 16) G.use |= 1;
+            }
+            // dy: enough slices of >= 128 (multiples of 32) for a workgroup per CU, <= 16 (what a consumer adds up in one round trip)
+            const bool consumer = l == 0 || k.bwd[l - 1] != BWD_FUSED;
+            if ((mask & 8) && consumer) {
+                const int K = 3 * D, tiles = cdiv(IN, 64) * cdiv(B, 64);
+                const int n = std::min(std::max(1, cdiv(n_cu, std::max(tiles, 1))), std::max(1, K / 128));
+                int ks = ((cdiv(K, n) + 31) / 32) * 32;
+                if (sw.bb_ks > 0) ks = std::max(32, sw.bb_ks / 32 * 32);
+                if (cdiv(K, ks) <= 16) { G.use |= 8; G.bbk = ks; G.bbn = cdiv(K, ks); }
+            }
+        }
+        k.fwd[l] = lean ? FWD_LEAN : ffwd ? FWD_FUSED : (G.use & 1) ? FWD_P1S : wide_layer(D) ? FWD_P1_N64 : FWD_P1_N32;
+        k.bwd[l] = lean ? BWD_LEAN : fbwd ? BWD_FUSED : onehot0 ? BWD_ONEHOT : (G.use & 8) ? BWD_BW : BWD_B;
+        k.p2_deep[l] = deep(sw.p2_geo, D);
+        k.ba_deep[l] = deep(sw.ba_geo, D);
+    }
+    // `wide`: long score rows / big batches; D a multiple of 64 from B = 192, N = 2048 on (B = 240, N = 2288, D = 512: 22.2 vs 25.1 us)
+    const int Dt = d.Dtop;
+    const bool wide = (B >= 256 && d.ldSc >= 4096) || (Dt % 64 == 0 && B >= 192 && d.ldSc >= 2048);
+    // LDS-DMA tiles (k_score_fwd_t3), D a multiple of 32: `wide`, and a wide top layer whenever the batch fills 64-row tiles -- fewer tiles than
+    // the chip holds, only the ring's depth hides a stage's round trip (B = 240, N = 2288, D = 512: 18.7 -> 15.0 us)
+    const bool dma = Dt % 32 == 0 && (wide || (Dt >= 256 && B >= 64 && d.ldSc >= 1024));
+    // k_score_mt: <= n_cu tiles of 64 rows x W = 272 columns filling >= 7/8 of the CUs.  Its two-stage pipeline needs an even number of
+    // 16-deep chunks: D a multiple of 32, at least 32.  G4R_NO_MT=1: off.
+    bool mt = false;
+    if (!sw.no_mt && dma && Dt % 32 == 0 && Dt >= 32 && n_cu / cdiv(B, 64) >= 1) {
+        const int nrb = cdiv(B, 64), W = 16 * cdiv(d.ldSc, 16 * (n_cu / nrb));
+        mt = W == 272 && nrb * cdiv(d.ldSc, W) * 8 >= n_cu * 7;
+    }
+    // k_score_s / k_score_b (register-fed 32 x 32 tiles): narrow top layers where k_score_fwd's LDS-staged tiles ran; k_score_b to B = 128
+    const bool lean_s = !sw.no_lean && Dt <= LN_MAXD && Dt % 4 == 0 && !wide && !dma && B < 65536 && d.ldSc < 65536;
+    k.score_fwd = lean_s ? SF_LEAN : mt ? SF_MT : dma ? SF_T3 : (wide && Dt % T2_BK == 0) ? SF_T2 : wide ? SF_K64 : SF_K128;
+    // the (final activation, loss) pairs of BASELINE's configurations run compile-time specialised builds of the row-loss kernel
+    k.loss_spec = (d.final_act == G4R_ACT_ELU && d.loss == G4R_LOSS_BPR_MAX) ? 1 : (d.final_act == G4R_ACT_SOFTMAX && d.loss == G4R_LOSS_XE) ? 2
+                : (d.final_act == G4R_ACT_ELU && d.loss == G4R_LOSS_TOP1_MAX) ? 3 : 0;
+    k.loss_long = (size_t)(2 * d.ldSc + 18 * LOSS_NW) * sizeof(float) > (size_t)(156 * 1024);      // one row copy in LDS, the other in the score row itself
+    // four columns per thread and trip from 4 columns per thread on (B = 512, 8192 negatives: 15.2 -> 13.0 us; 2176 columns: no difference)
+    k.loss_quads = d.ldSc >= 4 * LOSS_T;
+    // Scoring backward: k_score_b, else k_score_bmt, else k_score_bwd2 (`wide`, D a multiple of 64), else k_score_bwd_w / _n.  k_score_bmt:
+    // role A 272 x 32 tiles, role B 64 x 128 tiles x `ks` slabs, as many of each, two per CU.  It needs D a multiple of 128 up to 512, 272 /
+    // (D / 32) bias columns per tile (four threads each), slabs of a multiple of 32 columns up to 2048, and the top layer's k_gru_bwd_a
+    // (it carries the item rows' Adagrad rule).  G4R_NO_BMT=1: off.
+    const bool bwd2 = wide && Dt % 64 == 0;
+    const bool top_tiles = k.bwd[top] != BWD_LEAN && k.bwd[top] != BWD_FUSED;
+    if (!sw.no_bmt && bwd2 && top_tiles && Dt % 128 == 0 && Dt <= 512 && d.ldSc % BMT_WA == 0 && d.ldSc <= 0xFFFF && B <= 0xFFFF) {
+        const int ntA = d.ldSc / BMT_WA * (Dt / 32), den = cdiv(B, 64) * (Dt / 128), ks = ntA / den;
+        if (ntA % den == 0 && ntA % 8 == 0 && ntA <= n_cu && ntA * 8 >= n_cu * 7 && BMT_WA % (Dt / 32) == 0 && 4 * (BMT_WA / (Dt / 32)) <= 256 &&
+            ks >= 2 && ks <= 24 && d.ldSc % ks == 0 && (d.ldSc / ks) % 32 == 0 && d.ldSc / ks <= 2048)
+            k.bmt_slabs = ks;
+    }
+    k.score_bwd = (lean_s && B <= 128) ? SB_LEAN : k.bmt_slabs ? SB_BMT : bwd2 ? SB_BWD2 : wide ? SB_W : SB_N;
+    // its slabs: ~17; half as many, twice as deep where k_gru_bwd_fused / k_gru_da sum them next to everything else they load
+    const int slabs_target = top_tiles ? 17 : 9;
+    k.kch = GT_BK * std::max(1, (cdiv(d.ldSc, GT_BK) + slabs_target / 2) / slabs_target);
+    if (k.score_bwd == SB_LEAN) k.kch = 128;      // k_score_b: slabs of 128 score columns (eight waves x 16)
+    else if (k.score_bwd == SB_BMT) k.kch = d.ldSc / k.bmt_slabs;      // as many role-B as role-A tiles
+    else if (k.score_bwd == SB_BWD2) {
+        // k_score_bwd2's tiles are all resident at once: take the slab count (12..24) whose role A + B tiles fill whole rounds of CUs best
+        // (B = 512, N = 8704, D = 256: 17 slabs = 1088 tiles 64.2 us, 15 slabs = 1024 tiles 60.6 us); depth: 16-byte aligned rows
+        const int ndt = Dt / 64, nrt = cdiv(B, 64), nA = cdiv(d.ldSc, 64) * ndt;
+        double best = 2.0;
+        for (int ks = 12; ks <= 24; ++ks) {
+            const int kch = (cdiv(d.ldSc, ks) + 7) & ~7;
+            if (cdiv(d.ldSc, kch) != ks) continue;
+            const double rounds = (double)(nA + ks * nrt * ndt) / n_cu;
+            const double waste = (std::ceil(rounds) - rounds) / std::ceil(rounds) + 1e-3 * std::abs(ks - 17);
+            if (waste < best) { best = waste; k.kch = kch; }
+        }
+    }
+    k.ksplit = cdiv(d.ldSc, k.kch);
+    const int TB = wide ? 64 : 32;      // tile edge of k_score_bwd
+    k.ndtA = cdiv(Dt + 1, TB); k.nblkA = cdiv(d.ldSc, TB) * k.ndtA;
+    k.ndtB = cdiv(Dt, TB); k.nrtB = cdiv(B, TB); k.nblkB = k.ksplit * k.nrtB * k.ndtB;
+    // Update: dense-gradient tiles and sparse rows in ONE launch (k_update) on the Adagrad path, item rows of <= 512 floats (its registers
+    // hold two chunks per lane), no k_dense_grad2.  k_update_l: one GPU, B <= 128, rows of <= 256 floats, no deferral, no exact replicas,
+    // no touched-row bitmap, layer 0's dy not in partial sums.
+    const int w = std::max(Dt, d.Ein);
+    k.chunks = w <= 256 ? 1 : (w <= 512 ? 2 : 4);
+    const bool dy0_parts = (k.wg[0].use & 8) != 0;
+    const bool merged = !d.generic && !sw.no_merge && k.chunks <= 2 && !k.wide_dense;
+    const bool lean_u = !sw.no_lean && sw.allow_lean_update && merged && d.apply_dense_inplace && B <= 128 && k.chunks == 1 && !defer_on && d.xmode == 0 &&
+                        !d.touched && !dy0_parts && d.R < 65536 && cdiv(d.R, 8) < 65536 && dense_tiles(d, 16, 64).size() < 65536;
+    k.update = lean_u ? UP_LEAN : merged ? UP_MERGED : UP_SPLIT;
+    k.finish_rows = dy0_parts && !k.wide_dense;      // (k_dense_grad2 finishes the rows in workgroups of its own)
+    return k;
+}
 // publish the host descriptor to the device copy (stream-ordered; pageable source is staged before return)
 static int sync_dm(g4r_model* m) {
     HIPCHK(hipMemcpyAsync(m->d_dm, &m->dm, sizeof(DevModel), hipMemcpyHostToDevice, m->stream));

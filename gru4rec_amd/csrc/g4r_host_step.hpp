@@ -1,48 +1,29 @@
 // g4r_host_step.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
 // instantiated there).  Holds: the training step: launch_step (every launch of a step, in order), tail compaction, the captured step graphs, g4r_train_steps (+ virtual ranks), losses, counters, per-kernel profiling.
 // ------------------------------------------------------------------------------------------------ the step
-static inline bool no_merge_tail() { static const bool v = getenv("G4R_NO_MERGE") != nullptr; return v; }
-// float4 chunks per lane a gathered row needs in the sparse update: rows of <= 256 / 512 / 1024 floats
-static inline int row_chunks(const DevModel& d) { const int w = std::max(d.Dtop, d.Ein); return w <= 256 ? 1 : (w <= 512 ? 2 : 4); }
-// (rows wider than 512 floats take the two-launch form: k_update's register budget is sized for two chunks per lane)
-// (wide layers: the dense gradients run as 64 x 64 tiles in a launch of their own, k_dense_grad2, ahead of the sparse row update)
-// the lean form of the merged update (k_update_l, g4r_lean_kernels.cuh): one GPU, Adagrad(+momentum) with the dense rule fused, batches of <= 128
-// rows, item rows of <= 256 floats, no deferral, no touched-row bitmap (N > 1)
-static inline bool lean_update(const g4r_model* m);
-static inline bool merged_update(const g4r_model* m) { return !m->dm.generic && !no_merge_tail() && row_chunks(m->dm) <= 2 && !m->wide_dense; }
-static inline bool lean_update(const g4r_model* m) {
-    static const bool off = getenv("G4R_NO_LEAN") != nullptr;
-    const DevModel& d = m->dm;
-    return !off && m->lean_upd && merged_update(m) && m->d_leanU && d.apply_dense_inplace && d.B <= 128 && row_chunks(d) == 1 && !m->defer_on && d.xmode == 0 && !d.touched &&
-           d.R < 65536 && m->ntiles16 < 65536 && cdiv(d.R, 8) < 65536;
-}
+// Every launch of a training step, in order, as m->kern chose them (choose_kernels).
 // part: 0 = the whole step; 1 = head (everything up to the dense gradients); 2 = tail (all-reduce, dense apply, sparse update)
 static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
     DevModel& d = m->dm;
+    const StepKernels& k = m->kern;
     const int L = d.n_layers, B = d.B;
     hipStream_t s = m->stream;
     GruFwdPredict nopa = {};
     size_t evi = 0;
     hipEvent_t cur_a = nullptr, cur_b = nullptr;
+    static const bool trace = getenv("G4R_TRACE") != nullptr;
+    int trace_kn = -1;
+    // begin(kn) ... end(): the launches of kernel slot kn (KN_*).  Profiling: start / stop events attached to the dispatch itself
+    // (hipExtLaunchKernelGGL): kernel-only durations.  G4R_TRACE: every launch named on stderr and waited for.
     auto begin = [&](int kn) {
+        trace_kn = kn;
+        if (trace) { fprintf(stderr, "[g4r] launch %s\n", KN_NAMES[kn]); fflush(stderr); }
         if (!recs) return;
         while (m->evs.size() < evi + 2) { hipEvent_t e; (void)hipEventCreate(&e); m->evs.push_back(e); }
         EvRec r = {kn, m->evs[evi], m->evs[evi + 1]};
         evi += 2;
-        cur_a = r.a; cur_b = r.b;     // attached to the dispatch itself (hipExtLaunchKernelGGL): kernel-only duration
+        cur_a = r.a; cur_b = r.b;
         recs->push_back(r);
-    };
-    static const bool trace = getenv("G4R_TRACE") != nullptr;
-    // measurement aid (tools/kn_cost.py): bit k set = the launches of kernel slot k (KN_*) are left out of the step -- the step's results are
-    // garbage, its duration tells what that launch costs the captured step (HIP events and rocprofv3 both put a ~3 us floor under a dispatch
-    // that the graph does not pay: an empty kernel costs 1.5 us there, tools/probes/chain_probe.hip)
-    static const unsigned long long skip_kn = getenv("G4R_SKIP_KN") ? strtoull(getenv("G4R_SKIP_KN"), nullptr, 0) : 0ull;
-    int trace_kn = -1;
-    auto begin0 = begin;
-    auto begin_t = [&](int kn) {
-        trace_kn = kn;
-        if (trace) { fprintf(stderr, "[g4r] launch %s\n", KN_NAMES[kn]); fflush(stderr); }
-        begin0(kn);
     };
     auto end = [&]() {
         if (trace) {
@@ -51,19 +32,21 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
             fflush(stderr);
         }
     };
-#define begin begin_t
+    // (G4R_SKIP_KN, tools/kn_cost.py: the slots set in m->sw.skip_kn are left out; the duration tells what they cost the captured step --
+    // HIP events and rocprofv3 put a ~3 us floor under a dispatch that the graph does not pay, tools/probes/chain_probe.hip)
 #define LK(kern, grid, block, smem, strm, ...)                                                             \
     do {                                                                                                  \
-        if (skip_kn && trace_kn >= 0 && ((skip_kn >> trace_kn) & 1ull)) break;                            \
+        if (m->sw.skip_kn && trace_kn >= 0 && ((m->sw.skip_kn >> trace_kn) & 1ull)) break;                \
         if (recs) hipExtLaunchKernelGGL(kern, grid, block, smem, strm, cur_a, cur_b, 0, __VA_ARGS__);     \
         else hipLaunchKernelGGL(kern, grid, block, smem, strm, __VA_ARGS__);                              \
     } while (0)
     const DevModel* dmp = (const DevModel*)m->d_dm;
     StepState* stp = (StepState*)d.st;
-    bool merged = false;      // the sparse update already ran inside k_update
+    // g4r_profile(m, 2): the two roles of a merged update as launches of their own
+    const bool merged = k.update != UP_SPLIT && !(recs && m->profile_split);
     if (part != 2) {
     for (int l = 0; l < L; ++l) {
-        if (lean_gru(d, l)) {
+        if (k.fwd[l] == FWD_LEAN) {
             const int ntd = cdiv(d.D[l], 16), nrb = cdiv(B, 16);
             begin(KN_GRU_V);
             {
@@ -84,84 +67,92 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
             end();
             continue;
         }
-        if (fused_fwd(d, l)) {
+        if (k.fwd[l] == FWD_FUSED) {
             begin(KN_FWD_FUSED);
             LK(k_gru_fwd_fused, dim3(cdiv(d.D[l], 32), cdiv(B, FF_ROWS)), dim3(512), (size_t)fwd_fused_lds(d.IN[l], d.D[l]).total * sizeof(float), s, dmp, stp, l, l == 0 ? 1 : 0);
             end();
             continue;
         }
-        const g4r_model::WideGeo& G = m->wg[l];
+        const WideGeo& G = k.wg[l];
         const int nrt64 = cdiv(B, 64), nct64 = d.D[l] / 64;
         begin(KN_GRU_P1);
-        if (G.use & 1) {
+        if (k.fwd[l] == FWD_P1S) {
             LK(k_gru_p1s, dim3(nct64 * nrt64 * (3 * G.ny + 2 * G.nh)), dim3(256), SMEM_T2K, s, dmp, stp, l, l == 0 ? 1 : 0, G.ny, G.nh, G.kys, G.khs);
             end();
             begin(KN_GATE);
             LK(k_gru_gate, dim3(cdiv((long long)B * (d.D[l] / 4), 256)), dim3(256), 0, s, dmp, stp, l, G.ny, G.nh);
-        } else if (wide_layer(d.D[l])) LK(k_gru_p1_n64, dim3(cdiv(3 * d.D[l], 64), cdiv(B, GT_BM)), dim3(GT_NTH_FEW), SMEM_P1_N64, s, dmp, stp, l, 1, l == 0 ? 1 : 0, nopa);
+        } else if (k.fwd[l] == FWD_P1_N64) LK(k_gru_p1_n64, dim3(cdiv(3 * d.D[l], 64), cdiv(B, GT_BM)), dim3(GT_NTH_FEW), SMEM_P1_N64, s, dmp, stp, l, 1, l == 0 ? 1 : 0, nopa);
         else LK(k_gru_p1_n32, dim3(cdiv(3 * d.D[l], GT_BN), cdiv(B, GT_BM)), dim3(GT_NTH_FEW), SMEM_P1, s, dmp, stp, l, 1, l == 0 ? 1 : 0, nopa);
         end();
         begin(KN_GRU_P2);
         {
             const dim3 g2(cdiv(d.D[l], GT_BN), cdiv(B, GT_BM));
-            if (deep_geometry(m->p2_geo_env, m->n_cu, d.D[l], B)) LK(k_gru_p2_w8d, g2, dim3(512), SMEM_P2_256, s, dmp, stp, l, 1, nopa);
+            if (k.p2_deep[l]) LK(k_gru_p2_w8d, g2, dim3(512), SMEM_P2_256, s, dmp, stp, l, 1, nopa);
             else LK(k_gru_p2_w4, g2, dim3(GT_NTH), SMEM_NN, s, dmp, stp, l, 1, nopa);
         }
         end();
     }
     begin(KN_SCORE_FWD);
-    if (lean_scores(d)) {
+    switch (k.score_fwd) {
+    case SF_LEAN: {
         const unsigned dimsA = (unsigned)d.Dtop | ((unsigned)B << 16), dimsB = (unsigned)d.N | ((unsigned)d.ldSc << 16);
         const dim3 gs(cdiv(d.ldSc, 32), cdiv(B, 32));
         if (d.logq != 0.f) LK(k_score_s<true>, gs, dim3(256), 0, s, (const LeanS*)m->d_leanS, (const int*)(d.cur_in + 2 * B), (const int*)d.cur_col, (const float*)d.hd[L - 1],
                               (const float*)d.Wy, (const float*)d.By, (float*)d.Sc, dimsA, dimsB);
         else LK(k_score_s<false>, gs, dim3(256), 0, s, (const LeanS*)m->d_leanS, (const int*)(d.cur_in + 2 * B), (const int*)d.cur_col, (const float*)d.hd[L - 1],
                 (const float*)d.Wy, (const float*)d.By, (float*)d.Sc, dimsA, dimsB);
-    } else if (score_mt_width(d, m->n_cu) == 272) LK(k_score_mt_4s, dim3(cdiv(B, 64) * cdiv(d.ldSc, 272)), dim3(256), SMEM_MT_4S, s, (const int*)d.cur_col, (const int*)(d.cur_in + 2 * B),
-                                                       (const float*)d.hd[L - 1], (const float*)d.Wy, (const float*)d.zrow, dmp, (unsigned)d.Dtop | ((unsigned)cdiv(B, 64) << 16),
-                                                       (unsigned)d.N, (unsigned)d.ldSc, (unsigned)B);
-    else if (score_fwd_dma(d)) LK(k_score_fwd_t3, dim3(cdiv(d.ldSc, 64), cdiv(B, 64)), dim3(GT_NTH), SMEM_SF3, s, dmp, stp);
-    else if (wide_scores(d) && score_tile2() && d.Dtop % T2_BK == 0) LK(k_score_fwd_t2, dim3(cdiv(d.ldSc, 64), cdiv(B, 64)), dim3(GT_NTH), SMEM_SF2, s, dmp, stp);
-    else if (wide_scores(d)) LK(k_score_fwd_k64, dim3(cdiv(d.ldSc, SFW_BN), cdiv(B, SF_BM)), dim3(GT_NTH), SMEM_SF64, s, dmp, stp);
-    else LK(k_score_fwd_k128, dim3(cdiv(d.ldSc, GT_BN), cdiv(B, SF_BM)), dim3(GT_NTH), SMEM_SF, s, dmp, stp);
+        break;
+    }
+    case SF_MT: LK(k_score_mt_4s, dim3(cdiv(B, 64) * cdiv(d.ldSc, 272)), dim3(256), SMEM_MT_4S, s, (const int*)d.cur_col, (const int*)(d.cur_in + 2 * B),
+                   (const float*)d.hd[L - 1], (const float*)d.Wy, (const float*)d.zrow, dmp, (unsigned)d.Dtop | ((unsigned)cdiv(B, 64) << 16),
+                   (unsigned)d.N, (unsigned)d.ldSc, (unsigned)B); break;
+    case SF_T3: LK(k_score_fwd_t3, dim3(cdiv(d.ldSc, 64), cdiv(B, 64)), dim3(GT_NTH), SMEM_SF3, s, dmp, stp); break;
+    case SF_T2: LK(k_score_fwd_t2, dim3(cdiv(d.ldSc, 64), cdiv(B, 64)), dim3(GT_NTH), SMEM_SF2, s, dmp, stp); break;
+    case SF_K64: LK(k_score_fwd_k64, dim3(cdiv(d.ldSc, SFW_BN), cdiv(B, SF_BM)), dim3(GT_NTH), SMEM_SF64, s, dmp, stp); break;
+    default: LK(k_score_fwd_k128, dim3(cdiv(d.ldSc, GT_BN), cdiv(B, SF_BM)), dim3(GT_NTH), SMEM_SF, s, dmp, stp); break;
+    }
     end();
     begin(KN_LOSS);
     {
-        // the (final activation, loss) pairs of BASELINE's configurations run compile-time specialised builds of the kernel
-        const int spec = (d.final_act == G4R_ACT_ELU && d.loss == G4R_LOSS_BPR_MAX) ? 1
-                       : (d.final_act == G4R_ACT_SOFTMAX && d.loss == G4R_LOSS_XE) ? 2
-                       : (d.final_act == G4R_ACT_ELU && d.loss == G4R_LOSS_TOP1_MAX) ? 3 : 0;
-#define G4R_LK_LOSS(L, V)                                                                              \
-        do {                                                                                           \
-            if (spec == 1) LK((k_loss_rows<L, 1, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp);      \
-            else if (spec == 2) LK((k_loss_rows<L, 2, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp); \
-            else if (spec == 3) LK((k_loss_rows<L, 3, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp); \
-            else LK((k_loss_rows<L, 0, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp);                \
+#define G4R_LK_LOSS(L, V)                                                                                                      \
+        do {                                                                                                                   \
+            if (k.loss_spec == 1) LK((k_loss_rows<L, 1, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp);      \
+            else if (k.loss_spec == 2) LK((k_loss_rows<L, 2, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp); \
+            else if (k.loss_spec == 3) LK((k_loss_rows<L, 3, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp); \
+            else LK((k_loss_rows<L, 0, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp);                       \
         } while (0)
-        if (m->loss_long) G4R_LK_LOSS(true, 4);      // (rows that long always take four columns per thread)
-        else { if (m->loss_quads) G4R_LK_LOSS(false, 4); else G4R_LK_LOSS(false, 1); }
+        if (k.loss_long) G4R_LK_LOSS(true, 4);      // (rows that long always take four columns per thread)
+        else { if (k.loss_quads) G4R_LK_LOSS(false, 4); else G4R_LK_LOSS(false, 1); }
 #undef G4R_LK_LOSS
     }
     end();
     begin(KN_SCORE_BWD);
-    if (lean_score_bwd(d)) {
+    switch (k.score_bwd) {
+    case SB_LEAN: {
         const LeanB& q = m->h_leanB;
         LK(k_score_b, dim3(q.nA + d.ksplit * q.nrb * q.ndb), dim3(512), 0, s, (const LeanB*)m->d_leanB, (const int*)(d.cur_in + 2 * B), (const int*)d.cur_col,
            (const float*)d.Sc, (const float*)d.hd[L - 1], (const float*)d.Wy, (float*)d.accWy, (unsigned)d.Dtop | ((unsigned)B << 16), (unsigned)d.N | ((unsigned)d.ldSc << 16));
-    } else if (score_bmt_slabs(d, m->n_cu)) {
+        break;
+    }
+    case SB_BMT: {
         const int ntile = d.ldSc / BMT_WA * (d.Dtop / 32);
         LK(k_score_bmt, dim3(2 * ntile), dim3(256), SMEM_BMT, s, (const float*)d.Sc, (const float*)d.hd[L - 1], (const float*)d.Wy, (const int*)d.col_item,
            (const int*)(d.cur_in + 2 * B), (const float*)d.zrow, dmp, (unsigned)d.Dtop | ((unsigned)(d.Dtop / 32) << 16), (unsigned)d.N | ((unsigned)d.ldSc << 16),
            (unsigned)B | ((unsigned)d.kch << 16), (unsigned)cdiv(B, 64) | ((unsigned)(d.Dtop / 128) << 16));
-    } else if (score_bwd2(d)) {
+        break;
+    }
+    case SB_BWD2: {
         const int ndt = d.Dtop / 64, nrt = cdiv(B, 64);
         int nA = cdiv(d.ldSc, 64) * ndt, nB = d.ksplit * nrt * ndt, nC = cdiv(d.ldSc, 64);
         LK(k_score_bwd2, dim3(nA + nB + nC), dim3(GT_NTH), (size_t)(4 * 64 * 16) * sizeof(float) + (size_t)std::max(d.kch, 64) * sizeof(int), s, dmp, stp, nA, nB, ndt, nrt);
-    } else if (wide_scores(d)) LK(k_score_bwd_w, dim3(m->nblkA + m->nblkB), dim3(GT_NTH), SMEM_SBW + (size_t)d.kch * sizeof(int), s, dmp, stp, m->nblkA, m->ndtA, m->ndtB, m->nrtB);
-    else LK(k_score_bwd_n, dim3(m->nblkA + m->nblkB), dim3(GT_NTH), std::max(SMEM_TN, SMEM_NN) + (size_t)d.kch * sizeof(int), s, dmp, stp, m->nblkA, m->ndtA, m->ndtB, m->nrtB);
+        break;
+    }
+    case SB_W: LK(k_score_bwd_w, dim3(k.nblkA + k.nblkB), dim3(GT_NTH), SMEM_SBW + (size_t)d.kch * sizeof(int), s, dmp, stp, k.nblkA, k.ndtA, k.ndtB, k.nrtB); break;
+    default: LK(k_score_bwd_n, dim3(k.nblkA + k.nblkB), dim3(GT_NTH), std::max(SMEM_TN, SMEM_NN) + (size_t)d.kch * sizeof(int), s, dmp, stp, k.nblkA, k.ndtA, k.ndtB, k.nrtB); break;
+    }
     end();
     for (int l = L - 1; l >= 0; --l) {
-        if (lean_gru(d, l)) {
+        if (k.bwd[l] == BWD_LEAN) {
             const int nrb = cdiv(B, 16);
             begin(KN_GRU_DA);
             {
@@ -179,16 +170,16 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
             end();
             continue;
         }
-        if (fused_bwd(d, l)) {
+        if (k.bwd[l] == BWD_FUSED) {
             begin(KN_BWD_FUSED);
-            LK(k_gru_bwd_fused, dim3(cdiv(d.IN[l], 32), cdiv(B, BF_ROWS)), dim3(512), smem_fused_bwd(d.D[l]), s, dmp, stp, l);
+            LK(k_gru_bwd_fused, dim3(cdiv(d.IN[l], 32), cdiv(B, BF_ROWS)), dim3(512), smem_bwd_fused(d.D[l]), s, dmp, stp, l);
             end();
             continue;
         }
         begin(KN_BWD_PRE);
         LK(k_gru_bwd_pre, dim3(cdiv((long long)B * d.D[l], 256)), dim3(256), 0, s, dmp, stp, l);
         end();
-        const g4r_model::WideGeo& G = m->wg[l];
+        const WideGeo& G = k.wg[l];
         const int nrt64 = cdiv(B, 64);
         begin(KN_BWD_A);
         {
@@ -196,32 +187,28 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
             // behind k_score_bmt (raw gradient rows in the step plane) the top layer's launch carries their Adagrad rule: one extra
             // workgroup per 16 item rows (score_fin_rows)
             int nfin = 0;
-            if (l == L - 1 && score_bmt_slabs(d, m->n_cu)) { nfin = cdiv(cdiv(d.N, 16), (int)ga.x); ga.y += nfin; }
-            if (deep_geometry(m->ba_geo_env, m->n_cu, d.D[l], B)) LK(k_gru_bwd_a_w8d, ga, dim3(512), SMEM_BA_256, s, dmp, stp, l, nfin);
+            if (l == L - 1 && k.score_bwd == SB_BMT) { nfin = cdiv(cdiv(d.N, 16), (int)ga.x); ga.y += nfin; }
+            if (k.ba_deep[l]) LK(k_gru_bwd_a_w8d, ga, dim3(512), SMEM_BA_256, s, dmp, stp, l, nfin);
             else LK(k_gru_bwd_a_w4, ga, dim3(GT_NTH), SMEM_NT, s, dmp, stp, l, nfin);
         }
         end();
         begin(KN_BWD_B);
-        if (l == 0 && d.embed_mode == G4R_EMBED_ONEHOT) LK(k_onehot_step, dim3(cdiv((long long)B * d.Ein, 4 * 256)), dim3(256), 0, s, dmp, stp);
-        else if (G.use & 8) LK(k_gru_bwd_bw, dim3(cdiv(d.IN[l], 64) * nrt64 * G.bbn), dim3(256), SMEM_T3, s, dmp, stp, l, G.bbn, G.bbk);
+        if (k.bwd[l] == BWD_ONEHOT) LK(k_onehot_step, dim3(cdiv((long long)B * d.Ein, 4 * 256)), dim3(256), 0, s, dmp, stp);
+        else if (k.bwd[l] == BWD_BW) LK(k_gru_bwd_bw, dim3(cdiv(d.IN[l], 64) * nrt64 * G.bbn), dim3(256), SMEM_T3, s, dmp, stp, l, G.bbn, G.bbk);
         else LK(k_gru_bwd_b, dim3(cdiv(d.IN[l], GT_BN), cdiv(B, GT_BM)), dim3(GT_NTH_FEW), SMEM_BB, s, dmp, stp, l);
         end();
     }
-    merged = merged_update(m) && !(recs && m->profile_split);      // g4r_profile(m, 2): the two roles of k_update as launches of their own
     if (merged) {
         // dense-gradient tiles (+ fused dense Adagrad on a single GPU; gradients to the RCCL buffer otherwise) and the sparse row
         // update in ONE launch (k_update): the two are independent, the all-reduce / dense apply of N > 1 follow behind
-        const size_t smem = std::max(SMEM_TN, m->smem_sparse);
-        const dim3 grid(m->ntiles + m->nblk_occ + 1), blk(SP_WAVES * 64);
-        const bool one = row_chunks(d) == 1;
-        if (d.bbn[0] > 0) {      // (dy of layer 0 as K-slice partial sums with the merged update: only when asked for, G4R_WIDE2)
+        if (k.finish_rows) {      // (dy of layer 0 as K-slice partial sums with the merged update: only when asked for, G4R_WIDE2)
             begin(KN_FINISH);
             LK(k_finish_rows, dim3(cdiv((long long)B * (d.IN[0] / 4), 256)), dim3(256), 0, s, dmp, stp);
             end();
         }
         begin(KN_UPDATE);
         const bool mo = d.mom > 0.f;
-        if (lean_update(m) && !(d.bbn[0] > 0)) {
+        if (k.update == UP_LEAN) {
             const int nb8 = cdiv(d.R, 8);
             const unsigned packA = (unsigned)m->ntiles16 | ((unsigned)nb8 << 16), packB = (unsigned)d.R | ((unsigned)B << 16);
             const unsigned nbk = 1u + (unsigned)cdiv(d.ldSc, 512);
@@ -234,58 +221,57 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
             HIPCHK(hipGetLastError());
             return 0;
         }
+        const size_t smem = std::max(SMEM_TN, m->smem_sparse);
+        const dim3 grid(m->ntiles + m->nblk_occ + 1), blk(SP_WAVES * 64);
 #define G4R_LK_UPDATE(CH, DT_)                                                                                                          \
         do {                                                                                                                            \
             if (mo) LK((k_update<CH, DT_, true>), grid, blk, smem, s, dmp, stp, (const DenseTile*)m->d_tiles, m->ntiles, m->nblk_occ);  \
             else LK((k_update<CH, DT_, false>), grid, blk, smem, s, dmp, stp, (const DenseTile*)m->d_tiles, m->ntiles, m->nblk_occ);    \
         } while (0)
-        if (one) G4R_LK_UPDATE(1, 32); else G4R_LK_UPDATE(2, 32);
+        if (k.chunks == 1) G4R_LK_UPDATE(1, 32); else G4R_LK_UPDATE(2, 32);
 #undef G4R_LK_UPDATE
         end();
         if (d.apply_dense_inplace || part == 1) { HIPCHK(hipGetLastError()); return 0; }
     } else {
     // (the dense-gradient tiles on a BRANCH of the step graph next to the sparse rows -- they share nothing -- were measured: the
-    // fork / join costs more than the overlap gives, 126.6 -> 139.8 us per step at configs[2]; profiles/r05_experiments.md #8)
+    // fork / join costs more than running them side by side gives, 126.6 -> 139.8 us per step at configs[2]; profiles/r05_experiments.md #8)
     begin(KN_DENSE);
-    if (m->wide_dense) LK(k_dense_grad2, dim3(m->ntiles64 + (d.bbn[0] > 0 ? cdiv((long long)B * (d.IN[0] / 4), 256) : 0)), dim3(256), SMEM_T2K, s, dmp, stp, (const DenseTile*)m->d_tiles64, m->ntiles64);
+    if (k.wide_dense) LK(k_dense_grad2, dim3(m->ntiles64 + (d.bbn[0] > 0 ? cdiv((long long)B * (d.IN[0] / 4), 256) : 0)), dim3(256), SMEM_T2K, s, dmp, stp, (const DenseTile*)m->d_tiles64, m->ntiles64);
     else {
-        if (d.bbn[0] > 0) { LK(k_finish_rows, dim3(cdiv((long long)B * (d.IN[0] / 4), 256)), dim3(256), 0, s, dmp, stp); }
+        if (k.finish_rows) LK(k_finish_rows, dim3(cdiv((long long)B * (d.IN[0] / 4), 256)), dim3(256), 0, s, dmp, stp);
         LK(k_dense_grad<32>, dim3(m->ntiles), dim3(GT_NTH_FEW), SMEM_TN, s, dmp, stp, (const DenseTile*)m->d_tiles);
     }
     end();
     }
     }
     if (part == 1) { HIPCHK(hipGetLastError()); return 0; }
-    if (part == 2) merged = merged_update(m) && !(recs && m->profile_split);
     // multi-rank: dense-gradient all-reduce, dense Adagrad, then the sparse embedding update, in stream order.
     // (running the first two on a stream of their own next to the sparse update -- which touches item rows only -- was measured on one
     // MI355X with a one-rank communicator: the two cross-stream event dependencies cost ~20 us per step, more than the ~11 us of sparse
     // update they can hide; that path was removed in round 6)
-    const bool overlap = false;
     if (!d.apply_dense_inplace) {
         // staged dense path: (RCCL all-reduce when there are ranks) -> (global gradient norm -> clip factor, generic path with
         // grad_cap) -> dense rule on the flat gradient buffer
         const bool dist = !m->virtual_ranks && (m->cfg.nranks > 1 || m->comm_ready || m->p2p_ready);
         if (m->cfg.nranks > 1 && !m->comm_ready && !m->p2p_ready && !m->virtual_ranks) return fail("nranks > 1 but g4r_comm_init was not called");
-        hipStream_t cs = overlap ? m->comm_stream : s;
         if (dist && !m->exact) {      // (exact-replica mode: the dense gradients travel with the all-gather of the occurrence blocks below)
-            if (overlap) { HIPCHK(hipEventRecord(m->ev_fork, s)); HIPCHK(hipStreamWaitEvent(cs, m->ev_fork, 0)); }
-            if (!overlap) { begin(KN_ALLREDUCE); if (recs) (void)hipEventRecord(cur_a, cs); }
-            if (m->p2p_ready) hipLaunchKernelGGL(k_p2p_allreduce, dim3(m->p2p_nblk), dim3(256), 0, cs, m->p2p_args, (float*)d.dense_g);
-            else NCCLCHK(ncclAllReduce(d.dense_g, d.dense_g, d.dense_count, ncclFloat, ncclSum, m->comm, cs));
-            if (!overlap) { if (recs) (void)hipEventRecord(cur_b, cs); end(); }
+            begin(KN_ALLREDUCE);
+            if (recs) (void)hipEventRecord(cur_a, s);
+            if (m->p2p_ready) hipLaunchKernelGGL(k_p2p_allreduce, dim3(m->p2p_nblk), dim3(256), 0, s, m->p2p_args, (float*)d.dense_g);
+            else NCCLCHK(ncclAllReduce(d.dense_g, d.dense_g, d.dense_count, ncclFloat, ncclSum, m->comm, s));
+            if (recs) (void)hipEventRecord(cur_b, s);
+            end();
         }
         if (d.generic && d.grad_cap > 0.f) {
-            hipLaunchKernelGGL(k_grad_sqsum, dim3(G4R_NORM_BLOCKS), dim3(256), 0, cs, dmp, stp);
-            hipLaunchKernelGGL(k_grad_clip, dim3(1), dim3(64), 0, cs, dmp);
+            hipLaunchKernelGGL(k_grad_sqsum, dim3(G4R_NORM_BLOCKS), dim3(256), 0, s, dmp, stp);
+            hipLaunchKernelGGL(k_grad_clip, dim3(1), dim3(64), 0, s, dmp);
         }
         // (generic optimizer path: the dense rule runs as extra workgroups of the sparse update's launch below)
         if (!d.generic) {
-            if (!overlap) begin(KN_DENSE_APPLY);
-            LK(k_dense_apply, dim3(cdiv(d.dense_count, 256)), dim3(256), 0, cs, (const DevModel*)m->d_dm);
-            if (!overlap) end();
+            begin(KN_DENSE_APPLY);
+            LK(k_dense_apply, dim3(cdiv(d.dense_count, 256)), dim3(256), 0, s, (const DevModel*)m->d_dm);
+            end();
         }
-        if (dist && overlap) HIPCHK(hipEventRecord(m->ev_join, cs));
     }
     if (d.generic) {
         // generic optimizer path: the sparse rule on raw per-occurrence gradients
@@ -305,8 +291,8 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
         }
         begin(KN_SPARSE);
         const int nda = d.apply_dense_inplace ? 0 : cdiv(d.dense_count, SP_WAVES * 64);      // workgroups of the dense rule behind the row blocks
-        if (row_chunks(d) == 1) LK(k_sparse_update_generic<1>, dim3(nblk_g + 1 + nda), dim3(SP_WAVES * 64), smem_g, s, dmp, stp, nblk_g, nda);
-        else if (row_chunks(d) == 2) LK(k_sparse_update_generic<2>, dim3(nblk_g + 1 + nda), dim3(SP_WAVES * 64), smem_g, s, dmp, stp, nblk_g, nda);
+        if (k.chunks == 1) LK(k_sparse_update_generic<1>, dim3(nblk_g + 1 + nda), dim3(SP_WAVES * 64), smem_g, s, dmp, stp, nblk_g, nda);
+        else if (k.chunks == 2) LK(k_sparse_update_generic<2>, dim3(nblk_g + 1 + nda), dim3(SP_WAVES * 64), smem_g, s, dmp, stp, nblk_g, nda);
         else LK(k_sparse_update_generic<4>, dim3(nblk_g + 1 + nda), dim3(SP_WAVES * 64), smem_g, s, dmp, stp, nblk_g, nda);
         end();
         HIPCHK(hipGetLastError());
@@ -322,12 +308,10 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
             if (mo) LK((k_sparse_update<CH, true>), grid, blk, m->smem_sparse, s, dmp, stp, m->nblk_occ);            \
             else LK((k_sparse_update<CH, false>), grid, blk, m->smem_sparse, s, dmp, stp, m->nblk_occ);              \
         } while (0)
-        if (row_chunks(d) == 1) G4R_LK_SPARSE(1); else if (row_chunks(d) == 2) G4R_LK_SPARSE(2); else G4R_LK_SPARSE(4);
+        if (k.chunks == 1) G4R_LK_SPARSE(1); else if (k.chunks == 2) G4R_LK_SPARSE(2); else G4R_LK_SPARSE(4);
 #undef G4R_LK_SPARSE
     }
     end();
-    if (overlap) HIPCHK(hipStreamWaitEvent(s, m->ev_join, 0));
-#undef begin
 #undef LK
     HIPCHK(hipGetLastError());
     return 0;

@@ -45,6 +45,12 @@ int g4r_sync_enable(g4r_model* m) {
     }
     d.touched = m->d_touched;
     m->sync_on = true;
+    // the touched-row bitmap is an input of the update choice only (k_update_l keeps none; leaving it changes no buffer): choose again,
+    // and drop the step graphs captured with k_update_l
+    const int was = m->kern.update;
+    m->kern = choose_kernels(d, m->n_cu, m->sw, m->defer_on);
+    if (m->kern.update != was)
+        for (hipGraphExec_t* g : {&m->gexec, &m->gexec_small, &m->gexec_head}) if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
     return sync_dm(m);
 }
 
