@@ -10,6 +10,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define G4R_EPS_LOSS 1e-24f    /* gru4rec.py:230,241 */
 #define G4R_EPS_ADAGRAD 1e-6f  /* gru4rec.py:330 */
+#define G4R_OWN_INLINE 15      /* earlier occurrences an owner-table row holds (DevModel::own_pos) */
 
 // Mutation builds for the parity suite's self-test (tests/test_gpu_mutation.py builds them as variant libraries next to the product
 // one and expects the parity tests to turn red): G4R_MUTATE=1 inflates every per-occurrence sparse accumulator increment by
@@ -34,6 +35,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define G4R_MUT_ROW(n, x) ((n) == 0 ? (x) * 1.5f : (x))
 #else
 #define G4R_MUT_ROW(n, x) (x)
+#endif
+#if defined(G4R_MUTATE) && G4R_MUTATE == 8      // test build: the owner scan of the lean update (k_loss_rows' pre-scan, or k_update_l's own
+// scan under G4R_OWNER_SCAN=1) skips the last id of every 1024-slice after the first
+#define G4R_MUT_SLICE_SKIP(j, base0, start) ((base0) > (start) && (j) == (base0) + 1023)
+#else
+#define G4R_MUT_SLICE_SKIP(j, base0, start) false
 #endif
 #if defined(G4R_MUTATE) && G4R_MUTATE == 5      // the 1 / nranks factor of the exact-replica joint update (REDUCE / MEAN forms) x 1.01
 #define G4R_MUT_XSCALE(x) ((x) * 1.01f)
@@ -187,6 +194,11 @@ struct DevModel {
     GP(unsigned) dstat;  // [1024][2] rows / bias entries applied by flush launches, per workgroup id mod 1024 (statistics)
     // narrow layers (g4r_lean_kernels.cuh): dr' = da Wh^T leaves k_gru_da as ceil(D / 16) K-slice partial planes drp[slice][B][D]; k_gru_dy adds them
     GP(float) drp;
+    // owner table of the lean update (k_update_l; the pre-scan in k_loss_rows writes it, g4r_loss_kernel.cuh): [R][16] ints, row k of
+    // the owner of a repeated item = (number of earlier occurrences, their positions in ascending order), -1 when there are more than
+    // G4R_OWN_INLINE of them (k_update_l scans for those).  It sits behind k_update_l's dense-tile table.  Null: no pre-scan
+    // (G4R_OWNER_SCAN=1, or no k_update_l): every owner scans occ_idx itself.
+    GP(int) own_pos;
 };
 // step plane of global step g
 #define G4R_SLOT(m, g) ((size_t)((g) & (long long)(m).defer_mask))

@@ -86,7 +86,12 @@ static int build_lean_args(g4r_model* m) {
         m->h_leanU = u;
         const std::vector<DenseTile> tiles = dense_tiles(d, 16, 64);
         m->ntiles16 = (int)tiles.size();
-        if (dalloc(m, &m->d_tiles16, tiles.size()) || dalloc(m, &m->d_leanU, (size_t)1)) return -1;
+        // behind the tiles, in the same allocation: the owner table ([R][16] ints), so that k_update_l finds it from its arguments at
+        // the first load; k_loss_rows' pre-scan fills it unless G4R_OWNER_SCAN=1
+        const size_t nslot = cdiv((long long)d.R * 16 * sizeof(int), (long long)sizeof(DenseTile));
+        if (dalloc(m, &m->d_tiles16, tiles.size() + nslot) || dalloc(m, &m->d_leanU, (size_t)1)) return -1;
+        d.own_pos = m->sw.owner_scan_in_update ? nullptr : (int*)(m->d_tiles16 + tiles.size());
+        m->h_leanU.own_on = d.own_pos ? 1 : 0;
         HIPCHK(hipMemcpyAsync(m->d_tiles16, tiles.data(), tiles.size() * sizeof(DenseTile), hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipStreamSynchronize(m->stream));      // (before `tiles` goes out of scope)
     }
@@ -98,7 +103,7 @@ static int build_lean_args(g4r_model* m) {
 static KernelSwitches read_switches(const g4r_config& cfg) {
     KernelSwitches w;
     w.no_lean = getenv("G4R_NO_LEAN") != nullptr; w.no_mt = getenv("G4R_NO_MT") != nullptr; w.no_bmt = getenv("G4R_NO_BMT") != nullptr;
-    w.no_merge = getenv("G4R_NO_MERGE") != nullptr;
+    w.no_merge = getenv("G4R_NO_MERGE") != nullptr; w.owner_scan_in_update = env_int("G4R_OWNER_SCAN", 0) != 0;
     w.allow_lean_update = env_int("G4R_LEAN_UPDATE", 1) != 0; w.defer = env_int("G4R_DEFER", cfg.defer_updates) != 0;
     w.p2_geo = env_int("G4R_P2_GEO", -1); w.ba_geo = env_int("G4R_BA_GEO", -1);
     w.wide2 = env_int("G4R_WIDE2", -1); w.p1_ks = env_int("G4R_P1_KS", 128); w.bb_ks = env_int("G4R_BB_KS", 0);

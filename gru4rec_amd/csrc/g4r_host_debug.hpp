@@ -40,6 +40,8 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     else if (s == "dyl") { p = d.dyl[l]; n = bd; }
     else if (s == "Hprev") { p = d.H[l][(m->gstep + 1) & 1]; n = bd; }
     else if (s == "occ_idx") { p = (const float*)d.occ_idx; n = d.R; }
+    // the owner table of the last step (ints, [R][16]): row k valid for the owners of repeated items outside the negatives-only shortcut
+    else if (s == "own_pos") { if (!d.own_pos) return fail("no owner table (k_update_l not chosen, or G4R_OWNER_SCAN=1)"); p = (const float*)d.own_pos; n = 16 * (int64_t)d.R; }
 #if !defined(G4R_CLK_TRACE)
     else if (s == "dbgclk" || s == "dbgtile") return fail("in-kernel traces need a library built with G4R_BUILD_CLK=1 (python -m gru4rec_amd.build --force) and G4R_CLK=1 at run time");
 #endif

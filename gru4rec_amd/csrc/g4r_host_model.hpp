@@ -39,6 +39,7 @@ struct KernelSwitches {
     bool no_mt = false, no_bmt = false;   // G4R_NO_MT / G4R_NO_BMT: the 64 x 64 scoring tiles instead of k_score_mt / k_score_bmt
     bool no_merge = false;                // G4R_NO_MERGE: dense gradients and sparse rows as two launches, never the merged k_update
     bool allow_lean_update = true;        // G4R_LEAN_UPDATE=0: the merged k_update where k_update_l would run, as the deferred mode runs it
+    bool owner_scan_in_update = false;    // G4R_OWNER_SCAN=1: k_update_l's owners of repeated items scan occ_idx themselves (no pre-scan in k_loss_rows)
     bool defer = false;                   // G4R_DEFER (default: g4r_config::defer_updates)
     int p2_geo = -1, ba_geo = -1;         // G4R_P2_GEO / G4R_BA_GEO = 0 / 1: the 4-wave / 8-wave geometry of k_gru_p2 / k_gru_bwd_a (-1: the policy)
     int wide2 = -1, p1_ks = 128, bb_ks = 0;      // G4R_WIDE2 (wide-layer kernel mask, -1: the policy), G4R_P1_KS / G4R_BB_KS (their K slices)

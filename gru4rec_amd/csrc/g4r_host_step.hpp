@@ -114,12 +114,15 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
     end();
     begin(KN_LOSS);
     {
+        // a step that ends in k_update_l: up to one more workgroup per idle CU, the owner pre-scan of its repeated items (g4r_loss_kernel.cuh)
+        const int nown = std::min(cdiv(d.R, LOSS_NW), std::max(2 * m->n_cu - B, 32));
+        const dim3 gloss(B + (merged && k.update == UP_LEAN && d.own_pos ? nown : 0));
 #define G4R_LK_LOSS(L, V)                                                                                                      \
         do {                                                                                                                   \
-            if (k.loss_spec == 1) LK((k_loss_rows<L, 1, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp);      \
-            else if (k.loss_spec == 2) LK((k_loss_rows<L, 2, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp); \
-            else if (k.loss_spec == 3) LK((k_loss_rows<L, 3, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp); \
-            else LK((k_loss_rows<L, 0, V>), dim3(B), dim3(LOSS_T), m->smem_loss, s, dmp, stp);                       \
+            if (k.loss_spec == 1) LK((k_loss_rows<L, 1, V>), gloss, dim3(LOSS_T), m->smem_loss, s, dmp, stp);        \
+            else if (k.loss_spec == 2) LK((k_loss_rows<L, 2, V>), gloss, dim3(LOSS_T), m->smem_loss, s, dmp, stp);   \
+            else if (k.loss_spec == 3) LK((k_loss_rows<L, 3, V>), gloss, dim3(LOSS_T), m->smem_loss, s, dmp, stp);   \
+            else LK((k_loss_rows<L, 0, V>), gloss, dim3(LOSS_T), m->smem_loss, s, dmp, stp);                         \
         } while (0)
         if (k.loss_long) G4R_LK_LOSS(true, 4);      // (rows that long always take four columns per thread)
         else { if (k.loss_quads) G4R_LK_LOSS(false, 4); else G4R_LK_LOSS(false, 1); }

@@ -127,6 +127,7 @@ struct LeanU {
     GP(long long) dbg; GP(long long) dbgtile;
     int n_items, constrained, wE, wY;
     float lr, mom, lmbd, pad;
+    int own_on, pad2;      // 1: the owners of repeated items read their rows of the owner table (DevModel::own_pos), 0: they scan occ_idx
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -860,27 +861,25 @@ __global__ __launch_bounds__(512) void k_score_b(const LeanB* __restrict__ ap, c
 //     row: accumulator / parameter (/ velocity) quads in, Adagrad, quads out.  gru4rec.py:330-334,390-406.
 //   sparse role (one wave per occurrence k of X | Y | samples, eight per workgroup, NO LDS, no barrier): item id and step row with the
 //     first loads; behind the id the item's (last, first, count) entry, parameter row and bias -- one round trip; the wave of the LAST
-//     occurrence owns the row.  Single occurrences (~90 %) finish right there.  An owner of a repeated item finds the earlier
-//     occurrences itself: the id list is 9 KB and L2 resident, so it reads the slice [first, k) with 16-byte loads (up to 1024 ids per
-//     round trip), ballots the matches and adds their step rows in occurrence order, eight rows per round trip -- the arithmetic and the
+//     occurrence owns the row.  Single occurrences (~90 %) finish right there.  An owner of a repeated item takes the positions of the
+//     earlier occurrences from its row of the owner table k_loss_rows' pre-scan wrote (owner_prescan, g4r_loss_kernel.cuh: requested
+//     with the item id), or -- more than G4R_OWN_INLINE of them, or G4R_OWNER_SCAN=1 -- finds them itself: the id list is 9 KB and L2 resident,
+//     so it reads the slice [first, k) with 16-byte loads (up to 1024 ids per round trip) and ballots the matches.  Either way it adds
+//     their step rows in occurrence order, eight rows per round trip -- the arithmetic and the
 //     order of sparse_update_block (gru4rec.py:335-340,407-431: increments accumulate, accumulator and velocity take the last
 //     occurrence's value).  Items whose occurrences are all sampled negatives take the (count - 1) x own row shortcut as there.
-#if defined(G4R_MUTATE) && G4R_MUTATE == 8      // test build: the owner scan skips the last id of every 1024-slice after the first
-#define G4R_MUT_SLICE_SKIP(j, base0, start) ((base0) > (start) && (j) == (base0) + 1023)
-#else
-#define G4R_MUT_SLICE_SKIP(j, base0, start) false
-#endif
 template <bool MOM>
 __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* occ_idx, GAS int* occ_fl, const GAS float* dSx, const GAS float* dSy,
-                                                 const GAS float* dSBy, unsigned k, unsigned R, unsigned B) {
+                                                 const GAS float* dSBy, const GAS int* opos_t, unsigned k, unsigned R, unsigned B) {
     const unsigned lane = threadIdx.x & 63;
     const bool tableE = k < B && !a.constrained;
     const unsigned W = tableE ? (unsigned)a.wE : (unsigned)a.wY, nc4 = W >> 2;
     const unsigned c4 = min(lane, nc4 - 1);
     const bool lok = lane < nc4;
     const unsigned kc = min(k, R - 1);
-    // first loads: the occurrence's item, its step row, its bias step
+    // first loads: the occurrence's item, its row of the owner table (lane l < 16: entry l), its step row, its bias step
     int item = ldu_i(occ_idx, 4 * kc);
+    const int opos = ldu_i(opos_t, 4 * (16 * kc + min(lane, 15u)));
     const GAS float* srow = (kc < B) ? dSx + (size_t)kc * W : dSy + (size_t)(kc - B) * W;
     const float4 sk = ld4(srow + 4 * c4);
     const bool bias = k >= B;
@@ -902,9 +901,18 @@ __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* 
     if (MOM) bvz = a.velBy[ic];
     const bool owner = item >= 0 && fl.x == (int)k + 1;
     if (!owner) return;      // wave-uniform
+    const int n = fl.z;
+    // the last occurrence's accumulator row (repeated items only: a single's accumulator was written in place by the producer of its
+    // step row), requested before the earlier occurrences' rows so that its round trip overlaps theirs
+    float4 ak = make_float4(0.f, 0.f, 0.f, 0.f);
+    float bak = 0.f;
+    if (n > 1) {
+        const GAS float* arow = (k < B) ? a.dAx + (size_t)k * W : a.dAy + (size_t)(k - B) * W;
+        ak = ld4(arow + 4 * c4);
+        if (bias) bak = a.dABy[k - B];
+    }
     if (lane == 0) *(GAS int4*)flp = make_int4(0, 0, 0, 0);      // the entry is taken back for the next step
     const float lr = a.lr, momc = a.mom, lmbd = a.lmbd;
-    const int n = fl.z;
     const int lo = (a.constrained || k < B) ? 0 : (int)B;
     const int first_j = max(lo, (int)R - fl.y);
     float4 S = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -915,6 +923,31 @@ __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* 
             // all occurrences are sampled negatives of this step: their score columns are copies of one another, so are their step rows
             for (int cdup = 1; cdup < n; ++cdup) { S.x += sk.x; S.y += sk.y; S.z += sk.z; S.w += sk.w; Sb += bsk; }
             nb_e = n - 1;
+        } else if (a.own_on && __builtin_amdgcn_readfirstlane(opos) >= 0) {
+            // earlier occurrences from the owner table (ascending positions, k_loss_rows' pre-scan), eight step rows per round trip
+            const int ln = __builtin_amdgcn_readfirstlane(opos);
+            for (int q0 = 0; q0 < ln; q0 += 8) {
+                const int nj = min(8, ln - q0);
+                int js[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) js[q] = __builtin_amdgcn_readlane(opos, 1 + min(q0 + q, ln - 1));      // (slots past nj repeat a valid position)
+                float4 g[8];
+                float gb[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int jj = js[q];
+                    const GAS float* r2 = (jj < (int)B) ? dSx + (size_t)jj * W : dSy + (size_t)(jj - (int)B) * W;
+                    g[q] = ld4(r2 + 4 * c4);
+                    gb[q] = (bias && jj >= (int)B) ? dSBy[jj - (int)B] : 0.f;
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    if (q < nj) {      // wave-uniform
+                        S.x += g[q].x; S.y += g[q].y; S.z += g[q].z; S.w += g[q].w;
+                        if (js[q] >= (int)B) { Sb += gb[q]; ++nb_e; }
+                    }
+                }
+            }
         } else {
             // earlier occurrences in [first_j, k): ids in slices of 1024 (four 16-byte loads per lane), matches in ascending order
             for (int base0 = first_j & ~3; base0 < (int)k; base0 += 1024) {
@@ -989,14 +1022,6 @@ __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* 
         const float tot = (lmbd > 0.f) ? sb + fb * reg : sb;
         if (MOM) { bn = bpz + (fb * (momc * bvz) - tot); bvn = momc * bvz - (bsk + reg); }
         else bn = bpz - tot;
-    }
-    // the last occurrence's accumulator row (repeated items only: a single's accumulator was written in place by the producer of its step row)
-    float4 ak = make_float4(0.f, 0.f, 0.f, 0.f);
-    float bak = 0.f;
-    if (n > 1) {
-        const GAS float* arow = (k < B) ? a.dAx + (size_t)k * W : a.dAy + (size_t)(k - B) * W;
-        ak = ld4(arow + 4 * c4);
-        if (bias) bak = a.dABy[k - B];
     }
     lean_keep(bn); lean_keep(bvn); lean_keep(bak);
     const size_t o = (size_t)item * W + 4 * c4;
@@ -1146,8 +1171,10 @@ __global__ __launch_bounds__(512) void k_update_l(const LeanU* __restrict__ ap, 
     if (b < ntiles) { lean_dense_tile<MOM>(a, tiles_, b, B); LSPAN_END(); return; }
     // occurrences strided over the workgroups (wave w of workgroup q takes k = w nblk + q: the owners of the popular items -- the LAST
     // occurrences, with their duplicate sums -- sit together at the end of the list; contiguous, they would share a few workgroups)
+    // (the owner table sits behind the dense-tile table, in its allocation: its address is in the arguments)
     const unsigned q = b - ntiles, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    lean_rows_update<MOM>(a, (const GAS int*)occ_idx_, (GAS int*)occ_fl_, (const GAS float*)dSx_, (const GAS float*)dSy_, (const GAS float*)dSBy_, wid * nblk + q, R, B);
+    lean_rows_update<MOM>(a, (const GAS int*)occ_idx_, (GAS int*)occ_fl_, (const GAS float*)dSx_, (const GAS float*)dSy_, (const GAS float*)dSBy_,
+                          (const GAS int*)(tiles_ + ntiles), wid * nblk + q, R, B);
     LSPAN_END();
 }
 template __global__ void k_update_l<false>(const LeanU*, const DenseTile*, const int*, int*, const float*, const float*, const float*, unsigned, unsigned, unsigned);

@@ -52,6 +52,66 @@ __device__ __forceinline__ void vst(Ptr p, const float (&o)[V]) {
     else p[0] = o[0];
 }
 
+// Owner pre-scan of the lean update (k_update_l, g4r_lean_kernels.cuh), run by the workgroups of k_loss_rows past the batch rows: launch_step
+// adds min(ceil(R / 16), max(2 CUs - B, 32)) of them when the step ends in k_update_l (one occurrence per wave at the bench shapes; they
+// carry the launch's dynamic LDS, which they do not use, so their count stays bounded at large R).  Nothing here depends on that launch -- occ_idx / occ_fl are complete once
+// k_score_s has ended -- and k_loss_rows leaves most CUs idle (B = 128 workgroups on 256 CUs), so the owners of repeated items find
+// their earlier occurrences here instead of on k_update_l's longest path.  One wave per occurrence k (strided over the workgroups as
+// there: the owners sit together at the end of the list): the item and its (last, first, count) entry; an owner of a repeated item
+// that does not take the all-sampled-negatives shortcut and has at most G4R_OWN_INLINE earlier occurrences reads the ids of [first, k)
+// in slices of 1024 (four 16-byte loads per lane), ballots the matches and writes their positions in ascending order to its own row
+// of the owner table, own_pos[16 k + 1 ..], and their number to own_pos[16 k].  An owner with more (a hot item) writes -1 there and
+// k_update_l scans for it as before.  No counter, no atomic: every owner has a row of its own.  The same slices and the same matches
+// as k_update_l's own scan, which G4R_OWNER_SCAN=1 keeps for every owner.
+__device__ __forceinline__ void owner_prescan(const DevModel& m, unsigned k) {
+    const unsigned lane = threadIdx.x & 63;
+    const unsigned R = (unsigned)m.R, B = (unsigned)m.B;
+    const GAS int* occ_idx = m.occ_idx;
+    int item = occ_idx[min(k, R - 1)];
+    if (k >= R) item = -1;
+    if (item < 0) return;      // wave-uniform
+    const bool constrained = m.embed_mode == G4R_EMBED_CONSTRAINED;
+    const bool tableE = k < B && !constrained;
+    const int4 fl = ldi4(m.occ_fl + 4 * ((tableE ? (size_t)m.n_items : 0) + (unsigned)item));
+    if (fl.x != (int)k + 1 || fl.z < 2) return;      // not the owner, or a single occurrence
+    const int lo = (constrained || k < B) ? 0 : (int)B;
+    const int first_j = max(lo, (int)R - fl.y);
+    if (first_j >= 2 * (int)B) return;      // all occurrences are sampled negatives: k_update_l's (count - 1) x own row shortcut
+    GAS int* pos = m.own_pos + 16 * (size_t)k;
+    if (fl.z - 1 > G4R_OWN_INLINE) {      // a hot item: its owner in k_update_l scans the ids itself
+        if (lane == 0) pos[0] = -1;
+        return;
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int cnt = 0;      // positions written so far (wave-uniform)
+    for (int base0 = first_j & ~3; base0 < (int)k; base0 += 1024) {
+        int4 vv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) vv[u] = ldi4(occ_idx + min(base0 + 256 * u + 4 * (int)lane, (int)((R + 3) & ~3u) - 4));
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j0 = base0 + 256 * u + 4 * (int)lane;
+            const int ids[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+            unsigned long long mk[4];
+            int at = cnt;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                mk[e] = __ballot(ids[e] == item && j0 + e >= first_j && j0 + e < (int)k && !G4R_MUT_SLICE_SKIP(j0 + e, base0, first_j & ~3));
+                at += __popcll(mk[e] & below);      // matches of the lanes below (positions j0' < j0)
+                cnt += __popcll(mk[e]);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if ((mk[e] >> lane) & 1ull) {
+                    if ((unsigned)at < (unsigned)G4R_OWN_INLINE) pos[1 + at] = j0 + e;      // (at most count - 1 matches: bounds only)
+                    ++at;
+                }
+            }
+        }
+    }
+    if (lane == 0) pos[0] = min(cnt, G4R_OWN_INLINE);
+}
+
 // V: columns per thread and loop trip.  V = 1: thread t takes columns t, t + 1024, ... (short rows: every thread has a column);
 // V = 4: columns 4 t .. 4 t + 3, then + 4096 (long rows: the element loops are VALU-issue bound there -- 512 rows x 8704 columns cost
 // ~107 instructions per element in the one-column form, loop control, address arithmetic and predication around 4-byte accesses;
@@ -81,7 +141,16 @@ __global__ __launch_bounds__(LOSS_T) void k_loss_rows(const DevModel* __restrict
     // (measured, round 3: requesting the WHOLE row up front -- 10 scores per thread at B = 512 with 8192 negatives -- does not move
     // the kernel, 17.0 vs 17.1 us; neither do 512- or 256-thread workgroups, 18.7 / 29.5 us: the row is not waiting for its loads)
     constexpr int LOSS_PRE = (V == 4) ? 2 : 4;
+#if defined(G4R_CLK_TRACE)      // (first, last) stamp of workgroups < 1024 -> dbgtile[7168 + workgroup], the top of the span table (tools/clk_lean.py), written at thread 0's exit
+    struct Span { GAS long long* p; __device__ ~Span() { if (p) p[1] = wall_clock64(); } } span_{(m.dbgtile && tid == 0 && i < 1024) ? m.dbgtile + 8 * (size_t)(7168 + i) : nullptr};
+    if (span_.p) span_.p[0] = wall_clock64();
+#endif
     const StepCtx c = load_ctx(st);
+    if (i >= B) {      // (only launched for k_update_l) wave w of pre-scan workgroup q takes occurrences w nown + q, + 16 nown, ...
+        const unsigned nown = gridDim.x - B, R = m.R;
+        for (unsigned k = (threadIdx.x >> 6) * nown + (unsigned)(i - B); k < R; k += LOSS_NW * nown) owner_prescan(m, k);
+        return;
+    }
     float pre_s[LOSS_PRE][V];
 #pragma unroll
     for (int q = 0; q < LOSS_PRE; ++q) vld<V>(pre_s[q], row + min(jt + q * STEP, ldSc - V));

@@ -19,6 +19,7 @@ for rep in range(5):
     else:
         m.train_steps(200 + rep, 1)
     R = 2 * cfg['batch_size'] + cfg['n_sample']
+    NOWN = min((R + 15) // 16, max(2 * int(m.get_debug('n_cu', (1,))[0]) - cfg['batch_size'], 32))      # owner pre-scan workgroups (launch_step)
     raw = m.get_debug('dbgclk', (2 * (64 + 8 * R),)).view(np.int64)
     def show(name, v, idx):
         v = np.asarray(v, dtype=np.int64)
@@ -35,7 +36,7 @@ for rep in range(5):
     ld = (N_ + 15) // 16 * 16
     regions = [('k_gru_v', 1024, 3 * ((D_ + 15) // 16) * ((B_ + 15) // 16)), ('k_gru_h', 1280, ((D_ + 15) // 16) * ((B_ + 15) // 16)),
                ('k_score_s', 4096, ((ld + 31) // 32) * ((B_ + 31) // 32)), ('k_score_b', 2048, ((ld + 15) // 16) * ((D_ + 64) // 64) + ((ld + 127) // 128) * ((B_ + 15) // 16) * ((D_ + 63) // 64)),
-               ('k_update_l', 2700, 6 + 82 + (2 * B_ + cfg['n_sample'] + 7) // 8),
+               ('k_update_l', 2700, 6 + 82 + (2 * B_ + cfg['n_sample'] + 7) // 8), ('k_loss_rows', 7168, B_ + NOWN),
                ('k_gru_da', 1400, ((D_ + 15) // 16) * ((B_ + 15) // 16)), ('k_gru_dy', 1500, ((D_ + 15) // 16) * ((B_ + 15) // 16))]
     t0 = None
     for name, base, n in regions:
@@ -48,6 +49,17 @@ for rep in range(5):
         d = (t[:, 1] - t[:, 0]) / 100.
         print('   %-10s %4d workgroups: first stamp at %+6.2f .. %+6.2f us, last stamp at %+6.2f .. %+6.2f us (after k_gru_v began); own duration median %.2f max %.2f' % (
             name, len(t), (t[:, 0].min() - t0) / 100., (t[:, 0].max() - t0) / 100., (t[:, 1].min() - t0) / 100., (t[:, 1].max() - t0) / 100., np.median(d), d.max()))
+    # k_loss_rows (dbgtile[7168 ..]): the B row workgroups, then the owner pre-scan of k_update_l (if any)
+    tl = tl_all[7168:7168 + B_ + NOWN]
+    ok = tl[:, 1] > 0
+    if ok.any():
+        t0l = tl[ok][:, 0].min()
+        for nm, sl in (('loss rows', slice(0, B_)), ('owner pre-scan', slice(B_, None))):
+            tt = tl[sl]; tt = tt[tt[:, 1] > 0]
+            if len(tt):
+                print('      k_loss_rows %-23s %4d: start %+5.2f .. %+5.2f, end %+5.2f .. %+5.2f us; own duration median %.2f max %.2f' % (
+                    nm, len(tt), (tt[:, 0].min() - t0l) / 100., (tt[:, 0].max() - t0l) / 100., (tt[:, 1].min() - t0l) / 100., (tt[:, 1].max() - t0l) / 100.,
+                    np.median((tt[:, 1] - tt[:, 0]) / 100.), ((tt[:, 1] - tt[:, 0]) / 100.).max()))
     if True:
         nt = 82
         nbk = 1 + (ld + 511) // 512
