@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('G4R_LIB') or os.path.join(_HERE, 'libgru4rec_hip.so')
 G4R_MAX_LAYERS = 8
 G4R_TOPK_MAX = 256      # largest k of g4r_recommend_step
 G4R_EXCLUDE_MAX = 1024  # most distinct items one row of g4r_recommend_step_filtered may exclude
+G4R_CAND_MAX = 2 ** 31 - 256  # most candidate positions of one g4r_score_candidates* call
 LOSS_IDS = {'cross-entropy': 0, 'bpr-max': 1, 'top1-max': 2, 'bpr': 3, 'top1': 4, 'xe_logit': 5}
 ACT_IDS = {'linear': 0, 'relu': 1, 'tanh': 2, 'leaky': 3, 'elu': 4, 'selu': 5, 'softmax': 6, 'softmax_logit': 7}
 ADAPT_IDS = {'adagrad': 0, 'rmsprop': 1, 'adadelta': 2, 'adam': 3, None: 4}
@@ -44,7 +45,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -101,6 +102,8 @@ def lib():
     L.g4r_recommend_step_filtered.argtypes = [vp, i32p, i32, i32p, i64, i32, i64p, i32p, C.POINTER(C.c_uint32), i32p, f32p]
     L.g4r_recommend_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i64p, i32p, C.POINTER(C.c_uint32), i32p,
                                          f32p, C.POINTER(f32p)]
+    L.g4r_score_candidates.argtypes = [vp, i32p, i32, i64p, i32p, i32, f32p, i32p]
+    L.g4r_score_candidates_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i64p, i32p, i32, f32p, i32p, C.POINTER(f32p)]
     L.g4r_rank_targets.argtypes = [vp, i32p, i32, i64, i32, f32p]
     L.g4r_evaluate.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32p, i32, i32,
                                C.POINTER(C.c_double), C.POINTER(C.c_double), i64p]
@@ -440,6 +443,59 @@ class Model:
                                           None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)), _i32(cols),
                                           _f32(scores), None if hout is None else P(*[_f32(h) for h in hout])))
         return (cols, scores, hout) if return_hidden else (cols, scores)
+
+    @staticmethod
+    def _cand_csr(cand_offs, cand_items, rows):
+        offs = np.ascontiguousarray(cand_offs, dtype=np.int64)
+        items = np.ascontiguousarray(cand_items, dtype=np.int32)
+        if len(offs) != rows + 1 or offs[0] < 0 or offs[-1] > len(items):
+            raise ValueError('cand_offs must hold rows + 1 = %d offsets into cand_items' % (rows + 1))
+        return offs, items
+
+    @staticmethod
+    def _cand_out(offs, k):
+        n = len(offs) - 1
+        if k == 0:
+            return np.empty(int(offs[-1] - offs[0]), dtype=np.float32), None
+        return np.empty((n, k), dtype=np.float32), np.empty((n, k), dtype=np.int32)
+
+    def score_candidates(self, in_idx, cand_offs, cand_items, k=0):
+        """Scores of per-row candidate lists (g4r_score_candidates; the hidden state advances as in predict_step): row r's list is
+        cand_items[cand_offs[r]:cand_offs[r + 1]] (item indices).  k = 0: float32 scores in CSR order; k > 0: (pos int32[rows, k],
+        scores float32[rows, k]), pos the positions in the row's list."""
+        ii = np.ascontiguousarray(in_idx, dtype=np.int32)
+        offs, items = self._cand_csr(cand_offs, cand_items, len(ii))
+        scores, pos = self._cand_out(offs, k)
+        _chk(lib().g4r_score_candidates(self.h, _i32(ii), len(ii), _i64(offs), _i32(items), k, _f32(scores),
+                                        None if pos is None else _i32(pos)))
+        return scores if k == 0 else (pos, scores)
+
+    def score_candidates_sessions(self, hist_offs, hist_items, cand_offs, cand_items, k=0, hidden=None, return_hidden=False):
+        """score_candidates after replaying whole session histories, without the prediction state (g4r_score_candidates_sessions):
+        histories and hidden as in recommend_sessions, one candidate list per session.  Returns what score_candidates returns,
+        + the list of hidden states after the last items with return_hidden=True."""
+        ho = np.ascontiguousarray(hist_offs, dtype=np.int64)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32)
+        n = len(ho) - 1
+        if n < 1 or ho[0] < 0 or ho[-1] > len(hi):
+            raise ValueError('hist_offs must hold n + 1 >= 2 offsets into hist_items')
+        offs, items = self._cand_csr(cand_offs, cand_items, n)
+        h0 = None
+        if hidden is not None:
+            if len(hidden) != len(self.layers):
+                raise ValueError('hidden holds %d arrays, one per layer (%d) is needed' % (len(hidden), len(self.layers)))
+            h0 = [np.ascontiguousarray(h, dtype=np.float32) for h in hidden]
+            for l, h in enumerate(h0):
+                if h.shape != (n, self.layers[l]):
+                    raise ValueError('hidden[%d] has shape %s, (%d, %d) is needed' % (l, h.shape, n, self.layers[l]))
+        hout = [np.empty((n, D), dtype=np.float32) for D in self.layers] if return_hidden else None
+        P = C.POINTER(C.c_float) * len(self.layers)
+        scores, pos = self._cand_out(offs, k)
+        _chk(lib().g4r_score_candidates_sessions(self.h, _i64(ho), _i32(hi), n, None if h0 is None else P(*[_f32(h) for h in h0]),
+                                                 _i64(offs), _i32(items), k, _f32(scores), None if pos is None else _i32(pos),
+                                                 None if hout is None else P(*[_f32(h) for h in hout])))
+        out = scores if k == 0 else (pos, scores)
+        return (out, hout) if return_hidden else out
 
     def rank_targets(self, target_col, col_begin=0, mode='standard'):
         t = np.ascontiguousarray(target_col, dtype=np.int32)

@@ -154,6 +154,16 @@ struct g4r_model {
     int *r_in = nullptr, *r_perm = nullptr, *r_len = nullptr;
     float* r_scores = nullptr;
     int64_t r_in_cap = 0, r_scores_cap = 0;
+    // per-row candidate scoring (g4r_score_candidates*): one call's (or chunk's) CSR -- row offsets, candidate item indices, scores
+    // in CSR order -- the work items of k_score_cand, the top-k lists of k_cand_pack and the selected (position, score) pairs
+    long long* c_offs = nullptr;
+    int* c_items = nullptr;
+    float* c_scores = nullptr;
+    int4* c_work = nullptr;
+    uint2* c_topk = nullptr;
+    int* c_tpos = nullptr;
+    float* c_tscores = nullptr;
+    int64_t c_offs_cap = 0, c_items_cap = 0, c_scores_cap = 0, c_work_cap = 0, c_topk_cap = 0, c_tpos_cap = 0, c_tscores_cap = 0;
     unsigned tie_ctr = 0;                       // evaluation step counter of the 'tiebreaking' noise stream
     // rccl
     ncclComm_t comm = nullptr;

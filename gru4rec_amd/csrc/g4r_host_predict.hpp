@@ -446,64 +446,43 @@ static int replay_reserve(g4r_model* m, int rows, int64_t n_in) {
     return 0;
 }
 
-int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
-                           const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs, const int32_t* excl_items,
-                           const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, float* const* out_hidden) {
-    // ---- every check before any device work (nothing here has state to advance, but a refused call launches nothing)
-    if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores)) return -1;
+// the history / hidden-state checks of g4r_recommend_sessions / g4r_score_candidates_sessions
+static int replay_check(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                        float* const* out_hidden) {
     if (!hist_offs || !hist_items) return fail("null argument");
     if (n < 1) return fail("n must be positive");
-    HIPCHK(hipSetDevice(m->cfg.device));
     const DevModel& d = m->dm;
-    const int L = d.n_layers;
     if (hist_offs[0] < 0) return fail("hist_offs[0] is negative");
     for (int i = 0; i < n; ++i)
         if (hist_offs[i + 1] <= hist_offs[i]) return fail("history " + std::to_string(i) + " is empty (hist_offs must rise strictly)");
     for (int64_t j = hist_offs[0]; j < hist_offs[n]; ++j)
         if (hist_items[j] < 0 || hist_items[j] >= d.n_items) return fail("history item index out of range");
-    if (!item_idx) n_sel = d.n_items;
-    for (int64_t p = 0; item_idx && p < n_sel; ++p)
-        if (item_idx[p] < 0 || item_idx[p] >= d.n_items) return fail("item index out of range");
-    for (int l = 0; l < L; ++l) {
+    for (int l = 0; l < d.n_layers; ++l) {
         if (h0 && !h0[l]) return fail("null argument (h0[" + std::to_string(l) + "])");
         if (out_hidden && !out_hidden[l]) return fail("null argument (out_hidden[" + std::to_string(l) + "])");
     }
-    std::vector<long long> xoffs;
-    std::vector<int32_t> xitems;
-    if ((excl_offs || excl_mask) && excl_pack(m, n, item_idx, n_sel, k, excl_offs, excl_items, excl_mask, xoffs, xitems)) return -1;
-    const bool excl = excl_offs || excl_mask;
-    // ---- buffers and the call-wide uploads
+    return 0;
+}
+
+// rows per chunk of a replay of n sessions
+static int replay_chunk_rows(int32_t n) {
     const int env_c = env_int("G4R_SESSIONS_CHUNK", 0);
-    const int C = std::min<int>(n, env_c > 0 ? std::min(env_c, G4R_REPLAY_CHUNK) : G4R_REPLAY_CHUNK);
-    const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
-    const int64_t ldo = (n_sel + 3) & ~3LL;
-    if (sm && (int64_t)C * ldo > m->r_scores_cap) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(m, m->r_scores);
-        m->r_scores = nullptr;
-        m->r_scores_cap = 0;
-        if (dalloc(m, &m->r_scores, (size_t)C * ldo, false)) return -1;
-        m->r_scores_cap = (int64_t)C * ldo;
-    }
-    if (item_idx) {
-        if (n_sel > m->p_items_cap) {
-            HIPCHK(hipStreamSynchronize(m->stream));
-            dfree(m, m->p_items);
-            m->p_items = nullptr;
-            m->p_items_cap = 0;
-            if (dalloc(m, &m->p_items, (size_t)n_sel, false)) return -1;
-            m->p_items_cap = n_sel;
-        }
-        HIPCHK(hipMemcpyAsync(m->p_items, item_idx, n_sel * sizeof(int), hipMemcpyHostToDevice, m->stream));
-    }
-    const int* d_items = item_idx ? (const int*)m->p_items : (const int*)nullptr;
+    return std::min<int>(n, env_c > 0 ? std::min(env_c, G4R_REPLAY_CHUNK) : G4R_REPLAY_CHUNK);
+}
+
+// The checked histories replayed chunk by chunk (C rows per chunk, replay_chunk_rows).  Per chunk: the rows are sorted by history
+// length and stepped on the replay buffers; score(c0, Cc, perm, hsrc) enqueues what the caller computes from the top layer's output
+// hsrc (sorted row r is session c0 + perm[r]); the final states go to out_hidden (NULL: not wanted); the stream is synchronised once
+// and done(c0, Cc, perm) runs on the host.  Shared by g4r_recommend_sessions and g4r_score_candidates_sessions.
+extern "C++" {      // (this file is included inside extern "C")
+template <class S, class F>
+static int replay_chunks(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, int C, const float* const* h0,
+                         float* const* out_hidden, S score, F done) {
+    const DevModel& d = m->dm;
+    const int L = d.n_layers;
     const GruBufs rb = replay_bufs(m);
     std::vector<int> perm, len;
-    std::vector<int32_t> steps, tcols((size_t)C * k);
-    std::vector<float> tscores((size_t)C * k);
-    std::vector<long long> coffs;
-    std::vector<int32_t> citems;
-    // ---- chunk by chunk: enqueue the replay of every step and the selection, then synchronise once
+    std::vector<int32_t> steps;
     for (int c0 = 0; c0 < n; c0 += C) {
         const int Cc = std::min(C, n - c0);
         // rows sorted by history length, descending (stable): step t runs on the prefix of rows still active
@@ -536,7 +515,68 @@ int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t
             while (Mt > 0 && len[Mt - 1] <= t) --Mt;
             gru_step(m, rb, t & 1, (const int*)m->r_in + (size_t)t * Cc, Mt);
         }
-        const float* hsrc = (const float*)m->rhout[L - 1];
+        if (score(c0, Cc, (const std::vector<int>&)perm, (const float*)m->rhout[L - 1])) return -1;
+        if (out_hidden)
+            for (int l = 0; l < L; ++l) {
+                hipLaunchKernelGGL(k_replay_final, dim3(cdiv((long long)Cc * d.D[l], 256)), dim3(256), 0, m->stream, m->rio[l],
+                                   (const float*)m->rH[l][0], (const float*)m->rH[l][1], (const int*)m->r_perm, (const int*)m->r_len,
+                                   Cc, d.D[l], T);
+                HIPCHK(hipMemcpyAsync(out_hidden[l] + (size_t)c0 * d.D[l], m->rio[l], (size_t)Cc * d.D[l] * sizeof(float),
+                                      hipMemcpyDeviceToHost, m->stream));
+            }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(m->stream));
+        done(c0, Cc, (const std::vector<int>&)perm);
+    }
+    return 0;
+}
+}  // extern "C++"
+
+int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                           const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs, const int32_t* excl_items,
+                           const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, float* const* out_hidden) {
+    // ---- every check before any device work (nothing here has state to advance, but a refused call launches nothing)
+    if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores)) return -1;
+    HIPCHK(hipSetDevice(m->cfg.device));
+    if (replay_check(m, hist_offs, hist_items, n, h0, out_hidden)) return -1;
+    const DevModel& d = m->dm;
+    if (!item_idx) n_sel = d.n_items;
+    for (int64_t p = 0; item_idx && p < n_sel; ++p)
+        if (item_idx[p] < 0 || item_idx[p] >= d.n_items) return fail("item index out of range");
+    std::vector<long long> xoffs;
+    std::vector<int32_t> xitems;
+    if ((excl_offs || excl_mask) && excl_pack(m, n, item_idx, n_sel, k, excl_offs, excl_items, excl_mask, xoffs, xitems)) return -1;
+    const bool excl = excl_offs || excl_mask;
+    // ---- buffers and the call-wide uploads
+    const int C = replay_chunk_rows(n);
+    const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
+    const int64_t ldo = (n_sel + 3) & ~3LL;
+    if (sm && (int64_t)C * ldo > m->r_scores_cap) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        dfree(m, m->r_scores);
+        m->r_scores = nullptr;
+        m->r_scores_cap = 0;
+        if (dalloc(m, &m->r_scores, (size_t)C * ldo, false)) return -1;
+        m->r_scores_cap = (int64_t)C * ldo;
+    }
+    if (item_idx) {
+        if (n_sel > m->p_items_cap) {
+            HIPCHK(hipStreamSynchronize(m->stream));
+            dfree(m, m->p_items);
+            m->p_items = nullptr;
+            m->p_items_cap = 0;
+            if (dalloc(m, &m->p_items, (size_t)n_sel, false)) return -1;
+            m->p_items_cap = n_sel;
+        }
+        HIPCHK(hipMemcpyAsync(m->p_items, item_idx, n_sel * sizeof(int), hipMemcpyHostToDevice, m->stream));
+    }
+    const int* d_items = item_idx ? (const int*)m->p_items : (const int*)nullptr;
+    std::vector<int32_t> tcols((size_t)C * k);
+    std::vector<float> tscores((size_t)C * k);
+    std::vector<long long> coffs;
+    std::vector<int32_t> citems;
+    // ---- chunk by chunk: the replay, then the selection; one synchronisation per chunk
+    auto score = [&](int c0, int Cc, const std::vector<int>& perm, const float* hsrc) -> int {
         if (sm) score_rows(m, hsrc, Cc, d_items, n_sel, m->r_scores, ldo);
         TkExcl ex;
         if (excl) {
@@ -554,23 +594,154 @@ int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t
         if (topk_select(m, hsrc, Cc, d_items, n_sel, k, excl ? &ex : nullptr, (const float*)m->r_scores, ldo)) return -1;
         HIPCHK(hipMemcpyAsync(tcols.data(), m->p_tcols, (size_t)Cc * k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
         HIPCHK(hipMemcpyAsync(tscores.data(), m->p_tscores, (size_t)Cc * k * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-        if (out_hidden)
-            for (int l = 0; l < L; ++l) {
-                hipLaunchKernelGGL(k_replay_final, dim3(cdiv((long long)Cc * d.D[l], 256)), dim3(256), 0, m->stream, m->rio[l],
-                                   (const float*)m->rH[l][0], (const float*)m->rH[l][1], (const int*)m->r_perm, (const int*)m->r_len,
-                                   Cc, d.D[l], T);
-                HIPCHK(hipMemcpyAsync(out_hidden[l] + (size_t)c0 * d.D[l], m->rio[l], (size_t)Cc * d.D[l] * sizeof(float),
-                                      hipMemcpyDeviceToHost, m->stream));
-            }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(m->stream));
-        // sorted row r is session c0 + perm[r]
+        return 0;
+    };
+    // sorted row r is session c0 + perm[r]
+    auto done = [&](int c0, int Cc, const std::vector<int>& perm) {
         for (int r = 0; r < Cc; ++r) {
             memcpy(out_cols + (size_t)(c0 + perm[r]) * k, tcols.data() + (size_t)r * k, (size_t)k * sizeof(int32_t));
             memcpy(out_scores + (size_t)(c0 + perm[r]) * k, tscores.data() + (size_t)r * k, (size_t)k * sizeof(float));
         }
-    }
+    };
+    return replay_chunks(m, hist_offs, hist_items, n, C, h0, out_hidden, score, done);
+}
+
+// ------------------------------------------------------------------------------------------------ per-row candidate lists
+// grow-only device buffer of one candidate call (stream-ordered: the stream is drained before the old one is freed)
+extern "C++" {
+template <class T>
+static int cand_reserve(g4r_model* m, T** p, int64_t* cap, int64_t need) {
+    if (need <= *cap) return 0;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    dfree(m, *p);
+    *p = nullptr;
+    *cap = 0;
+    if (dalloc(m, p, (size_t)need, false)) return -1;
+    *cap = need;
     return 0;
+}
+}  // extern "C++"
+
+// the checks of the candidate lists of g4r_score_candidates*: rows >= 1 non-empty lists, items in range, at most G4R_CAND_MAX
+// positions in all, 0 <= k <= G4R_TOPK_MAX and every list at least k long when k > 0
+static int cand_check(g4r_model* m, int32_t rows, const int64_t* cand_offs, const int32_t* cand_items, int32_t k, float* out_scores,
+                      int32_t* out_pos) {
+    if (!m || !cand_offs || !cand_items || !out_scores) return fail("null argument");
+    if (rows < 1) return fail("the number of rows must be positive");
+    if (k < 0 || k > G4R_TOPK_MAX) return fail("k must be in [0, " + std::to_string(G4R_TOPK_MAX) + "]");
+    if (k > 0 && !out_pos) return fail("null argument (out_pos)");
+    if (cand_offs[0] < 0) return fail("cand_offs[0] is negative");
+    for (int r = 0; r < rows; ++r) {
+        const int64_t n = cand_offs[r + 1] - cand_offs[r];
+        if (n < 1) return fail("candidate list " + std::to_string(r) + " is empty (cand_offs must rise strictly)");
+        if (n < k) return fail("candidate list " + std::to_string(r) + " holds " + std::to_string(n) + " positions, fewer than k = " + std::to_string(k));
+        if (cand_offs[r + 1] - cand_offs[0] > G4R_CAND_MAX)
+            return fail("more than G4R_CAND_MAX = " + std::to_string((long long)G4R_CAND_MAX) + " candidate positions in one call");
+    }
+    const int64_t I = m->dm.n_items;
+    for (int64_t p = cand_offs[0]; p < cand_offs[rows]; ++p)
+        if (cand_items[p] < 0 || cand_items[p] >= I) return fail("candidate item index out of range");
+    return 0;
+}
+
+// host staging of one candidate call (kept until the stream has been synchronised)
+struct CandHost { std::vector<long long> offs; std::vector<int4> work; };
+
+// Enqueues the scoring of `rows` checked candidate lists against rows of hsrc (the top layer's output): list r (the items
+// items[offs[r] .. offs[r + 1]), absolute indices) is scored against hsrc row hrow[r] (hrow NULL: row r).  k == 0: the scores in CSR
+// order -> out_scores[offs[rows] - offs[0]]; k > 0: row r's k best (position in its list, score) -> out_pos / out_scores[r * k ..].
+// The copies to the host are enqueued; the caller synchronises.
+static int cand_enqueue(g4r_model* m, const float* hsrc, int32_t rows, const int* hrow, const int64_t* offs, const int32_t* items,
+                        int32_t k, float* out_scores, int32_t* out_pos, CandHost& hs) {
+    const DevModel& d = m->dm;
+    const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
+    const int64_t base = offs[0], P = offs[rows] - base;
+    // work items (h row, first position, end position, the row's first position): slices of at most CS_SLICE positions
+    hs.offs.resize((size_t)rows + 1);
+    hs.work.clear();
+    for (int r = 0; r <= rows; ++r) hs.offs[r] = offs[r] - base;
+    for (int r = 0; r < rows; ++r)
+        for (long long p = hs.offs[r]; p < hs.offs[r + 1]; p += CS_SLICE)
+            hs.work.push_back(make_int4(hrow ? hrow[r] : r, (int)p, (int)std::min<long long>(p + CS_SLICE, hs.offs[r + 1]), (int)hs.offs[r]));
+    // top-k: groups of consecutive rows whose lists (nl * k entries per row, nl = ceil(the group's longest / k)) fit in CS_TOPK_ENTRIES
+    // together (a longer single row gets a buffer of its own size); one k_cand_pack + k_topk_merge pair per group
+    std::vector<int4> groups;      // (first row, rows, nl, -)
+    int64_t topk_need = 0;
+    if (k > 0) {
+        for (int r0 = 0; r0 < rows;) {
+            int64_t mx = 0;
+            int r1 = r0;
+            while (r1 < rows && r1 - r0 < 65535) {
+                const int64_t nm = std::max<int64_t>(mx, hs.offs[r1 + 1] - hs.offs[r1]);
+                if (r1 > r0 && (int64_t)(r1 - r0 + 1) * ((nm + k - 1) / k) * k > CS_TOPK_ENTRIES) break;
+                mx = nm;
+                ++r1;
+            }
+            const int nl = (int)((mx + k - 1) / k);
+            groups.push_back(make_int4(r0, r1 - r0, nl, 0));
+            topk_need = std::max<int64_t>(topk_need, (int64_t)(r1 - r0) * nl * k);
+            r0 = r1;
+        }
+    }
+    if (cand_reserve(m, &m->c_offs, &m->c_offs_cap, (int64_t)rows + 1) || cand_reserve(m, &m->c_items, &m->c_items_cap, P) ||
+        cand_reserve(m, &m->c_scores, &m->c_scores_cap, P) || cand_reserve(m, &m->c_work, &m->c_work_cap, (int64_t)hs.work.size()) ||
+        (k > 0 && (cand_reserve(m, &m->c_topk, &m->c_topk_cap, topk_need) || cand_reserve(m, &m->c_tpos, &m->c_tpos_cap, (int64_t)rows * k) ||
+                   cand_reserve(m, &m->c_tscores, &m->c_tscores_cap, (int64_t)rows * k))))
+        return -1;
+    HIPCHK(hipMemcpyAsync(m->c_offs, hs.offs.data(), hs.offs.size() * sizeof(long long), hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(m->c_items, items + base, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(m->c_work, hs.work.data(), hs.work.size() * sizeof(int4), hipMemcpyHostToDevice, m->stream));
+    // softmax needs the row's raw scores first: stored without the activation, then normalised over the row's own list
+    hipLaunchKernelGGL(k_score_cand, dim3((unsigned)hs.work.size()), dim3(256), 0, m->stream, (const DevModel*)m->d_dm, hsrc,
+                       (const int*)m->c_items, (const int4*)m->c_work, m->c_scores, sm ? 0 : 1);
+    if (sm) hipLaunchKernelGGL(k_softmax_csr, dim3(rows), dim3(256), 0, m->stream, m->c_scores, (const long long*)m->c_offs);
+    if (k == 0) {
+        HIPCHK(hipMemcpyAsync(out_scores, m->c_scores, (size_t)P * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    } else {
+        for (const int4& g : groups) {
+            const int L = g.z * k;
+            hipLaunchKernelGGL(k_cand_pack, dim3(cdiv(L, 256), g.y), dim3(256), 0, m->stream, (const float*)m->c_scores,
+                               (const long long*)m->c_offs + g.x, L, m->c_topk);
+            hipLaunchKernelGGL(k_topk_merge, dim3(g.y), dim3(256), 0, m->stream, (const uint2*)m->c_topk, g.z, (int)k,
+                               m->c_tpos + (size_t)g.x * k, m->c_tscores + (size_t)g.x * k);
+        }
+        HIPCHK(hipMemcpyAsync(out_pos, m->c_tpos, (size_t)rows * k * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(out_scores, m->c_tscores, (size_t)rows * k * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int g4r_score_candidates(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int64_t* cand_offs, const int32_t* cand_items,
+                         int32_t k, float* out_scores, int32_t* out_pos) {
+    // every check before the state advances: the lists here, the input items and mrows in predict_inputs (which only uploads)
+    if (cand_check(m, mrows, cand_offs, cand_items, k, out_scores, out_pos)) return -1;
+    int64_t n_sel = 0;
+    if (predict_inputs(m, in_idx, mrows, nullptr, &n_sel)) return -1;
+    predict_gru(m, m->p_in, mrows);
+    CandHost hs;
+    if (cand_enqueue(m, (const float*)m->phout[m->dm.n_layers - 1], mrows, nullptr, cand_offs, cand_items, k, out_scores, out_pos, hs)) return -1;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return 0;
+}
+
+int g4r_score_candidates_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                                  const int64_t* cand_offs, const int32_t* cand_items, int32_t k, float* out_scores, int32_t* out_pos,
+                                  float* const* out_hidden) {
+    if (cand_check(m, n, cand_offs, cand_items, k, out_scores, out_pos)) return -1;
+    HIPCHK(hipSetDevice(m->cfg.device));
+    if (replay_check(m, hist_offs, hist_items, n, h0, out_hidden)) return -1;
+    CandHost hs;
+    std::vector<int> hrow;
+    // chunk rows are in session order (their lists are one contiguous stretch of the CSR, their results land in place); session
+    // c0 + i's hidden row is the sorted row r with perm[r] = i
+    auto score = [&](int c0, int Cc, const std::vector<int>& perm, const float* hsrc) -> int {
+        hrow.resize(Cc);
+        for (int r = 0; r < Cc; ++r) hrow[perm[r]] = r;
+        float* dst = k ? out_scores + (size_t)c0 * k : out_scores + (cand_offs[c0] - cand_offs[0]);
+        return cand_enqueue(m, hsrc, Cc, hrow.data(), cand_offs + c0, cand_items, k, dst, k ? out_pos + (size_t)c0 * k : nullptr, hs);
+    };
+    return replay_chunks(m, hist_offs, hist_items, n, replay_chunk_rows(n), h0, out_hidden, score, [](int, int, const std::vector<int>&) {});
 }
 
 int g4r_evaluate(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, const uint8_t* reset, const int32_t* M, int64_t T,

@@ -914,6 +914,30 @@ class GRU4Rec:
         cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
         return cand[cols], scores
 
+    def _session_inputs(self, histories, hidden):
+        """Checks and packs the histories and the initial hidden state of a stateless call (recommend_sessions,
+        score_candidates_sessions): (N, lengths, offsets int64[N + 1], item indices int32, per-layer padded states or None)."""
+        hist = [np.ravel(h) if isinstance(h, np.ndarray) else list(h) for h in histories]
+        N = len(hist)
+        if N < 1:
+            raise ValueError('histories is empty: at least one session is needed')
+        lens = np.array([len(h) for h in hist], dtype=np.int64)
+        if (lens == 0).any():
+            raise ValueError('history %d is empty' % np.flatnonzero(lens == 0)[0])
+        hidx = self.itemidmap[np.concatenate(hist)].values.astype(np.int32)
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        h0 = None
+        if hidden is not None:
+            if not isinstance(hidden, (list, tuple)) or len(hidden) != len(self.layers):
+                raise ValueError('hidden must be a list of %d arrays, one per layer' % len(self.layers))
+            h0 = []
+            for l, (h, D) in enumerate(zip(hidden, self.layers)):
+                if not isinstance(h, np.ndarray) or h.dtype != np.float32 or h.shape != (N, D):
+                    raise ValueError('hidden[%d] must be a float32 array of shape (%d, %d), not %s %s' % (
+                        l, N, D, getattr(h, 'dtype', type(h).__name__), getattr(h, 'shape', '')))
+                h0.append(_pad_cols(h, 1, D, _pad4(D)))
+        return N, lens, offs, hidx, h0
+
     def recommend_sessions(self, histories, k=20, predict_for_item_ids=None, exclude_history=False, exclude=None, exclude_per_row=None,
                            hidden=None, return_hidden=False):
         """Top-k next items of N whole sessions in one stateless call: (item_ids[N, k], scores[N, k] float32), plus the new hidden
@@ -939,25 +963,7 @@ class GRU4Rec:
         n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
         if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
             raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
-        hist = [np.ravel(h) if isinstance(h, np.ndarray) else list(h) for h in histories]
-        N = len(hist)
-        if N < 1:
-            raise ValueError('histories is empty: at least one session is needed')
-        lens = np.array([len(h) for h in hist], dtype=np.int64)
-        if (lens == 0).any():
-            raise ValueError('history %d is empty' % np.flatnonzero(lens == 0)[0])
-        hidx = self.itemidmap[np.concatenate(hist)].values.astype(np.int32)
-        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        h0 = None
-        if hidden is not None:
-            if not isinstance(hidden, (list, tuple)) or len(hidden) != len(self.layers):
-                raise ValueError('hidden must be a list of %d arrays, one per layer' % len(self.layers))
-            h0 = []
-            for l, (h, D) in enumerate(zip(hidden, self.layers)):
-                if not isinstance(h, np.ndarray) or h.dtype != np.float32 or h.shape != (N, D):
-                    raise ValueError('hidden[%d] must be a float32 array of shape (%d, %d), not %s %s' % (
-                        l, N, D, getattr(h, 'dtype', type(h).__name__), getattr(h, 'shape', '')))
-                h0.append(_pad_cols(h, 1, D, _pad4(D)))
+        N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
         iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
         xoffs = xitems = mask = None
         if exclude_history or exclude is not None or exclude_per_row is not None:
@@ -969,6 +975,101 @@ class GRU4Rec:
         if not return_hidden:
             return cand[out[0]], out[1]
         return cand[out[0]], out[1], [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(out[2], self.layers)]
+
+    # ------------------------------------------------------------------ per-row candidate lists (not in the reference)
+    def _candidate_csr(self, candidates, rows, k):
+        """Checks and packs the `candidates` argument of score_candidates*: (offsets int64[rows + 1], item indices int32, the
+        candidate ids in CSR order, C for a 2-D array / None for ragged lists, k or 0).  Raises before anything changes."""
+        if isinstance(candidates, np.ndarray) and candidates.ndim == 2:
+            if candidates.shape[0] != rows:
+                raise ValueError('candidates has %d rows, one per row (%d) is needed' % (candidates.shape[0], rows))
+            width = candidates.shape[1]
+            if width < 1:
+                raise ValueError('candidate list 0 is empty')
+            flat = candidates.ravel()
+            lens = np.full(rows, width, dtype=np.int64)
+        else:
+            if isinstance(candidates, (str, bytes)) or not hasattr(candidates, '__len__'):
+                raise ValueError('candidates must be a 2-D array or a list of sequences of item ids')
+            lists = [np.ravel(x) if isinstance(x, np.ndarray) else list(x) for x in candidates]
+            if len(lists) != rows:
+                raise ValueError('candidates holds %d lists, one per row (%d) is needed' % (len(lists), rows))
+            lens = np.array([len(x) for x in lists], dtype=np.int64)
+            if (lens == 0).any():
+                raise ValueError('candidate list %d is empty' % np.flatnonzero(lens == 0)[0])
+            flat = np.concatenate([np.asarray(x) for x in lists])
+            width = None
+        if lens.sum() > _native.G4R_CAND_MAX:
+            raise ValueError('%d candidate positions in one call: at most G4R_CAND_MAX = %d' % (lens.sum(), _native.G4R_CAND_MAX))
+        if k is not None:
+            if isinstance(k, bool) or int(k) != k or not 1 <= k <= _native.G4R_TOPK_MAX:
+                raise ValueError('k = %r: it must be None or an integer in [1, %d]' % (k, _native.G4R_TOPK_MAX))
+            short = np.flatnonzero(lens < k)
+            if len(short):
+                raise ValueError('candidate list %d holds %d positions, fewer than k = %d' % (short[0], lens[short[0]], k))
+        cidx = self.itemidmap[flat].values.astype(np.int32)
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        return offs, cidx, flat, width, 0 if k is None else int(k)
+
+    @staticmethod
+    def _candidate_result(out, offs, flat, width, k):
+        if k == 0:
+            return out.reshape(-1, width) if width is not None else [out[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
+        pos, scores = out
+        return flat[offs[:-1, None] + pos], scores
+
+    def score_candidates(self, session_ids, input_item_ids, candidates, k=None, batch=100):
+        """Scores of every session's OWN candidate list (the re-ranking stage behind a retrieval stage).  Not in the reference.
+
+          candidates  one list per row: a 2-D array [n, C] of item ids, or n non-empty sequences of item ids (lengths may differ).
+                      Duplicates are allowed; every position is scored.
+          k=None      the scores in the caller's order: float32 [n, C] for a 2-D array, else a list of n float32 arrays (views into
+                      one CSR buffer).
+          k           (item_ids[n, k], scores[n, k]): the k best of each row's own list in the recommend_next_batch order (score
+                      descending, equal scores by the lower position in the list, NaN last); 1 <= k <= G4R_TOPK_MAX and every list
+                      holds at least k positions.
+
+        Row i is bit for bit what the existing calls return with predict_for_item_ids = candidates[i]: column i of
+        predict_next_batch for k=None, row i of recommend_next_batch for k.  So softmax / softmax_logit normalise over the row's own
+        list; with an element-wise final activation a score equals the full-catalogue predict_next_batch score of that item.  The
+        prediction state advances as in predict_next_batch (changed sessions zeroed, the seen-history recorded), so calls may be
+        interleaved with predict_next_batch / recommend_next_batch.  Not supported, as the caller controls each list: exclusions
+        (exclude_seen, exclude, exclude_per_row) and predict_for_item_ids.  Everything is checked before the state changes: an
+        unknown item id raises KeyError; an empty list, a wrong number of lists, a bad k or more than G4R_CAND_MAX positions in all
+        raise ValueError."""
+        if self.error_during_train:
+            raise Exception
+        plan = self._predict_plan(session_ids, input_item_ids, batch)
+        n = len(np.ravel(plan[3]))
+        if not 1 <= n <= batch:
+            raise ValueError('%d input items: between 1 and batch = %d are needed' % (n, batch))
+        offs, cidx, flat, width, kk = self._candidate_csr(candidates, n, k)
+        m, in_idxs = self._predict_rows(session_ids, input_item_ids, batch, plan=plan)
+        out = m.score_candidates(in_idxs, offs, cidx, kk)
+        return self._candidate_result(out, offs, flat, width, kk)
+
+    def score_candidates_sessions(self, histories, candidates, k=None, hidden=None, return_hidden=False):
+        """score_candidates for N whole sessions in one stateless call.  Not in the reference.
+
+          histories, hidden, return_hidden   as in recommend_sessions (any N, replayed on the device in chunks; the prediction state
+                                             is neither read nor changed).
+          candidates, k                      as in score_candidates, one list per history.
+        Returns what score_candidates returns; with return_hidden=True the list of hidden states is appended (k=None: (scores,
+        hidden); k: (item_ids, scores, hidden)).  Row i equals, bit for bit, the stepwise route of recommend_sessions: the first
+        T - 1 items through predict_next_batch from a fresh state, the last through score_candidates.  Not supported: exclusions and
+        predict_for_item_ids.  Everything is checked before any device work (KeyError for an unknown item id, ValueError for an
+        empty history or list, a wrong number of lists, a bad k, a bad hidden or more than G4R_CAND_MAX positions)."""
+        if self.error_during_train:
+            raise Exception
+        N, _, hoffs, hidx, h0 = self._session_inputs(histories, hidden)
+        offs, cidx, flat, width, kk = self._candidate_csr(candidates, N, k)
+        m = self._ensure_model()
+        out = m.score_candidates_sessions(hoffs, hidx, offs, cidx, kk, hidden=h0, return_hidden=return_hidden)
+        if not return_hidden:
+            return self._candidate_result(out, offs, flat, width, kk)
+        res = self._candidate_result(out[0], offs, flat, width, kk)
+        H = [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(out[1], self.layers)]
+        return (res, H) if kk == 0 else (res[0], res[1], H)
 
     def symbolic_predict(self, X, Y, M, items, batch_size):
         raise NotImplementedError('symbolic_predict builds a Theano graph (gru4rec.py:729-741); the MI355X path '

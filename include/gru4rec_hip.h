@@ -202,6 +202,23 @@ int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t
                            const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs, const int32_t* excl_items,
                            const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, float* const* out_hidden);
 
+/* not in the reference: scores of per-row candidate lists (the re-ranking stage behind a retrieval stage).  Row r's list is the
+ * item indices cand_items[cand_offs[r] .. cand_offs[r + 1]) (at least one; cand_offs rises strictly; duplicates allowed, every
+ * position is scored), at most G4R_CAND_MAX positions in all.  g4r_score_candidates advances the prediction state exactly as
+ * g4r_predict_step does (in_idx / mrows as there).  k == 0: out_scores[cand_offs[mrows] - cand_offs[0]] receives the scores in CSR
+ * order, row r's bit for bit those g4r_predict_step returns with item_idx = row r's list (softmax / softmax_logit normalise over the
+ * row's own list); out_pos may be NULL.  1 <= k <= G4R_TOPK_MAX (every list at least k long): out_pos / out_scores[mrows * k]
+ * receive row r's k best (position in its list, score), what g4r_recommend_step returns for that list, bit for bit.  Everything is
+ * checked before the state advances. */
+#define G4R_CAND_MAX 2147483392LL      /* 2^31 - 256 */
+int g4r_score_candidates(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int64_t* cand_offs, const int32_t* cand_items,
+                         int32_t k, float* out_scores, int32_t* out_pos);
+/* The same for n whole session histories, stateless: hist_offs / hist_items / h0 / h_out as in g4r_recommend_sessions (same chunks,
+ * same replay), cand_offs[n + 1] / cand_items / k / out_scores / out_pos as in g4r_score_candidates with one list per session. */
+int g4r_score_candidates_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                                  const int64_t* cand_offs, const int32_t* cand_items, int32_t k, float* out_scores, int32_t* out_pos,
+                                  float* const* h_out);
+
 /* The whole of evaluation.evaluate_gpu (evaluation.py:86-147) as ONE call with no host round trip per step: the
  * session-parallel test loop comes as a plan (g4r_build_plan on the test sessions in id order with n_sample = 1: the loop of
  * evaluation.py:96-139 is the loop of fit), every step runs the GRU forward, scores all items (items == NULL) or
