@@ -104,6 +104,7 @@ static KernelSwitches read_switches(const g4r_config& cfg) {
     KernelSwitches w;
     w.no_lean = getenv("G4R_NO_LEAN") != nullptr; w.no_mt = getenv("G4R_NO_MT") != nullptr; w.no_bmt = getenv("G4R_NO_BMT") != nullptr;
     w.no_merge = getenv("G4R_NO_MERGE") != nullptr; w.owner_scan_in_update = env_int("G4R_OWNER_SCAN", 0) != 0;
+    w.score_b_split = env_int("G4R_SCORE_B_SPLIT", 1) != 0;
     w.allow_lean_update = env_int("G4R_LEAN_UPDATE", 1) != 0; w.defer = env_int("G4R_DEFER", cfg.defer_updates) != 0;
     w.p2_geo = env_int("G4R_P2_GEO", -1); w.ba_geo = env_int("G4R_BA_GEO", -1);
     w.wide2 = env_int("G4R_WIDE2", -1); w.p1_ks = env_int("G4R_P1_KS", 128); w.bb_ks = env_int("G4R_BB_KS", 0);

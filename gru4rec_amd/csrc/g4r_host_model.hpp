@@ -39,6 +39,7 @@ struct KernelSwitches {
     bool no_mt = false, no_bmt = false;   // G4R_NO_MT / G4R_NO_BMT: the 64 x 64 scoring tiles instead of k_score_mt / k_score_bmt
     bool no_merge = false;                // G4R_NO_MERGE: dense gradients and sparse rows as two launches, never the merged k_update
     bool allow_lean_update = true;        // G4R_LEAN_UPDATE=0: the merged k_update where k_update_l would run, as the deferred mode runs it
+    bool score_b_split = true;            // G4R_SCORE_B_SPLIT=0: k_score_b keeps its role A (the item-gradient tiles), no hosting in k_gru_dy
     bool owner_scan_in_update = false;    // G4R_OWNER_SCAN=1: k_update_l's owners of repeated items scan occ_idx themselves (no pre-scan in k_loss_rows)
     bool defer = false;                   // G4R_DEFER (default: g4r_config::defer_updates)
     int p2_geo = -1, ba_geo = -1;         // G4R_P2_GEO / G4R_BA_GEO = 0 / 1: the 4-wave / 8-wave geometry of k_gru_p2 / k_gru_bwd_a (-1: the policy)
@@ -63,6 +64,7 @@ struct StepKernels {
     int score_fwd;
     int loss_spec, loss_long, loss_quads;      // k_loss_rows<loss_long, loss_spec, loss_long || loss_quads ? 4 : 1>
     int score_bwd;
+    int score_a_host;                     // k_score_b's role A: 0 in k_score_b itself, 1 as extra workgroups of the top layer's k_gru_dy (k_gru_dy_a); debug key `score_b_split`
     int kch, ksplit;                      // slabs of the scoring backward: kch score columns each, ksplit of them (-> DevModel)
     int bmt_slabs;                        // k_score_bmt's role-B slabs (0: not chosen)
     int nblkA, nblkB, ndtA, ndtB, nrtB;   // k_score_bwd_w / _n: role A tiles (n x d, one spare d column for dSBy), role B tiles (b x d x slab)
@@ -383,6 +385,9 @@ static StepKernels choose_kernels(const DevModel& d, int n_cu, const KernelSwitc
             k.bmt_slabs = ks;
     }
     k.score_bwd = (lean_s && B <= 128) ? SB_LEAN : k.bmt_slabs ? SB_BMT : bwd2 ? SB_BWD2 : wide ? SB_W : SB_N;
+    // k_score_b's role A (dSy, dSBy, the item rows' Adagrad pieces: nothing before the update reads them) rides in the top layer's k_gru_dy
+    // launch, which leaves most CUs idle, instead of doubling the grid of the step's longest launch (profiles/r08_experiments.md)
+    k.score_a_host = (sw.score_b_split && k.score_bwd == SB_LEAN && k.bwd[top] == BWD_LEAN) ? 1 : 0;
     // its slabs: ~17; half as many, twice as deep where k_gru_bwd_fused / k_gru_da sum them next to everything else they load
     const int slabs_target = top_tiles ? 17 : 9;
     k.kch = GT_BK * std::max(1, (cdiv(d.ldSc, GT_BK) + slabs_target / 2) / slabs_target);

@@ -44,6 +44,9 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
     StepState* stp = (StepState*)d.st;
     // g4r_profile(m, 2): the two roles of a merged update as launches of their own
     const bool merged = k.update != UP_SPLIT && !(recs && m->profile_split);
+    // per-kernel profiling times k_score_b with both roles in it (what the per-kernel tables price as the scoring backward), as it
+    // times the update in two launches: the moved form is what graph replay and plain eager steps run
+    const bool a_hosted = k.score_a_host && !recs;
     if (part != 2) {
     for (int l = 0; l < L; ++l) {
         if (k.fwd[l] == FWD_LEAN) {
@@ -133,8 +136,11 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
     switch (k.score_bwd) {
     case SB_LEAN: {
         const LeanB& q = m->h_leanB;
-        LK(k_score_b, dim3(q.nA + d.ksplit * q.nrb * q.ndb), dim3(512), 0, s, (const LeanB*)m->d_leanB, (const int*)(d.cur_in + 2 * B), (const int*)d.cur_col,
-           (const float*)d.Sc, (const float*)d.hd[L - 1], (const float*)d.Wy, (float*)d.accWy, (unsigned)d.Dtop | ((unsigned)B << 16), (unsigned)d.N | ((unsigned)d.ldSc << 16));
+#define G4R_LK_SB(RA, NWG) LK(k_score_b<RA>, dim3(NWG), dim3(512), 0, s, (const LeanB*)m->d_leanB, (const int*)(d.cur_in + 2 * B), (const int*)d.cur_col,   \
+           (const float*)d.Sc, (const float*)d.hd[L - 1], (const float*)d.Wy, (float*)d.accWy, (unsigned)d.Dtop | ((unsigned)B << 16), (unsigned)d.N | ((unsigned)d.ldSc << 16))
+        if (a_hosted) G4R_LK_SB(false, d.ksplit * q.nrb * q.ndb);      // role B alone: role A rides in the top layer's k_gru_dy launch below
+        else G4R_LK_SB(true, q.nA + d.ksplit * q.nrb * q.ndb);
+#undef G4R_LK_SB
         break;
     }
     case SB_BMT: {
@@ -167,6 +173,16 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
             begin(KN_GRU_DY);
             {
                 const LeanDy& y = m->h_leanDy[l];
+                if (a_hosted && l == L - 1) {
+                    // + k_score_b's role A, two tiles per workgroup, in grid rows behind the launch's own (k_gru_dy_a: what keeps the two
+                    // independent -- single-occurrence accumulator rows, no buffer one writes and the other reads -- is written there)
+                    const LeanB& q = m->h_leanB;
+                    const int gx = cdiv(d.IN[l], 16);
+                    LK(k_gru_dy_a, dim3(gx, nrb + cdiv(cdiv(q.nA, 2), gx)), dim3(1024), 0, s, (const LeanDy*)(m->d_leanDy + l), (const int*)(d.cur_in + 2 * B),
+                       (const int*)y.occ_idx, (const float*)y.dV, (const float*)y.drp, (const float*)y.Wx, (const float*)y.r, (unsigned)d.D[l] | ((unsigned)d.IN[l] << 16),
+                       (unsigned)B, (const LeanB*)m->d_leanB, (const int*)d.cur_col, (const float*)d.Sc, (const float*)d.hd[L - 1], (float*)d.accWy,
+                       (unsigned)d.Dtop | ((unsigned)B << 16), (unsigned)d.N | ((unsigned)d.ldSc << 16), (unsigned)q.nA | ((unsigned)q.ndh << 16));
+                } else
                 LK(k_gru_dy, dim3(cdiv(d.IN[l], 16), nrb), dim3(1024), 0, s, (const LeanDy*)(m->d_leanDy + l), (const int*)(d.cur_in + 2 * B), (const int*)y.occ_idx,
                    (const float*)y.dV, (const float*)y.drp, (const float*)y.Wx, (const float*)y.r, (unsigned)d.D[l] | ((unsigned)d.IN[l] << 16), (unsigned)B);
             }

@@ -46,12 +46,16 @@ __device__ __forceinline__ void stu4(GAS float* base, unsigned boff, float4 v) {
 #define LSPAN_BEGIN(tilep, base) GAS long long* span_ = ((tilep) && threadIdx.x == 0) ? (tilep) + 8 * (size_t)((base) + (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) : nullptr; \
     if (span_) span_[0] = wall_clock64()
 #define LSPAN_END() do { if (span_) span_[1] = wall_clock64(); } while (0)
+// the same for a workgroup (or half of one) whose row of the table is not its linear id: row `idx`, stamped by the thread that has `lead`
+#define LSPAN_BEGIN_AT(tilep, idx, lead) GAS long long* span_ = ((tilep) && (lead)) ? (tilep) + 8 * (size_t)(idx) : nullptr; \
+    if (span_) span_[0] = wall_clock64()
 #else
 #define LCLK_INIT(dbgp, slot)
 #define LCLK(i)
 #define LCLK_USE(x)
 #define LSPAN_BEGIN(tilep, base)
 #define LSPAN_END()
+#define LSPAN_BEGIN_AT(tilep, idx, lead)
 #endif
 
 // argument blocks (device resident, one per layer; g4r_host_create.hpp: build_lean_args).  Pointers only to buffers that live as long as the model.
@@ -463,9 +467,8 @@ __global__ __launch_bounds__(128) void k_gru_da(const LeanDa* __restrict__ ap, c
 // writes it to dV[:, D:2D] for the dense-gradient tiles.  Epilogue (waves 0 .. 3, as k_gru_bwd_b): layer 0 embedding-dropout mask and the
 // Adagrad pieces dSx / dAx (or the accumulator in place for a single-occurrence item), else the lower layer's dh.
 #define LN_PL 8        // partial planes (= ceil(D / 16) <= 8)
-__global__ __launch_bounds__(1024) void k_gru_dy(const LeanDy* __restrict__ ap, const int* meta_, const int* occ_idx_, const float* dV_, const float* drp_,
-                                                 const float* Wx_, const float* r_, unsigned dims, unsigned B) {
-    __shared__ float sJ[4 * 16 * 64];
+__device__ __forceinline__ void gru_dy_tile(const LeanDy* __restrict__ ap, const int* meta_, const int* occ_idx_, const float* dV_, const float* drp_,
+                                            const float* Wx_, const float* r_, const unsigned dims, const unsigned B, float* sJ) {
     const unsigned tid = threadIdx.x, lane = tid & 63, li = lane & 15, lg = lane >> 4;
     const unsigned wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned D = dims & 0xFFFFu, IN = dims >> 16, Dq = D >> 2;
@@ -580,6 +583,9 @@ __global__ __launch_bounds__(1024) void k_gru_dy(const LeanDy* __restrict__ ap, 
     const LeanDy a = *ap;
     LCLK_INIT(a.dbg, 48); LCLK(6);
     LSPAN_BEGIN(a.dbgtile, 1500);
+#if defined(G4R_CLK_TRACE)
+    if (span_) { span_[2] = span_[0]; span_[0] = tk0; }      // the span from the workgroup's first instruction; [2]: the epilogue's start
+#endif
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < 16; ++w) v += sJ[(wid * 16 + w) * 64 + lane];      // K slices in wave order
@@ -597,6 +603,11 @@ __global__ __launch_bounds__(1024) void k_gru_dy(const LeanDy* __restrict__ ap, 
     }
     LCLK(7);
     LSPAN_END();
+}
+__global__ __launch_bounds__(1024) void k_gru_dy(const LeanDy* __restrict__ ap, const int* meta_, const int* occ_idx_, const float* dV_, const float* drp_,
+                                                 const float* Wx_, const float* r_, unsigned dims, unsigned B) {
+    __shared__ float sJ[4 * 16 * 64];
+    gru_dy_tile(ap, meta_, occ_idx_, dV_, drp_, Wx_, r_, dims, B, sJ);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -715,140 +726,194 @@ template __global__ void k_score_s<true>(const LeanS*, const int*, const int*, c
 //   role B: slab kc of dh = ds Sy (gathered Wy rows of 128 score columns), 16 batch rows x 64 d; wave w takes columns 16 w .. 16 w + 15 of
 //          the slab.  k_gru_da adds the slabs in slab order.
 // Replaces k_score_bwd<32, 128> (LDS-staged 32 x 32 tiles, 6.0 us in the step) where k_score_s replaces k_score_fwd.
+// Role A, tile `t` (column tile t / ndh, d block t % ndh; ndh = LeanB::ndh), on the eight waves `wid` = 0 .. 7 of the caller that share the 32 KB at sJ.  Every
+// wave of the caller reaches the barrier inside; `live` == false (a hosted workgroup's half behind the last tile: the caller clamps t)
+// computes and leaves without a store.  `lead`: the thread that stamps the tile's row of the span table (trace builds).
+__device__ __forceinline__ void score_b_role_a(const LeanB& a, const int4 mt, const GAS int* cur_col, const GAS float* Sc, const GAS float* hd, float* accWy_,
+                                               const unsigned D, const unsigned B, const unsigned N, const unsigned ldSc, const unsigned t, const unsigned ndh,
+                                               const unsigned wid, const unsigned lane, f32x4* sJ, const bool live, const bool lead) {
+    const unsigned li = lane & 15, lg = lane >> 4;
+    LSPAN_BEGIN_AT(a.dbgtile, 2048 + t, lead && live);
+    f32x4 acc[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const unsigned nt = t / ndh, dh_ = t - nt * ndh;
+    const unsigned n0 = 16 * nt, d0 = 64 * dh_;
+    const unsigned n = n0 + li, nc = min(n, ldSc - 1);
+    // epilogue operands of wave rg (requested first: the gathers behind the item id are the longest chain of the kernel)
+    const unsigned d4 = d0 + 16 * lg + 4 * (wid & 3);
+    const int item = ldu_i(cur_col, 4 * nc);
+    // operands: wave w -> batch rows 16 w + 4 s + lg, s = 0 .. 3
+    float4 av[4];
+    float bv[4];
+    const unsigned da = d0 + 4 * li;      // h columns da .. da + 3 (A operand: output index i <-> d = d0 + 4 i + c)
+    const unsigned dac = min(da, D - 4);
+#pragma unroll
+    for (int s_ = 0; s_ < 4; ++s_) {
+        const unsigned b = min(16 * wid + 4 * s_ + lg, B - 1);
+        av[s_] = ldu4(hd, 4 * (b * D + dac));
+        bv[s_] = ldu(Sc, 4 * (b * ldSc + nc));
+    }
+    lean_pin(a.accBy, a.occ_fl);
+    const bool iok = item >= 0 && n < N;
+    const unsigned ic = (unsigned)max(item, 0);
+    // (every wave requests them, with clamped addresses and no branch around the loads: a branch here makes hipcc drain ALL loads
+    // at its join -- the accumulator gather's round trip then sits in front of the MFMAs instead of under them)
+    float4 acc4 = ld4((const GAS float*)accWy_ + (size_t)ic * D + min(d4, D - 4));
+    const float accb = a.accBy[ic];
+    const int cnt = a.occ_fl[4 * (size_t)ic + 2];
+    if (d4 >= D) acc4 = make_float4(accb, 0.f, 0.f, 0.f);
+    __builtin_amdgcn_sched_barrier(0);      // (all loads out before the first MFMA)
+    const LeanState sx = lean_state(mt);
+    const int M = sx.M;
+#pragma unroll
+    for (int s_ = 0; s_ < 4; ++s_) {
+        const unsigned b = 16 * wid + 4 * s_ + lg;
+        const bool bok = (int)b < M;
+        float4 h4 = av[s_];
+        // columns past the layer: the ones column at d == D (bias gradient), zeros behind it
+        const float hx[4] = {h4.x, h4.y, h4.z, h4.w};
+        float hv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) hv[c] = (da + c < D) ? hx[c] : ((da + c == D) ? 1.f : 0.f);
+        const float dsv = (bok && n < ldSc) ? bv[s_] : 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = mfma16(hv[c], dsv, acc[c]);
+    }
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) sJ[(rg * 8 + wid) * 64 + lane] = (f32x4){acc[0][rg], acc[1][rg], acc[2][rg], acc[3][rg]};
+    __syncthreads();
+    if (wid >= 4 || !live) return;
+    f32x4 g4 = sJ[(wid * 8 + 0) * 64 + lane];      // batch slices in wave order
+#pragma unroll
+    for (int w = 1; w < 8; ++w) g4 += sJ[(wid * 8 + w) * 64 + lane];
+    if (n >= N || d4 > D) return;
+    const float gg[4] = {g4[0], g4[1], g4[2], g4[3]}, a0[4] = {acc4.x, acc4.y, acc4.z, acc4.w};
+    float st[4], an[4];
+    const bool generic = a.generic != 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        an[c] = a0[c] + G4R_MUT_ACC(gg[c] * gg[c]);
+        st[c] = iok ? G4R_MUT_ROW(n, G4R_MUT_STEP(a.lr * gg[c] * frsq(an[c] + G4R_EPS_ADAGRAD))) : 0.f;
+        if (generic) st[c] = iok ? gg[c] : 0.f;      // raw per-occurrence gradient: the update kernel applies the rule
+    }
+    const bool single = !generic && iok && cnt == 1;
+    const size_t slot = (size_t)(sx.g & (unsigned)a.defer_mask);
+    if (d4 < D) {
+        st4(a.dSy + slot * (size_t)a.dSy_stride + (size_t)n * D + d4, make_float4(st[0], st[1], st[2], st[3]));
+        if (single) st4((GAS float*)accWy_ + (size_t)ic * D + d4, make_float4(an[0], an[1], an[2], an[3]));
+        else st4(a.dAy + (size_t)n * D + d4, make_float4(an[0], an[1], an[2], an[3]));
+    } else {      // d4 == D: the bias column
+        (a.dSBy + slot * (size_t)a.dSBy_stride)[n] = st[0];
+        if (single) a.accBy[ic] = an[0]; else a.dABy[n] = an[0];
+    }
+    LSPAN_END();
+}
+
+// Role B, workgroup `w_` of the role (slab w_ / (nrb ndb), then row block, then d block), eight waves, 32 KB at sJ.
+__device__ __forceinline__ void score_b_role_b(const LeanB& a, const int4 mt, const GAS int* cur_col, const GAS float* Sc, const float* Wy_,
+                                               const unsigned D, const unsigned B, const unsigned ldSc, const unsigned w_,
+                                               const unsigned wid, const unsigned lane, f32x4* sJ) {
+    const unsigned li = lane & 15, lg = lane >> 4;
+    LSPAN_BEGIN_AT(a.dbgtile, 2048 + (unsigned)a.nA + w_, threadIdx.x == 0);
+    f32x4 acc[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const unsigned per = (unsigned)(a.nrb * a.ndb);
+    const unsigned kc = w_ / per, rem = w_ - kc * per, rb = rem / (unsigned)a.ndb, db = rem - rb * (unsigned)a.ndb;
+    const unsigned b0 = 16 * rb, d0 = 64 * db;
+    // wave w: score columns kbeg + 16 w + 4 lg + u (u = 0 .. 3) as K; A operand: ds[b0 + li][those four] (K-contiguous float4),
+    // B operand: the gathered Wy rows of the four columns, float4 along d (output index j <-> d = d0 + 4 j + c)
+    const unsigned nk = 128 * kc + 16 * wid + 4 * lg;
+    const unsigned nkc = min(nk, ldSc - 4);
+    const int4 it4 = ldi4(cur_col + nkc);
+    float4 ds4 = ldu4(Sc, 4 * (min(b0 + li, B - 1) * ldSc + nkc));
+    const unsigned dq = d0 + 4 * li, dqc = min(dq, D - 4);
+    const GAS float* Wy = (const GAS float*)Wy_;
+    const int its[4] = {it4.x, it4.y, it4.z, it4.w};
+    float4 wv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) wv[u] = ld4(Wy + (size_t)max(its[u], 0) * D + dqc);
+    __builtin_amdgcn_sched_barrier(0);      // (all four gathers out before the first MFMA: hipcc otherwise sinks two of them behind it)
+    const LeanState sx = lean_state(mt);
+    const int M = sx.M;
+    if ((int)b0 >= M) return;
+    const float dsx[4] = {ds4.x, ds4.y, ds4.z, ds4.w};
+    const bool bok = (int)(b0 + li) < M;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const bool kok = nk + u < ldSc && nk == nkc && its[u] >= 0 && dq < D;
+        const float av_ = bok ? dsx[u] : 0.f;
+        const float4 w4 = kok ? wv[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+        acc[0] = mfma16(av_, w4.x, acc[0]);
+        acc[1] = mfma16(av_, w4.y, acc[1]);
+        acc[2] = mfma16(av_, w4.z, acc[2]);
+        acc[3] = mfma16(av_, w4.w, acc[3]);
+    }
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) sJ[(rg * 8 + wid) * 64 + lane] = (f32x4){acc[0][rg], acc[1][rg], acc[2][rg], acc[3][rg]};
+    __syncthreads();
+    if (wid >= 4) return;
+    f32x4 v = sJ[(wid * 8 + 0) * 64 + lane];      // column groups in wave order
+#pragma unroll
+    for (int w = 1; w < 8; ++w) v += sJ[(wid * 8 + w) * 64 + lane];
+    const unsigned b = b0 + 4 * lg + (wid & 3);
+    if ((int)b < M && dq < D) st4(a.dhpart + ((size_t)kc * B + b) * D + dq, make_float4(v[0], v[1], v[2], v[3]));
+    LSPAN_END();
+}
+
+// ROLE_A: both roles in the launch (role A's nA workgroups first); else role B alone -- the role-A tiles then run as extra workgroups of
+// the top layer's k_gru_dy launch (k_gru_dy_a below), off the chain k_score_b -> k_gru_da -> k_gru_dy -> k_update_l.
+template <bool ROLE_A>
 __global__ __launch_bounds__(512) void k_score_b(const LeanB* __restrict__ ap, const int* meta_, const int* cur_col_, const float* Sc_, const float* hd_,
                                                  const float* Wy_, float* accWy_, unsigned dimsA, unsigned dimsB) {
     __shared__ f32x4 sJ[4 * 8 * 64];
-    const unsigned tid = threadIdx.x, lane = tid & 63, li = lane & 15, lg = lane >> 4;
+    const unsigned tid = threadIdx.x, lane = tid & 63;
     const unsigned wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned D = dimsA & 0xFFFFu, B = dimsA >> 16, N = dimsB & 0xFFFFu, ldSc = dimsB >> 16;
     const GAS int* cur_col = (const GAS int*)cur_col_;
     const GAS float *Sc = (const GAS float*)Sc_, *hd = (const GAS float*)hd_;
     const int4 mt = ldi4((const GAS int*)meta_);
     const LeanB a = *ap;      // (its role-dependent fields are used far below: the compiler's lazy loads cost nothing there)
-    LSPAN_BEGIN(a.dbgtile, 2048);
-    f32x4 acc[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (blockIdx.x < (unsigned)a.nA) {
-        // ---------------- role A
-        const unsigned nt = blockIdx.x / (unsigned)a.ndh, dh_ = blockIdx.x - nt * (unsigned)a.ndh;
-        const unsigned n0 = 16 * nt, d0 = 64 * dh_;
-        const unsigned n = n0 + li, nc = min(n, ldSc - 1);
-        // epilogue operands of wave rg (requested first: the gathers behind the item id are the longest chain of the kernel)
-        const unsigned d4 = d0 + 16 * lg + 4 * (wid & 3);
-        const int item = ldu_i(cur_col, 4 * nc);
-        // operands: wave w -> batch rows 16 w + 4 s + lg, s = 0 .. 3
-        float4 av[4];
-        float bv[4];
-        const unsigned da = d0 + 4 * li;      // h columns da .. da + 3 (A operand: output index i <-> d = d0 + 4 i + c)
-        const unsigned dac = min(da, D - 4);
-#pragma unroll
-        for (int s_ = 0; s_ < 4; ++s_) {
-            const unsigned b = min(16 * wid + 4 * s_ + lg, B - 1);
-            av[s_] = ldu4(hd, 4 * (b * D + dac));
-            bv[s_] = ldu(Sc, 4 * (b * ldSc + nc));
-        }
-        lean_pin(a.accBy, a.occ_fl);
-        const bool iok = item >= 0 && n < N;
-        const unsigned ic = (unsigned)max(item, 0);
-        // (every wave requests them, with clamped addresses and no branch around the loads: a branch here makes hipcc drain ALL loads
-        // at its join -- the accumulator gather's round trip then sits in front of the MFMAs instead of under them)
-        float4 acc4 = ld4((const GAS float*)accWy_ + (size_t)ic * D + min(d4, D - 4));
-        const float accb = a.accBy[ic];
-        const int cnt = a.occ_fl[4 * (size_t)ic + 2];
-        if (d4 >= D) acc4 = make_float4(accb, 0.f, 0.f, 0.f);
-        __builtin_amdgcn_sched_barrier(0);      // (all loads out before the first MFMA)
-        const LeanState sx = lean_state(mt);
-        const int M = sx.M;
-#pragma unroll
-        for (int s_ = 0; s_ < 4; ++s_) {
-            const unsigned b = 16 * wid + 4 * s_ + lg;
-            const bool bok = (int)b < M;
-            float4 h4 = av[s_];
-            // columns past the layer: the ones column at d == D (bias gradient), zeros behind it
-            const float hx[4] = {h4.x, h4.y, h4.z, h4.w};
-            float hv[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) hv[c] = (da + c < D) ? hx[c] : ((da + c == D) ? 1.f : 0.f);
-            const float dsv = (bok && n < ldSc) ? bv[s_] : 0.f;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[c] = mfma16(hv[c], dsv, acc[c]);
-        }
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) sJ[(rg * 8 + wid) * 64 + lane] = (f32x4){acc[0][rg], acc[1][rg], acc[2][rg], acc[3][rg]};
-        __syncthreads();
-        if (wid >= 4) return;
-        f32x4 g4 = sJ[(wid * 8 + 0) * 64 + lane];      // batch slices in wave order
-#pragma unroll
-        for (int w = 1; w < 8; ++w) g4 += sJ[(wid * 8 + w) * 64 + lane];
-        if (n >= N || d4 > D) return;
-        const float gg[4] = {g4[0], g4[1], g4[2], g4[3]}, a0[4] = {acc4.x, acc4.y, acc4.z, acc4.w};
-        float st[4], an[4];
-        const bool generic = a.generic != 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            an[c] = a0[c] + G4R_MUT_ACC(gg[c] * gg[c]);
-            st[c] = iok ? G4R_MUT_ROW(n, G4R_MUT_STEP(a.lr * gg[c] * frsq(an[c] + G4R_EPS_ADAGRAD))) : 0.f;
-            if (generic) st[c] = iok ? gg[c] : 0.f;      // raw per-occurrence gradient: the update kernel applies the rule
-        }
-        const bool single = !generic && iok && cnt == 1;
-        const size_t slot = (size_t)(sx.g & (unsigned)a.defer_mask);
-        if (d4 < D) {
-            st4(a.dSy + slot * (size_t)a.dSy_stride + (size_t)n * D + d4, make_float4(st[0], st[1], st[2], st[3]));
-            if (single) st4((GAS float*)accWy_ + (size_t)ic * D + d4, make_float4(an[0], an[1], an[2], an[3]));
-            else st4(a.dAy + (size_t)n * D + d4, make_float4(an[0], an[1], an[2], an[3]));
-        } else {      // d4 == D: the bias column
-            (a.dSBy + slot * (size_t)a.dSBy_stride)[n] = st[0];
-            if (single) a.accBy[ic] = an[0]; else a.dABy[n] = an[0];
-        }
-        LSPAN_END();
-        return;
+    if (ROLE_A) {
+        if (blockIdx.x < (unsigned)a.nA) { score_b_role_a(a, mt, cur_col, Sc, hd, accWy_, D, B, N, ldSc, blockIdx.x, (unsigned)a.ndh, wid, lane, sJ, true, tid == 0); return; }
+        score_b_role_b(a, mt, cur_col, Sc, Wy_, D, B, ldSc, blockIdx.x - (unsigned)a.nA, wid, lane, sJ);
+    } else {
+        score_b_role_b(a, mt, cur_col, Sc, Wy_, D, B, ldSc, blockIdx.x, wid, lane, sJ);
     }
-    // ---------------- role B
-    {
-        const unsigned w_ = blockIdx.x - (unsigned)a.nA;
-        const unsigned per = (unsigned)(a.nrb * a.ndb);
-        const unsigned kc = w_ / per, rem = w_ - kc * per, rb = rem / (unsigned)a.ndb, db = rem - rb * (unsigned)a.ndb;
-        const unsigned b0 = 16 * rb, d0 = 64 * db;
-        // wave w: score columns kbeg + 16 w + 4 lg + u (u = 0 .. 3) as K; A operand: ds[b0 + li][those four] (K-contiguous float4),
-        // B operand: the gathered Wy rows of the four columns, float4 along d (output index j <-> d = d0 + 4 j + c)
-        const unsigned nk = 128 * kc + 16 * wid + 4 * lg;
-        const unsigned nkc = min(nk, ldSc - 4);
-        const int4 it4 = ldi4(cur_col + nkc);
-        float4 ds4 = ldu4(Sc, 4 * (min(b0 + li, B - 1) * ldSc + nkc));
-        const unsigned dq = d0 + 4 * li, dqc = min(dq, D - 4);
-        const GAS float* Wy = (const GAS float*)Wy_;
-        const int its[4] = {it4.x, it4.y, it4.z, it4.w};
-        float4 wv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) wv[u] = ld4(Wy + (size_t)max(its[u], 0) * D + dqc);
-        __builtin_amdgcn_sched_barrier(0);      // (all four gathers out before the first MFMA: hipcc otherwise sinks two of them behind it)
-        const LeanState sx = lean_state(mt);
-        const int M = sx.M;
-        if ((int)b0 >= M) return;
-        const float dsx[4] = {ds4.x, ds4.y, ds4.z, ds4.w};
-        const bool bok = (int)(b0 + li) < M;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool kok = nk + u < ldSc && nk == nkc && its[u] >= 0 && dq < D;
-            const float av_ = bok ? dsx[u] : 0.f;
-            const float4 w4 = kok ? wv[u] : make_float4(0.f, 0.f, 0.f, 0.f);
-            acc[0] = mfma16(av_, w4.x, acc[0]);
-            acc[1] = mfma16(av_, w4.y, acc[1]);
-            acc[2] = mfma16(av_, w4.z, acc[2]);
-            acc[3] = mfma16(av_, w4.w, acc[3]);
-        }
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) sJ[(rg * 8 + wid) * 64 + lane] = (f32x4){acc[0][rg], acc[1][rg], acc[2][rg], acc[3][rg]};
-        __syncthreads();
-        if (wid >= 4) return;
-        f32x4 v = sJ[(wid * 8 + 0) * 64 + lane];      // column groups in wave order
-#pragma unroll
-        for (int w = 1; w < 8; ++w) v += sJ[(wid * 8 + w) * 64 + lane];
-        const unsigned b = b0 + 4 * lg + (wid & 3);
-        if ((int)b < M && dq < D) st4(a.dhpart + ((size_t)kc * B + b) * D + dq, make_float4(v[0], v[1], v[2], v[3]));
-        LSPAN_END();
-    }
+}
+template __global__ void k_score_b<true>(const LeanB*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned);
+template __global__ void k_score_b<false>(const LeanB*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned);
+
+// The top layer's k_gru_dy launch with k_score_b's role A behind it: rows [0, ceil(B / 16)) of the grid are k_gru_dy's own workgroups
+// (dispatched first), the rows behind them carry TWO role-A tiles each (waves 0 .. 7 tile 2 h, waves 8 .. 15 tile 2 h + 1, 32 KB of LDS per
+// half, one barrier both halves reach), on CUs the own workgroups leave idle.  Role A's arguments -- tilesA = nA | ndh << 16 with them, so
+// that no load waits for the LeanB block -- come as kernel arguments behind k_gru_dy's: one scalar round trip in front of a hosted
+// workgroup's first request (the own workgroups wait for `dims` / `B` from the same segment, as in k_gru_dy).
+// What makes the two independent inside one launch:
+//   - accumulator rows in place: both epilogues write an item's accumulator row only for an item that occurs ONCE in the step (occ_fl
+//     count over X, Y and the samples of the row's table), so never the same row -- also with a constrained embedding, where layer 0's
+//     X rows and the scored rows share accWy; an item both wrote would have count >= 2 and goes through dAx / dAy;
+//   - role A reads Sc (k_loss_rows' ds), hd, the staged step state and occ_fl counts, which no launch between k_loss_rows and the
+//     update's bookkeeping writes; it reads nothing k_gru_da / k_gru_dy write (dV, drp, dSx, dAx, dylo);
+//   - dSy / dSBy / dAy / dABy and the accumulator rows role A wrote are first read by the update launch behind this one.
+// Two GRU layers: the host is the top layer's launch (the first k_gru_dy of the step); the lower layers' launches are plain k_gru_dy.
+__global__ __launch_bounds__(1024) void k_gru_dy_a(const LeanDy* __restrict__ ap, const int* meta_, const int* occ_idx_, const float* dV_, const float* drp_,
+                                                   const float* Wx_, const float* r_, unsigned dims, unsigned B, const LeanB* __restrict__ bp,
+                                                   const int* cur_col_, const float* Sc_, const float* hd_, float* accWy_, unsigned dimsA, unsigned dimsB, unsigned tilesA) {
+    __shared__ f32x4 sJ[2 * 4 * 8 * 64];
+    const unsigned nrb = (B + 15) >> 4;
+    if (blockIdx.y < nrb) { gru_dy_tile(ap, meta_, occ_idx_, dV_, drp_, Wx_, r_, dims, B, (float*)sJ); return; }
+    const unsigned tid = threadIdx.x, lane = tid & 63;
+    const unsigned wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned nA = tilesA & 0xFFFFu, half = wid >> 3;
+    const unsigned t0 = 2 * ((blockIdx.y - nrb) * gridDim.x + blockIdx.x), t = t0 + half;
+    if (t0 >= nA) return;      // (the whole workgroup: the grid is rounded up to rows)
+    const int4 mt = ldi4((const GAS int*)meta_);
+    const LeanB a = *bp;
+    const bool live = t < nA;
+    score_b_role_a(a, mt, (const GAS int*)cur_col_, (const GAS float*)Sc_, (const GAS float*)hd_, accWy_, dimsA & 0xFFFFu, dimsA >> 16, dimsB & 0xFFFFu,
+                   dimsB >> 16, live ? t : nA - 1, tilesA >> 16, wid & 7, lane, sJ + half * (4 * 8 * 64), live, (tid & 511) == 0);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """In-kernel phase stamps of the lean GRU kernels (debug build: python -m gru4rec_amd.build --variant tmp_var/libclk.so G4R_CLK_TRACE;
-G4R_LIB=tmp_var/libclk.so G4R_CLK=1 python tools/clk_lean.py)"""
+G4R_LIB=tmp_var/libclk.so G4R_CLK=1 python tools/clk_lean.py; GRAPH=1: stamps of a graph replay; G4R_SCORE_B_SPLIT=0: role A kept in k_score_b)"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,8 +34,9 @@ for rep in range(5):
     tl_all = m.get_debug('dbgtile', (2 * 8 * 8192,)).view(np.int64).reshape(8192, 8)
     B_, N_, D_ = cfg['batch_size'], cfg['batch_size'] + cfg['n_sample'], cfg['layers'][-1]
     ld = (N_ + 15) // 16 * 16
+    # (k_score_b: per role, below -- its role-A rows may belong to the k_gru_dy launch)
     regions = [('k_gru_v', 1024, 3 * ((D_ + 15) // 16) * ((B_ + 15) // 16)), ('k_gru_h', 1280, ((D_ + 15) // 16) * ((B_ + 15) // 16)),
-               ('k_score_s', 4096, ((ld + 31) // 32) * ((B_ + 31) // 32)), ('k_score_b', 2048, ((ld + 15) // 16) * ((D_ + 64) // 64) + ((ld + 127) // 128) * ((B_ + 15) // 16) * ((D_ + 63) // 64)),
+               ('k_score_s', 4096, ((ld + 31) // 32) * ((B_ + 31) // 32)),
                ('k_update_l', 2700, 6 + 82 + (2 * B_ + cfg['n_sample'] + 7) // 8), ('k_loss_rows', 7168, B_ + NOWN),
                ('k_gru_da', 1400, ((D_ + 15) // 16) * ((B_ + 15) // 16)), ('k_gru_dy', 1500, ((D_ + 15) // 16) * ((B_ + 15) // 16))]
     t0 = None
@@ -49,6 +50,28 @@ for rep in range(5):
         d = (t[:, 1] - t[:, 0]) / 100.
         print('   %-10s %4d workgroups: first stamp at %+6.2f .. %+6.2f us, last stamp at %+6.2f .. %+6.2f us (after k_gru_v began); own duration median %.2f max %.2f' % (
             name, len(t), (t[:, 0].min() - t0) / 100., (t[:, 0].max() - t0) / 100., (t[:, 1].min() - t0) / 100., (t[:, 1].max() - t0) / 100., np.median(d), d.max()))
+    # k_score_b's table (dbgtile[2048 ..]): role A's nA tiles first, then role B -- whichever launch ran role A (k_score_b itself, or the
+    # top layer's k_gru_dy launch when the debug key score_b_split says 1); k_gru_dy's own workgroups from their first instruction
+    nA = ((ld + 15) // 16) * ((D_ + 64) // 64)
+    nB = ((ld + 127) // 128) * ((B_ + 15) // 16) * ((D_ + 63) // 64)
+    moved = int(m.get_debug('score_b_split', (1,))[0])
+    tb = tl_all[2048:2048 + nA + nB]
+    okb = tb[nA:][tb[nA:, 1] > 0]
+    if len(okb):
+        t0b = okb[:, 0].min()      # role B's first start: the launch k_score_b in both forms
+        ends = {}
+        for nm, tt in (('k_score_b role A (%s)' % ('hosted in k_gru_dy' if moved else 'in k_score_b'), tb[:nA]), ('k_score_b role B', tb[nA:]),
+                       ('k_gru_da', tl_all[1400:1400 + ((D_ + 15) // 16) * ((B_ + 15) // 16)]),
+                       ('k_gru_dy own workgroups', tl_all[1500:1500 + ((D_ + 15) // 16) * ((B_ + 15) // 16)])):
+            tt = tt[tt[:, 1] > 0]
+            if len(tt):
+                ends[nm[:8]] = (tt[:, 0].min(), tt[:, 1].max())
+                print('      %-38s %4d: start %+5.2f .. %+5.2f, end %+5.2f .. %+5.2f us (after role B began); own duration median %.2f max %.2f' % (
+                    nm, len(tt), (tt[:, 0].min() - t0b) / 100., (tt[:, 0].max() - t0b) / 100., (tt[:, 1].min() - t0b) / 100., (tt[:, 1].max() - t0b) / 100.,
+                    np.median((tt[:, 1] - tt[:, 0]) / 100.), ((tt[:, 1] - tt[:, 0]) / 100.).max()))
+        kb_end = max(tb[tb[:, 1] > 0][:, 1].max(), 0) if not moved else okb[:, 1].max()
+        if 'k_gru_da' in ends:
+            print('      k_score_b launch: last end %+5.2f us; gap to k_gru_da\'s first start %.2f us' % ((kb_end - t0b) / 100., (ends['k_gru_da'][0] - kb_end) / 100.))
     # k_loss_rows (dbgtile[7168 ..]): the B row workgroups, then the owner pre-scan of k_update_l (if any)
     tl = tl_all[7168:7168 + B_ + NOWN]
     ok = tl[:, 1] > 0
