@@ -15,6 +15,7 @@ G4R_MAX_LAYERS = 8
 G4R_TOPK_MAX = 256      # largest k of g4r_recommend_step
 G4R_EXCLUDE_MAX = 1024  # most distinct items one row of g4r_recommend_step_filtered may exclude
 G4R_CAND_MAX = 2 ** 31 - 256  # most candidate positions of one g4r_score_candidates* call
+G4R_SCAN_CAND_MAX = 1024  # most candidates per row (k * oversample) of g4r_recommend_step_scan / g4r_recommend_sessions_scan
 LOSS_IDS = {'cross-entropy': 0, 'bpr-max': 1, 'top1-max': 2, 'bpr': 3, 'top1': 4, 'xe_logit': 5}
 ACT_IDS = {'linear': 0, 'relu': 1, 'tanh': 2, 'leaky': 3, 'elu': 4, 'selu': 5, 'softmax': 6, 'softmax_logit': 7}
 ADAPT_IDS = {'adagrad': 0, 'rmsprop': 1, 'adadelta': 2, 'adam': 3, None: 4}
@@ -45,7 +46,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_scan_table_release', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -102,6 +103,10 @@ def lib():
     L.g4r_recommend_step_filtered.argtypes = [vp, i32p, i32, i32p, i64, i32, i64p, i32p, C.POINTER(C.c_uint32), i32p, f32p]
     L.g4r_recommend_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i64p, i32p, C.POINTER(C.c_uint32), i32p,
                                          f32p, C.POINTER(f32p)]
+    L.g4r_recommend_step_scan.argtypes = [vp, i32p, i32, i32p, i64, i32, i32, i64p, i32p, C.POINTER(C.c_uint32), i32p, f32p]
+    L.g4r_recommend_sessions_scan.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i32, i64p, i32p, C.POINTER(C.c_uint32),
+                                              i32p, f32p, C.POINTER(f32p)]
+    L.g4r_scan_table_release.argtypes = [vp]
     L.g4r_score_candidates.argtypes = [vp, i32p, i32, i64p, i32p, i32, f32p, i32p]
     L.g4r_score_candidates_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i64p, i32p, i32, f32p, i32p, C.POINTER(f32p)]
     L.g4r_rank_targets.argtypes = [vp, i32p, i32, i64, i32, f32p]
@@ -278,6 +283,14 @@ class Model:
         _chk(lib().g4r_get_param(self.h, name.encode(), layer, _f32(a), a.size))
         return a
 
+    def scan_table(self):
+        """State of the bf16 shadow table of the two-stage top-k: (bytes held, valid, builds so far)."""
+        a = self.get_debug('scan_table', 3)
+        return int(a[0]), bool(a[1]), int(a[2])
+
+    def scan_table_release(self):
+        _chk(lib().g4r_scan_table_release(self.h))
+
     def get_debug(self, name, shape):
         a = np.empty(shape, dtype=np.float32)
         _chk(lib().g4r_get_debug(self.h, name.encode(), _f32(a), a.size))
@@ -385,10 +398,12 @@ class Model:
         _chk(lib().g4r_recommend_step(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k, _i32(cols), _f32(scores)))
         return cols, scores
 
-    def recommend_step_filtered(self, in_idx, item_idx=None, k=20, excl_offs=None, excl_items=None, excl_mask=None):
+    def recommend_step_filtered(self, in_idx, item_idx=None, k=20, excl_offs=None, excl_items=None, excl_mask=None, oversample=None):
         """recommend_step without the excluded items (g4r_recommend_step_filtered): row r never receives a candidate whose item index
         is in excl_items[excl_offs[r]:excl_offs[r + 1]] (excl_offs: rows + 1 offsets) or has its bit set in excl_mask (uint32 words,
-        bit i & 31 of word i >> 5).  None: no such exclusion.  Same return value as recommend_step."""
+        bit i & 31 of word i >> 5).  None: no such exclusion.  Same return value as recommend_step.
+        oversample (an integer >= 1): the two-stage selection instead (g4r_recommend_step_scan): a bf16 scan keeps k * oversample
+        candidates per row, which are re-ranked by their exact fp32 scores."""
         ii = np.ascontiguousarray(in_idx, dtype=np.int32)
         it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
         n_sel = self.cfg.n_items if it is None else len(it)
@@ -401,17 +416,20 @@ class Model:
             raise ValueError('excl_mask must hold ceil(n_items / 32) words')
         cols = np.empty((len(ii), k), dtype=np.int32)
         scores = np.empty((len(ii), k), dtype=np.float32)
-        _chk(lib().g4r_recommend_step_filtered(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k,
-                                               None if offs is None else _i64(offs), _i32(xi),
-                                               None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)), _i32(cols), _f32(scores)))
+        tail = (None if offs is None else _i64(offs), _i32(xi), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)),
+                _i32(cols), _f32(scores))
+        if oversample is None:
+            _chk(lib().g4r_recommend_step_filtered(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k, *tail))
+        else:
+            _chk(lib().g4r_recommend_step_scan(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k, int(oversample), *tail))
         return cols, scores
 
     def recommend_sessions(self, hist_offs, hist_items, item_idx=None, k=20, excl_offs=None, excl_items=None, excl_mask=None,
-                           hidden=None, return_hidden=False):
+                           hidden=None, return_hidden=False, oversample=None):
         """Top-k after replaying whole session histories, without the prediction state (g4r_recommend_sessions): session i is
         hist_items[hist_offs[i]:hist_offs[i + 1]] (item indices), started from hidden (a list of float32[n, layers[l]], None = zeros).
         Exclusions as in recommend_step_filtered, one list per session.  Returns (cols, scores), + the list of hidden states after
-        the last items with return_hidden=True."""
+        the last items with return_hidden=True.  oversample: as in recommend_step_filtered (g4r_recommend_sessions_scan)."""
         offs = np.ascontiguousarray(hist_offs, dtype=np.int64)
         hi = np.ascontiguousarray(hist_items, dtype=np.int32)
         n = len(offs) - 1
@@ -438,10 +456,13 @@ class Model:
         P = C.POINTER(C.c_float) * len(self.layers)
         cols = np.empty((n, k), dtype=np.int32)
         scores = np.empty((n, k), dtype=np.float32)
-        _chk(lib().g4r_recommend_sessions(self.h, _i64(offs), _i32(hi), n, None if h0 is None else P(*[_f32(h) for h in h0]),
-                                          None if it is None else _i32(it), n_sel, k, None if xo is None else _i64(xo), _i32(xi),
-                                          None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)), _i32(cols),
-                                          _f32(scores), None if hout is None else P(*[_f32(h) for h in hout])))
+        head = (self.h, _i64(offs), _i32(hi), n, None if h0 is None else P(*[_f32(h) for h in h0]), None if it is None else _i32(it), n_sel, k)
+        tail = (None if xo is None else _i64(xo), _i32(xi), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)), _i32(cols),
+                _f32(scores), None if hout is None else P(*[_f32(h) for h in hout]))
+        if oversample is None:
+            _chk(lib().g4r_recommend_sessions(*head, *tail))
+        else:
+            _chk(lib().g4r_recommend_sessions_scan(*head, int(oversample), *tail))
         return (cols, scores, hout) if return_hidden else (cols, scores)
 
     @staticmethod

@@ -16,6 +16,7 @@
 #include "g4r_eval_kernels.cuh"
 #include "g4r_topk_kernels.cuh"
 #include "g4r_cand_kernels.cuh"
+#include "g4r_scan_kernels.cuh"
 #include "g4r_sync_kernels.cuh"
 #include "g4r_micro_kernels.cuh"
 #include "g4r_wide_kernels.cuh"

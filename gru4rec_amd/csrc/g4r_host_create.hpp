@@ -347,6 +347,9 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
     HIPCHK(hipFuncSetAttribute((const void*)k_topk_stored, hipFuncAttributeMaxDynamicSharedMemorySize, big));
     HIPCHK(hipFuncSetAttribute((const void*)k_topk_fused_x, hipFuncAttributeMaxDynamicSharedMemorySize, big));
     HIPCHK(hipFuncSetAttribute((const void*)k_topk_stored_x, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+    HIPCHK(hipFuncSetAttribute((const void*)k_scan_bf16<2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+    HIPCHK(hipFuncSetAttribute((const void*)k_scan_bf16<4>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+    HIPCHK(hipFuncSetAttribute((const void*)k_scan_bf16<8>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
 #define G4R_LOSS_ATTR(L, S)                                                                                                    \
     if (!L) HIPCHK(hipFuncSetAttribute((const void*)k_loss_rows<false, S, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, big)); \
     HIPCHK(hipFuncSetAttribute((const void*)k_loss_rows<L, S, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, big))

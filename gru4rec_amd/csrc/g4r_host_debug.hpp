@@ -29,6 +29,11 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
         host[0] = (float)rows; host[1] = (float)bias; host[2] = m->defer_on ? 1.f : 0.f; host[3] = (float)(d.defer_mask + 1);
         return 0;
     }
+    else if (s == "scan_table") {      // (bytes the bf16 shadow table holds, 1 if it is valid, builds so far)
+        if (count < 3) return fail("count");
+        host[0] = (float)((double)m->s_tab_units * 16.0); host[1] = m->s_tab_valid ? 1.f : 0.f; host[2] = (float)m->s_tab_builds;
+        return 0;
+    }
     else if (s == "dhpart") { p = d.dhpart; n = (int64_t)d.ksplit * d.B * d.Dtop; }
     else if (s == "lossrow") { p = d.lossrow; n = d.B; }
     else if (s == "hd") { p = d.hd[l]; n = bd; }

@@ -166,6 +166,16 @@ struct g4r_model {
     int* c_tpos = nullptr;
     float* c_tscores = nullptr;
     int64_t c_offs_cap = 0, c_items_cap = 0, c_scores_cap = 0, c_work_cap = 0, c_topk_cap = 0, c_tpos_cap = 0, c_tscores_cap = 0;
+    // two-stage top-k (g4r_recommend_step_scan / g4r_recommend_sessions_scan): the bf16 shadow table of Wy in MFMA fragment order
+    // (g4r_scan_kernels.cuh), built on first use and again after anything that may have changed Wy (weights_changed); the
+    // candidates' columns and counts of one call or chunk; the host copy of k_score_cand's work items
+    uint4* s_tab = nullptr;
+    int64_t s_tab_units = 0, s_tab_builds = 0;
+    bool s_tab_valid = false;
+    int* s_cols = nullptr;
+    int* s_cnt = nullptr;
+    int64_t s_cols_cap = 0, s_cnt_cap = 0;
+    std::vector<int4> s_work;
     unsigned tie_ctr = 0;                       // evaluation step counter of the 'tiebreaking' noise stream
     // rccl
     ncclComm_t comm = nullptr;
@@ -196,6 +206,9 @@ struct g4r_model {
     float* d_dense[2] = {nullptr, nullptr};      // dense reconciliation buffers [n_items][sum of plane widths + 1] per table group (small catalogues)
     bool sync_on = false;
 };
+
+// every entry that may rewrite Wy calls this: the bf16 shadow table of the two-stage top-k is rebuilt on its next use
+static inline void weights_changed(g4r_model* m) { m->s_tab_valid = false; }
 
 template <class T>
 static int dalloc(g4r_model* m, T** p, size_t n, bool zero = true) {

@@ -40,6 +40,7 @@ int g4r_set_param(g4r_model* m, const char* name, int32_t layer, const float* ho
     if (locate(m, name, layer, &p, &n)) return -1;
     if (n != count) return fail(std::string("size mismatch for ") + name);
     HIPCHK(hipMemcpyAsync(p, host, n * sizeof(float), hipMemcpyHostToDevice, m->stream));
+    weights_changed(m);
     for (int g = 0; g < 2; ++g)      // a table set from the host is the new common base of its rows
         for (auto& pl : m->planes[g])
             if (pl.cur == p) HIPCHK(hipMemcpyAsync(pl.base, host, n * sizeof(float), hipMemcpyHostToDevice, m->stream));

@@ -267,9 +267,137 @@ static int topk_select(g4r_model* m, const float* hsrc, int32_t mrows, const int
     return 0;
 }
 
+// grow-only device buffer of one candidate call (stream-ordered: the stream is drained before the old one is freed)
+extern "C++" {
+template <class T>
+static int cand_reserve(g4r_model* m, T** p, int64_t* cap, int64_t need) {
+    if (need <= *cap) return 0;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    dfree(m, *p);
+    *p = nullptr;
+    *cap = 0;
+    if (dalloc(m, p, (size_t)need, false)) return -1;
+    *cap = need;
+    return 0;
+}
+}  // extern "C++"
+
+// ------------------------------------------------------------------------------------------------ two-stage top-k (bf16 scan)
+// the checks of scan = bf16 next to recommend_check's: *c = the candidates kept per row, min(number of candidates, k * oversample)
+static int scan_check(g4r_model* m, const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample, int32_t* c) {
+    const DevModel& d = m->dm;
+    if (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT)
+        return fail("the bf16 scan is not implemented for softmax / softmax_logit final activations (their exact values need the whole row)");
+    if (oversample < 1 || (int64_t)k * oversample > G4R_SCAN_CAND_MAX)
+        return fail("oversample must be at least 1 and k * oversample at most G4R_SCAN_CAND_MAX = " + std::to_string(G4R_SCAN_CAND_MAX));
+    if (d.Dtop > 512) return fail("the bf16 scan supports top layers of at most 512 units");
+    *c = (int32_t)std::min<int64_t>(item_idx ? n_sel : (int64_t)d.n_items, (int64_t)k * oversample);
+    return 0;
+}
+
+// k-chunks of 64 columns of the padded top layer (the instantiations of k_scan_bf16: 2, 4, 8)
+static int scan_nch(const DevModel& d) { return d.Dtop <= 128 ? 2 : d.Dtop <= 256 ? 4 : 8; }
+
+// the bf16 shadow table of Wy, (re)built on the stream when anything may have changed Wy since the last build
+static int scan_table_ensure(g4r_model* m) {
+    if (m->s_tab_valid) return 0;
+    const DevModel& d = m->dm;
+    const int KS = 4 * scan_nch(d);
+    const int64_t nblk = ((int64_t)d.n_items + 31) / 32, units = nblk * KS * 64;
+    if (units > m->s_tab_units) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        dfree(m, m->s_tab);
+        m->s_tab = nullptr;
+        m->s_tab_units = 0;
+        if (dalloc(m, &m->s_tab, (size_t)units, false)) return -1;
+        m->s_tab_units = units;
+    }
+    hipLaunchKernelGGL(k_wy_bf16, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, m->stream, (const DevModel*)m->d_dm, m->s_tab,
+                       (long long)nblk, KS);
+    HIPCHK(hipGetLastError());
+    m->s_tab_valid = true;
+    ++m->s_tab_builds;
+    return 0;
+}
+
+int g4r_scan_table_release(g4r_model* m) {
+    if (!m) return fail("null model");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    dfree(m, m->s_tab);
+    m->s_tab = nullptr;
+    m->s_tab_units = 0;
+    m->s_tab_valid = false;
+    return 0;
+}
+
+// topk_select's two-stage twin (element-wise final activations only): rows [0, mrows) of hsrc -> p_tcols / p_tscores, enqueued only,
+// no host synchronisation between the stages.  Stage 1: k_scan_bf16 keeps c candidates per row and range, k_scan_merge the row's c.
+// Stage 2: k_score_cand scores them (fp32, bit-identical to g4r_predict_step), k_scan_pack + k_topk_merge return the k best.
+static int topk_select_scan(g4r_model* m, const float* hsrc, int32_t mrows, const int* d_items, int64_t n_sel, int32_t k, int32_t c,
+                            const TkExcl* ex) {
+    if (scan_table_ensure(m)) return -1;
+    const int row_blocks = cdiv(mrows, SC_BM);
+    const int64_t tiles = (n_sel + SCN_TN - 1) / SCN_TN;
+    const int64_t R0 = std::min<int64_t>(std::max(1, m->n_cu / row_blocks), tiles);
+    const int tpr = (int)((tiles + R0 - 1) / R0);
+    const int R = (int)((tiles + tpr - 1) / tpr);
+    const int nl = (c + k - 1) / k, L = nl * k;
+    const int64_t need = (int64_t)mrows * R * c, nout = (int64_t)mrows * k, P = (int64_t)mrows * c;
+    if (mrows > 65535) return fail("the bf16 scan takes at most 65535 rows per call");
+    if (need > m->p_topk_cap || nout > m->p_tout_cap) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        if (need > m->p_topk_cap) {
+            dfree(m, m->p_topk);
+            m->p_topk = nullptr;
+            m->p_topk_cap = 0;
+            if (dalloc(m, &m->p_topk, (size_t)need, false)) return -1;
+            m->p_topk_cap = need;
+        }
+        if (nout > m->p_tout_cap) {
+            dfree(m, m->p_tcols); dfree(m, m->p_tscores);
+            m->p_tcols = nullptr; m->p_tscores = nullptr;
+            m->p_tout_cap = 0;
+            if (dalloc(m, &m->p_tcols, (size_t)nout, false) || dalloc(m, &m->p_tscores, (size_t)nout, false)) return -1;
+            m->p_tout_cap = nout;
+        }
+    }
+    // k_score_cand's work items depend on c and the row count only: row r's list is positions [r c, (r + 1) c)
+    m->s_work.clear();
+    for (int r = 0; r < mrows; ++r)
+        for (int p = 0; p < c; p += CS_SLICE) m->s_work.push_back(make_int4(r, r * c + p, r * c + std::min(p + CS_SLICE, (int)c), r * c));
+    if (cand_reserve(m, &m->c_items, &m->c_items_cap, P) || cand_reserve(m, &m->c_scores, &m->c_scores_cap, P) ||
+        cand_reserve(m, &m->c_work, &m->c_work_cap, (int64_t)m->s_work.size()) || cand_reserve(m, &m->c_topk, &m->c_topk_cap, (int64_t)mrows * L) ||
+        cand_reserve(m, &m->s_cols, &m->s_cols_cap, P) || cand_reserve(m, &m->s_cnt, &m->s_cnt_cap, (int64_t)mrows))
+        return -1;
+    HIPCHK(hipMemcpyAsync(m->c_work, m->s_work.data(), m->s_work.size() * sizeof(int4), hipMemcpyHostToDevice, m->stream));
+    const dim3 grid(R, row_blocks);
+    const TkExcl x = ex ? *ex : TkExcl{nullptr, nullptr, nullptr};
+#define SCAN_LAUNCH(N) hipLaunchKernelGGL(k_scan_bf16<N>, grid, dim3(256), SCN_SMEM, m->stream, (const DevModel*)m->d_dm, hsrc, (int)mrows, d_items, \
+                                          (long long)n_sel, (const uint4*)m->s_tab, (int)c, tpr, m->p_topk, x)
+    switch (scan_nch(m->dm)) {
+        case 2: SCAN_LAUNCH(2); break;
+        case 4: SCAN_LAUNCH(4); break;
+        default: SCAN_LAUNCH(8); break;
+    }
+#undef SCAN_LAUNCH
+    hipLaunchKernelGGL(k_scan_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->p_topk, R, (int)c, d_items, m->s_cols, m->c_items,
+                       m->c_scores, m->s_cnt);
+#if !(defined(G4R_MUTATE) && G4R_MUTATE == 12)      // test build 12: stage 2 ranks by the approximate scores k_scan_merge left there
+    hipLaunchKernelGGL(k_score_cand, dim3((unsigned)m->s_work.size()), dim3(256), 0, m->stream, (const DevModel*)m->d_dm, hsrc,
+                       (const int*)m->c_items, (const int4*)m->c_work, m->c_scores, 1);
+#endif
+    hipLaunchKernelGGL(k_scan_pack, dim3(cdiv(L, 256), mrows), dim3(256), 0, m->stream, (const float*)m->c_scores, (const int*)m->s_cols,
+                       (const int*)m->s_cnt, (int)c, L, m->c_topk);
+    hipLaunchKernelGGL(k_topk_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->c_topk, nl, (int)k, m->p_tcols, m->p_tscores);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // GRU step + selection of a checked call whose inputs predict_inputs has uploaded; ex (device exclusions) NULL: the unfiltered kernels
+// scan_c > 0: the two-stage selection with scan_c candidates per row (scan_check has refused softmax)
 static int recommend_run(g4r_model* m, int32_t mrows, const int32_t* item_idx, int64_t n_sel, int32_t k, const TkExcl* ex,
-                         int32_t* out_cols, float* out_scores) {
+                         int32_t* out_cols, float* out_scores, int32_t scan_c = 0) {
     DevModel& d = m->dm;
     const int* d_items = item_idx ? (const int*)m->p_items : (const int*)nullptr;
     const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
@@ -280,7 +408,9 @@ static int recommend_run(g4r_model* m, int32_t mrows, const int32_t* item_idx, i
     } else {
         predict_gru(m, m->p_in, mrows);
     }
-    if (topk_select(m, (const float*)m->phout[d.n_layers - 1], mrows, d_items, n_sel, k, ex, (const float*)m->p_scores, m->p_ldo)) return -1;
+    if (scan_c > 0) {
+        if (topk_select_scan(m, (const float*)m->phout[d.n_layers - 1], mrows, d_items, n_sel, k, scan_c, ex)) return -1;
+    } else if (topk_select(m, (const float*)m->phout[d.n_layers - 1], mrows, d_items, n_sel, k, ex, (const float*)m->p_scores, m->p_ldo)) return -1;
     const int64_t nout = (int64_t)mrows * k;
     HIPCHK(hipMemcpyAsync(out_cols, m->p_tcols, nout * sizeof(int), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipMemcpyAsync(out_scores, m->p_tscores, nout * sizeof(float), hipMemcpyDeviceToHost, m->stream));
@@ -411,6 +541,21 @@ int g4r_recommend_step_filtered(g4r_model* m, const int32_t* in_idx, int32_t mro
     return recommend_run(m, mrows, item_idx, n_sel, k, &ex, out_cols, out_scores);
 }
 
+int g4r_recommend_step_scan(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel, int32_t k,
+                            int32_t oversample, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
+                            int32_t* out_cols, float* out_scores) {
+    int32_t c = 0;
+    if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores) || scan_check(m, item_idx, n_sel, k, oversample, &c)) return -1;
+    if (predict_inputs(m, in_idx, mrows, item_idx, &n_sel)) return -1;      // (uploads only: the state advances in recommend_run)
+    if (!excl_offs && !excl_mask) return recommend_run(m, mrows, item_idx, n_sel, k, nullptr, out_cols, out_scores, c);
+    std::vector<long long> offs;
+    std::vector<int32_t> items;
+    if (excl_pack(m, mrows, item_idx, n_sel, k, excl_offs, excl_items, excl_mask, offs, items)) return -1;
+    TkExcl ex;
+    if (excl_upload(m, excl_offs != nullptr, offs, items, excl_mask, &ex)) return -1;
+    return recommend_run(m, mrows, item_idx, n_sel, k, &ex, out_cols, out_scores, c);
+}
+
 // ------------------------------------------------------------------------------------------------ stateless session replay
 // Rows per chunk of g4r_recommend_sessions: its score matrix (softmax / softmax_logit) is then never larger than g4r_recommend_step's
 // at 512 rows.  G4R_SESSIONS_CHUNK > 0 (read per call) forces a smaller chunk: tests show the results do not depend on it.
@@ -532,11 +677,15 @@ static int replay_chunks(g4r_model* m, const int64_t* hist_offs, const int32_t* 
 }
 }  // extern "C++"
 
-int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
-                           const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs, const int32_t* excl_items,
-                           const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, float* const* out_hidden) {
+// g4r_recommend_sessions (oversample = 0: the exact selection) and g4r_recommend_sessions_scan (oversample >= 1)
+static int recommend_sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                                  const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample, const int64_t* excl_offs,
+                                  const int32_t* excl_items, const uint32_t* excl_mask, int32_t* out_cols, float* out_scores,
+                                  float* const* out_hidden) {
     // ---- every check before any device work (nothing here has state to advance, but a refused call launches nothing)
     if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores)) return -1;
+    int32_t scan_c = 0;
+    if (oversample && scan_check(m, item_idx, n_sel, k, oversample, &scan_c)) return -1;
     HIPCHK(hipSetDevice(m->cfg.device));
     if (replay_check(m, hist_offs, hist_items, n, h0, out_hidden)) return -1;
     const DevModel& d = m->dm;
@@ -591,7 +740,9 @@ int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t
                 }
             if (excl_upload(m, excl_offs != nullptr, coffs, citems, excl_mask, &ex)) return -1;
         }
-        if (topk_select(m, hsrc, Cc, d_items, n_sel, k, excl ? &ex : nullptr, (const float*)m->r_scores, ldo)) return -1;
+        if (scan_c > 0) {
+            if (topk_select_scan(m, hsrc, Cc, d_items, n_sel, k, scan_c, excl ? &ex : nullptr)) return -1;
+        } else if (topk_select(m, hsrc, Cc, d_items, n_sel, k, excl ? &ex : nullptr, (const float*)m->r_scores, ldo)) return -1;
         HIPCHK(hipMemcpyAsync(tcols.data(), m->p_tcols, (size_t)Cc * k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
         HIPCHK(hipMemcpyAsync(tscores.data(), m->p_tscores, (size_t)Cc * k * sizeof(float), hipMemcpyDeviceToHost, m->stream));
         return 0;
@@ -606,22 +757,23 @@ int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t
     return replay_chunks(m, hist_offs, hist_items, n, C, h0, out_hidden, score, done);
 }
 
-// ------------------------------------------------------------------------------------------------ per-row candidate lists
-// grow-only device buffer of one candidate call (stream-ordered: the stream is drained before the old one is freed)
-extern "C++" {
-template <class T>
-static int cand_reserve(g4r_model* m, T** p, int64_t* cap, int64_t need) {
-    if (need <= *cap) return 0;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    dfree(m, *p);
-    *p = nullptr;
-    *cap = 0;
-    if (dalloc(m, p, (size_t)need, false)) return -1;
-    *cap = need;
-    return 0;
+int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                           const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs, const int32_t* excl_items,
+                           const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, float* const* out_hidden) {
+    return recommend_sessions_run(m, hist_offs, hist_items, n, h0, item_idx, n_sel, k, 0, excl_offs, excl_items, excl_mask, out_cols,
+                                  out_scores, out_hidden);
 }
-}  // extern "C++"
 
+int g4r_recommend_sessions_scan(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                                const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample, const int64_t* excl_offs,
+                                const int32_t* excl_items, const uint32_t* excl_mask, int32_t* out_cols, float* out_scores,
+                                float* const* out_hidden) {
+    if (oversample < 1) return fail("oversample must be at least 1 and k * oversample at most G4R_SCAN_CAND_MAX = " + std::to_string(G4R_SCAN_CAND_MAX));
+    return recommend_sessions_run(m, hist_offs, hist_items, n, h0, item_idx, n_sel, k, oversample, excl_offs, excl_items, excl_mask,
+                                  out_cols, out_scores, out_hidden);
+}
+
+// ------------------------------------------------------------------------------------------------ per-row candidate lists
 // the checks of the candidate lists of g4r_score_candidates*: rows >= 1 non-empty lists, items in range, at most G4R_CAND_MAX
 // positions in all, 0 <= k <= G4R_TOPK_MAX and every list at least k long when k > 0
 static int cand_check(g4r_model* m, int32_t rows, const int64_t* cand_offs, const int32_t* cand_items, int32_t k, float* out_scores,

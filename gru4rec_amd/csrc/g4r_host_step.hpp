@@ -436,6 +436,7 @@ int g4r_train_steps(g4r_model* m, int64_t t0, int64_t n_steps) {
     if (!m->d_in) return fail("no plan uploaded");
     if (t0 < 0 || n_steps < 0 || t0 + n_steps > m->T) return fail("step range outside the plan");
     if (m->dm.ns > 0 && !m->have_pop && !m->store_frozen) return fail("negative sampling needs g4r_set_popularity first");
+    weights_changed(m);      // (deferred row updates are flushed inside this call: they are covered too)
     if (m->defer_on) {
         // k_defer_scan keys its newest-use table by the low 32 bits of the global step (signed atomicMax): refuse before they wrap
         // (27 h of training at 22 K steps/s on one handle; g4r_set_step_counters rebases the step and clears the table)
@@ -573,6 +574,7 @@ int g4r_virtual_train_steps(g4r_model* const* ms, int32_t n, int64_t t0, int64_t
         if (m->dm.ns > 0 && !m->have_pop && !m->store_frozen) return fail("negative sampling needs g4r_set_popularity first");
         m->virtual_ranks = true;
     }
+    for (int q = 0; q < n; ++q) weights_changed(ms[q]);
     HIPCHK(hipSetDevice(ms[0]->cfg.device));
     g4r_model* m0 = ms[0];
     const int cnt = m0->dm.dense_count;

@@ -163,6 +163,7 @@ int g4r_sync_import(g4r_model* m, int32_t group, int32_t nparts, const int64_t* 
     if (!m || group < 0 || group > 1 || nparts < 1 || !counts || !ids || !rows) return fail("bad argument");
     if (!m->sync_on) return fail("g4r_sync_enable first");
     HIPCHK(hipSetDevice(m->cfg.device));
+    weights_changed(m);
     std::vector<int> loc;
     if (sync_local_ids(m, group, loc)) return -1;
     const size_t I = m->dm.n_items;
@@ -230,6 +231,7 @@ int g4r_virtual_sync_dense(g4r_model* const* ms, int32_t n) {
     if (!ms || n < 1 || n > 16) return fail("virtual ranks: 1..16 handles");
     for (int q = 0; q < n; ++q) if (!ms[q] || !ms[q]->sync_on || !ms[q]->d_dense[0]) return fail("virtual dense sync: g4r_sync_enable first (and a table small enough for the dense form)");
     HIPCHK(hipSetDevice(ms[0]->cfg.device));
+    for (int q = 0; q < n; ++q) weights_changed(ms[q]);
     for (int g = 0; g < 2; ++g) {
         if (ms[0]->planes[g].empty()) continue;
         if (!ms[0]->d_dense[g]) return fail("virtual dense sync: table group too large for the dense form");
@@ -292,6 +294,7 @@ int g4r_comm_sync_sparse(g4r_model* m) {
     if (!m->comm_ready) return fail("g4r_comm_init first");
     if (!m->sync_on) return fail("g4r_sync_enable first");
     HIPCHK(hipSetDevice(m->cfg.device));
+    weights_changed(m);
     DevModel& d = m->dm;
     int nr = 1;
     NCCLCHK(ncclCommCount(m->comm, &nr));

@@ -878,8 +878,25 @@ class GRU4Rec:
         preds = m.predict_step(in_idxs).T
         return pd.DataFrame(data=preds, index=self.itemidmap.index)
 
+    def _scan_oversample(self, scan, oversample, k):
+        """The checks of scan / oversample (recommend_next_batch, recommend_sessions), after the k check: None for scan='fp32', the
+        checked oversample for scan='bf16'."""
+        if scan not in ('fp32', 'bf16'):
+            raise ValueError("scan = %r: it must be 'fp32' or 'bf16'" % (scan,))
+        cmax = _native.G4R_SCAN_CAND_MAX
+        if isinstance(oversample, bool) or int(oversample) != oversample or oversample < 1:
+            raise ValueError('oversample = %r: it must be an integer in [1, %d // k]' % (oversample, cmax))
+        if scan == 'fp32':
+            return None
+        if int(k) * int(oversample) > cmax:
+            raise ValueError('k * oversample = %d * %d: it must be at most G4R_SCAN_CAND_MAX = %d' % (k, oversample, cmax))
+        if self.final_act.startswith('softmax'):
+            raise NotImplementedError("scan='bf16' is not implemented for final_act=%r: a softmax value needs the whole row's maximum "
+                                      "and sum, which is the fp32 scan again" % self.final_act)
+        return int(oversample)
+
     def recommend_next_batch(self, session_ids, input_item_ids, k=20, predict_for_item_ids=None, batch=100,
-                             exclude_seen=False, exclude=None, exclude_per_row=None):
+                             exclude_seen=False, exclude=None, exclude_per_row=None, scan='fp32', oversample=8):
         """Top-k next items of every session: (item_ids[len(session_ids), k], scores[len(session_ids), k] float32).
         Not in the reference.  Row r holds the k largest entries of column r of what predict_next_batch would return for the same
         call (score descending, equal scores by the lower candidate position, NaN last), the scores bit-identical to it; the
@@ -895,19 +912,33 @@ class GRU4Rec:
         The rest keep their order and their predict_next_batch scores: softmax / softmax_logit scores are NOT renormalised over them.
         A call is checked before anything changes (hidden state, current_session, seen-history): an unknown item id raises
         KeyError; a row with more than G4R_EXCLUDE_MAX = 1024 distinct items in exclude_per_row plus the items seen, or with fewer
-        than k eligible candidate positions (duplicates count), raises ValueError."""
+        than k eligible candidate positions (duplicates count), raises ValueError.
+
+        scan='bf16' (opt-in; 'fp32', the default, is the exact selection above) is a two-stage selection for LARGE catalogues
+        (millions of items, where the fp32 scoring of every item dominates the call; on catalogues of tens of thousands of items
+        the exact call is already bound by its merge and the option gains nothing).  A scan in bf16 (h and Wy rounded to bf16, fp32
+        accumulation, bias and activation) keeps c = min(number of candidates, k * oversample) candidates per row, exclusions
+        applied; those are scored again in fp32 and the k best returned.  Every returned score still is predict_next_batch's, bit
+        for bit, and the order and tie rule are unchanged; only WHICH items were considered is approximate: an item whose bf16 score
+        is not among the row's c best cannot appear.  With c >= the row's eligible candidates the result equals scan='fp32'
+        exactly.  oversample is an integer >= 1 with k * oversample <= G4R_SCAN_CAND_MAX = 1024 (ValueError otherwise); final_act
+        softmax / softmax_logit raise NotImplementedError (their values need the whole row: out of scope).  The hidden state
+        advances exactly as with scan='fp32'.  The bf16 copy of Wy is built on the first such call and after every change of Wy."""
         if self.error_during_train:
             raise Exception
         n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
         if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
             raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        over = self._scan_oversample(scan, oversample, k)
         plan = self._predict_plan(session_ids, input_item_ids, batch)
         iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
         filtered = exclude_seen or exclude is not None or exclude_per_row is not None
         if filtered:
             offs, items, mask = self._exclusions(plan, int(k), iidx, exclude_seen, exclude, exclude_per_row)
         m, in_idxs = self._predict_rows(session_ids, input_item_ids, batch, plan=plan)
-        if filtered:
+        if over is not None:
+            cols, scores = m.recommend_step_filtered(in_idxs, iidx, int(k), *((offs, items, mask) if filtered else ()), oversample=over)
+        elif filtered:
             cols, scores = m.recommend_step_filtered(in_idxs, iidx, int(k), offs, items, mask)
         else:
             cols, scores = m.recommend_step(in_idxs, iidx, int(k))
@@ -939,7 +970,7 @@ class GRU4Rec:
         return N, lens, offs, hidx, h0
 
     def recommend_sessions(self, histories, k=20, predict_for_item_ids=None, exclude_history=False, exclude=None, exclude_per_row=None,
-                           hidden=None, return_hidden=False):
+                           hidden=None, return_hidden=False, scan='fp32', oversample=8):
         """Top-k next items of N whole sessions in one stateless call: (item_ids[N, k], scores[N, k] float32), plus the new hidden
         state with return_hidden=True.  Not in the reference.
 
@@ -950,6 +981,8 @@ class GRU4Rec:
           exclude_history  row i never receives an item of histories[i].  Items seen before a supplied `hidden` are unknown to the
                            call: pass them in exclude_per_row.
           predict_for_item_ids, exclude, exclude_per_row, k: as in recommend_next_batch (exclude_per_row: N lists).
+          scan, oversample as in recommend_next_batch: scan='bf16' is the two-stage selection (bf16 scan, exact fp32 re-rank); the
+                           replay, and so the returned hidden state, is the same either way.
 
         Row i equals, items and score bits, what recommend_next_batch returns for a session whose first T - 1 items went through
         predict_next_batch from a fresh prediction state and whose last item is the recommend_next_batch input (exclude_history as
@@ -963,6 +996,7 @@ class GRU4Rec:
         n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
         if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
             raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        over = self._scan_oversample(scan, oversample, k)
         N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
         iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
         xoffs = xitems = mask = None
@@ -970,7 +1004,10 @@ class GRU4Rec:
             hist_rows = (np.repeat(np.arange(N), lens), hidx) if exclude_history else None
             xoffs, xitems, mask = self._pack_exclusions(N, int(k), iidx, hist_rows, 'the history', exclude, exclude_per_row)
         m = self._ensure_model()
-        out = m.recommend_sessions(offs, hidx, iidx, int(k), xoffs, xitems, mask, hidden=h0, return_hidden=return_hidden)
+        if over is None:
+            out = m.recommend_sessions(offs, hidx, iidx, int(k), xoffs, xitems, mask, hidden=h0, return_hidden=return_hidden)
+        else:
+            out = m.recommend_sessions(offs, hidx, iidx, int(k), xoffs, xitems, mask, hidden=h0, return_hidden=return_hidden, oversample=over)
         cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
         if not return_hidden:
             return cand[out[0]], out[1]

@@ -202,6 +202,34 @@ int g4r_recommend_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t
                            const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs, const int32_t* excl_items,
                            const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, float* const* out_hidden);
 
+/* not in the reference: two-stage top-k for large catalogues, the twins of g4r_recommend_step_filtered / g4r_recommend_sessions
+ * (same arguments, same checks, same effect on the prediction state; excl_offs and excl_mask may both be NULL) with one more
+ * argument, oversample >= 1.  Stage 1 scans the candidates in bf16 and keeps c = min(number of candidates, k * oversample) of them
+ * per row, k * oversample <= G4R_SCAN_CAND_MAX; stage 2 scores those in fp32 and returns the k best.
+ *   approximate score of (row, column): h and the item's Wy row rounded to bf16 (round to nearest even), the products summed in
+ *     fp32 in any order, + By[item] in fp32, then the element-wise final activation in fp32;
+ *   candidates of a row: the c best approximate scores among the row's eligible columns, in the order of g4r_recommend_step (score
+ *     descending, equal scores by the lower column, NaN last).  Exclusions apply here, so an excluded item never reaches stage 2; a
+ *     row with fewer than c eligible columns keeps all it has;
+ *   result: every candidate is scored as g4r_predict_step scores it (bit-identical), and the k best by (exact score descending,
+ *     lower column first, NaN last) are returned.
+ * So every returned score is g4r_predict_step's bit pattern for that item and the order is g4r_recommend_step's; the only
+ * approximation is which items reach stage 2, and with c >= the row's eligible columns the result IS the exact call's, bit for bit.
+ * softmax / softmax_logit final activations are refused (their values need the whole row: the fp32 scan again); so are top layers
+ * wider than 512.  The bf16 copy of Wy (a "shadow table", n_items x the top layer padded to 128 / 256 / 512, 2 bytes each) is built
+ * on the first call and rebuilt on the first call after anything that may have changed Wy (g4r_train_steps,
+ * g4r_virtual_train_steps, g4r_set_param, g4r_comm_sync_sparse, g4r_sync_import, g4r_virtual_sync_dense).  g4r_scan_table_release
+ * frees it (the next scan rebuilds it); g4r_get_debug "scan_table" -> (bytes held, 1 if valid, builds so far); g4r_destroy frees it. */
+#define G4R_SCAN_CAND_MAX 1024
+int g4r_recommend_step_scan(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel, int32_t k,
+                            int32_t oversample, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
+                            int32_t* out_cols, float* out_scores);
+int g4r_recommend_sessions_scan(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                                const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample, const int64_t* excl_offs,
+                                const int32_t* excl_items, const uint32_t* excl_mask, int32_t* out_cols, float* out_scores,
+                                float* const* out_hidden);
+int g4r_scan_table_release(g4r_model* m);
+
 /* not in the reference: scores of per-row candidate lists (the re-ranking stage behind a retrieval stage).  Row r's list is the
  * item indices cand_items[cand_offs[r] .. cand_offs[r + 1]) (at least one; cand_offs rises strictly; duplicates allowed, every
  * position is scored), at most G4R_CAND_MAX positions in all.  g4r_score_candidates advances the prediction state exactly as
