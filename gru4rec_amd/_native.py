@@ -46,7 +46,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_scan_table_release', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_scan_table_release', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -112,6 +112,8 @@ def lib():
     L.g4r_rank_targets.argtypes = [vp, i32p, i32, i64, i32, f32p]
     L.g4r_evaluate.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32p, i32, i32,
                                C.POINTER(C.c_double), C.POINTER(C.c_double), i64p]
+    L.g4r_recommend_events.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32, i64p, i64, i32,
+                                       C.POINTER(C.c_uint32), i64p, i32p, i32p, i64, i32p, i32p, i32p, f32p, f32p, f32p]
     L.g4r_comm_unique_id.argtypes = [C.c_char_p]
     L.g4r_comm_init.argtypes = [vp, C.c_char_p, i32, i32]
     L.g4r_comm_sync_sparse.argtypes = [vp]
@@ -542,6 +544,48 @@ class Model:
                                 _i32(cuts), len(cuts), RANK_MODES[mode], rec.ctypes.data_as(C.POINTER(C.c_double)),
                                 mrr.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
         return rec, mrr, int(n.value)
+
+    def recommend_events(self, plan, batch, items, mode, slot, n_slots, k, excl_mask=None, seen=None, want_lists=True):
+        """Top-k list, target rank and target score of every event of an evaluation plan in one call (g4r_recommend_events).
+        slot: int64[T, batch], the output row of the event at (step, row), -1 for padding.  seen: None or the dict of
+        evaluation.seen_tables plus 'sess' / 'pos' int32[T, batch].  Returns (items int32[n_slots, k], scores float32[n_slots, k],
+        rank float32[n_slots], target_score float32[n_slots]); items / scores are None with want_lists=False."""
+        T = int(plan['T'])
+        it = None if items is None else np.ascontiguousarray(items, dtype=np.int32)
+        nc = int(plan.get('n_compact', 0))
+        cs = np.ascontiguousarray(plan['compact_steps'], dtype=np.int64) if nc else np.zeros(1, dtype=np.int64)
+        cm = np.ascontiguousarray(plan['compact_maps'], dtype=np.int32) if nc else np.zeros((1, batch), dtype=np.int32)
+        arr = {key: np.ascontiguousarray(plan[key]) for key in ('in_idx', 'out_idx', 'reset', 'M')}
+        sl = np.ascontiguousarray(slot, dtype=np.int64)
+        if sl.size != T * batch:
+            raise ValueError('slot must hold T * batch = %d entries' % (T * batch))
+        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
+        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
+            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
+        u32p = C.POINTER(C.c_uint32)
+        if seen is None:
+            st = (None, None, None, 0, None, None)
+            keep = ()
+        else:
+            keep = (np.ascontiguousarray(seen['offs'], dtype=np.int64), np.ascontiguousarray(seen['items'], dtype=np.int32),
+                    np.ascontiguousarray(seen['first'], dtype=np.int32), np.ascontiguousarray(seen['sess'], dtype=np.int32),
+                    np.ascontiguousarray(seen['pos'], dtype=np.int32))
+            if keep[3].size != T * batch or keep[4].size != T * batch or len(keep[1]) != len(keep[2]) or keep[0][-1] > len(keep[1]):
+                raise ValueError('seen tables: sess / pos must hold T * batch entries, items / first one entry per offset')
+            st = (_i64(keep[0]), _i32(keep[1]), _i32(keep[2]), len(keep[0]) - 1, _i32(keep[3]), _i32(keep[4]))
+        oi = np.empty((n_slots, k), dtype=np.int32) if want_lists else None
+        os_ = np.empty((n_slots, k), dtype=np.float32) if want_lists else None
+        rk = np.empty(n_slots, dtype=np.float32)
+        ts = np.empty(n_slots, dtype=np.float32)
+        _chk(lib().g4r_recommend_events(self.h, _i32(arr['in_idx']), _i32(arr['out_idx']), _u8(arr['reset']), _i32(arr['M']), T, batch,
+                                        _i64(cs), _i32(cm), nc, None if it is None else _i32(it), 0 if it is None else len(it),
+                                        RANK_MODES[mode], _i64(sl), n_slots, k, None if mask is None else mask.ctypes.data_as(u32p), *st,
+                                        None if oi is None else _i32(oi), None if os_ is None else _f32(os_), _f32(rk), _f32(ts)))
+        return oi, os_, rk, ts
+
+    def events_launches(self):
+        """(steps, launches that scan the candidate columns, all launches, pieces) of the last recommend_events call."""
+        return tuple(int(x) for x in self.get_debug('events_launches', 4))
 
     def comm_init(self, unique_id, nranks, rank):
         _chk(lib().g4r_comm_init(self.h, unique_id, nranks, rank))

@@ -34,6 +34,11 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
         host[0] = (float)((double)m->s_tab_units * 16.0); host[1] = m->s_tab_valid ? 1.f : 0.f; host[2] = (float)m->s_tab_builds;
         return 0;
     }
+    else if (s == "events_launches") {      // the last g4r_recommend_events call: (steps, launches that scan the candidate columns, all launches, pieces)
+        if (count < 4) return fail("count");
+        host[0] = (float)m->ev_steps; host[1] = (float)m->ev_scans; host[2] = (float)m->ev_launches; host[3] = (float)m->ev_pieces;
+        return 0;
+    }
     else if (s == "dhpart") { p = d.dhpart; n = (int64_t)d.ksplit * d.B * d.Dtop; }
     else if (s == "lossrow") { p = d.lossrow; n = d.B; }
     else if (s == "hd") { p = d.hd[l]; n = bd; }

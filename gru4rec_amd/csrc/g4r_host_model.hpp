@@ -177,6 +177,9 @@ struct g4r_model {
     int64_t s_cols_cap = 0, s_cnt_cap = 0;
     std::vector<int4> s_work;
     unsigned tie_ctr = 0;                       // evaluation step counter of the 'tiebreaking' noise stream
+    // the last g4r_recommend_events call (g4r_get_debug "events_launches"): its steps, the launches whose grid spans the candidate
+    // columns, all its launches, the pieces its lists came back in
+    int64_t ev_steps = 0, ev_scans = 0, ev_launches = 0, ev_pieces = 0;
     // rccl
     ncclComm_t comm = nullptr;
     bool comm_ready = false;
@@ -233,6 +236,9 @@ static constexpr auto k_topk_fused = k_topk_range<false, false>;         // scor
 static constexpr auto k_topk_stored = k_topk_range<true, false>;         // selection over p_scores (softmax / softmax_logit)
 static constexpr auto k_topk_fused_x = k_topk_range<false, true, TkExcl>;        // the same two with exclusions (g4r_recommend_step_filtered)
 static constexpr auto k_topk_stored_x = k_topk_range<true, true, TkExcl>;
+static constexpr auto k_topk_rank = k_topk_range<false, false, TkEvents>;        // g4r_recommend_events: k_topk_fused + the rank counters of k_score_count
+static constexpr auto k_topk_rank_x = k_topk_range<false, true, TkEvents>;       // + the session-list / mask exclusions
+static constexpr auto k_topk_stored_ev = k_topk_range<true, true, TkEvents>;     // softmax / softmax_logit with those exclusions (no counters)
 
 static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 // dynamic LDS of the tile-GEMM kernels (g4r_gemm.cuh)

@@ -2,6 +2,9 @@
 //   k_topk_fused   scores of a column range (the k_score_all chain) -> the range's k best per row, nothing stored
 //   k_topk_stored  the same selection over a score matrix already in memory (softmax / softmax_logit final activations)
 //   k_topk_merge   the ranges' lists of one row -> the row's k best (int32 column, float score)
+//   k_topk_rank    k_topk_fused for g4r_recommend_events: the same scan also counts, per row, the columns whose score is greater
+//                  than / equal to the row's target score (the counters of k_score_all<.., COUNT = true>, finished by k_rank_counts)
+//   k_events_merge k_topk_merge writing its row, the row's rank and target score at the event's place in the call's output
 // The EXCL = true instantiations of k_topk_range (behind g4r_recommend_step_filtered) drop excluded items where a survivor queue is
 // merged into its row's list (topk_merge_row): a global bit mask over item indices and a sorted per-row list (at most
 // G4R_EXCLUDE_MAX items).  The EXCL = false instantiations are the unfiltered kernels, instruction for instruction.
@@ -40,16 +43,37 @@ __device__ __forceinline__ unsigned long long topk_key(uint2 e) { return e.y == 
 #define TK_SEL_X (SC_BM * 12)           // EXCL: + every row's list start (8 B) and length (4 B), staged once per workgroup
 #define TK_SMEM_STORED_X (TK_SMEM_STORED + TK_SEL_X + 4 * (TK_SCRATCH_WAVE_X - TK_SCRATCH_WAVE))
 #define TK_SMEM_FUSED_X (TK_SMEM_FUSED + TK_SEL_X)
+#define TK_SEL_EV (SC_BM * 4)           // TkEvents with EXCL: + every row's position in its session
 // LDS budget (160 KiB per CU): k_topk_stored 77,824 B, 95,744 B with EXCL; k_topk_fused 150,912 B, 152,448 B with EXCL, the four
 // waves' merge scratch (4 x 2,560 B, 4 x 6,656 B = 26,624 B with EXCL) aliasing its 66,560 B A tile
 static_assert(4 * TK_SCRATCH_WAVE_X <= SC_BM * (SC_KC + 2) * 4, "the EXCL merge scratch must fit in the fused kernel's A tile");
-static_assert(TK_SMEM_STORED_X <= 156 * 1024 && TK_SMEM_FUSED_X <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
+static_assert(TK_SMEM_STORED_X + TK_SEL_EV <= 156 * 1024 && TK_SMEM_FUSED_X + TK_SEL_EV <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
 
 // Exclusions of one g4r_recommend_step_filtered call (device pointers, NULL = none): row r's sorted, duplicate-free item indices are
 // items[offs[r] .. offs[r + 1]), at most G4R_EXCLUDE_MAX of them; bit (i & 31) of mask[i >> 5] excludes item index i in every row.
 struct TkExcl { const long long* offs; const int* items; const unsigned* mask; };
 __device__ __forceinline__ TkExcl tk_excl() { return TkExcl{}; }
 __device__ __forceinline__ TkExcl tk_excl(TkExcl e) { return e; }
+
+// The trailing argument of the g4r_recommend_events instantiations (k_topk_range<.., .., TkEvents>), one evaluation step's rows.
+// Rank counters (fused form only): tscore[r] is row r's target score (k_score_cand: g4r_predict_step's bit pattern); every column
+// of the range whose score is greater / equal adds to cnt[2 r] / cnt[2 r + 1] -- excluded columns too: exclusions shape the list,
+// never the rank.  tie_col != NULL ('tiebreaking'): score (r, n) is moved by tie_noise(r, n + col_off) and the target's by
+// tie_noise(r, tie_col[r]) for the comparison only (k_score_all's keys: col_off = the number of target columns g4r_evaluate puts
+// in front of `items`).  Exclusions (EXCL): seen[r] = (begin, length, position, -): the row's session list is the sorted distinct
+// items s_items[begin .. begin + length), s_first[begin + j] the position in the session of item j's first occurrence; an item is
+// excluded iff it is found there with s_first <= position (the input event's position).  One pair of arrays per call serves every
+// event of a session.  mask: TkExcl's.  seen == NULL: no lists.
+struct TkEvents {
+    const float* tscore; int* cnt; const int* tie_col; long long col_off; unsigned tie_ctr;
+    const int4* seen; const int* s_items; const int* s_first; const unsigned* mask;
+};
+__device__ __forceinline__ TkExcl tk_excl(TkEvents e) { return TkExcl{nullptr, e.s_items, e.mask}; }
+__device__ __forceinline__ TkEvents tk_events() { return TkEvents{}; }
+__device__ __forceinline__ TkEvents tk_events(TkExcl) { return TkEvents{}; }
+__device__ __forceinline__ TkEvents tk_events(TkEvents e) { return e; }
+template <typename... X> struct tk_is_events { static constexpr bool value = false; };
+template <> struct tk_is_events<TkEvents> { static constexpr bool value = true; };
 
 // One wave merges the survivor queue of local row r into the row's sorted list L (global, length n <= k): the queue is sorted in
 // registers (bitonic over the 64 lanes), then every element's place in the union is its own index plus the number of elements of
@@ -59,10 +83,12 @@ __device__ __forceinline__ TkExcl tk_excl(TkExcl e) { return e; }
 // counted in c.  The list then only ever holds eligible entries, so the threshold is an eligible key; an excluded item can still
 // beat it, but enters the range's queue at most once (a range visits each column once): the queue bound (<= 32 per tile) holds.
 // (xb, nx: the row's list is ex.items[xb .. xb + nx), read from LDS so that its load goes out together with the list copy)
-template <bool EXCL>
+// SEEN (TkEvents): an item found in the row's list is dropped only when first[xb + its place] <= pos
+template <bool EXCL, bool SEEN = false>
 __device__ __forceinline__ void topk_merge_row(int r, uint2* L, int k, uint2* sq, unsigned long long* skq, uint2* sl, int* s_qn,
                                                int* s_ln, unsigned long long* s_thr, long long xb = 0, int nx = 0,
-                                               const int* item_idx = nullptr, TkExcl ex = TkExcl{}, int* sx = nullptr) {
+                                               const int* item_idx = nullptr, TkExcl ex = TkExcl{}, int* sx = nullptr, const int* first = nullptr,
+                                               int pos = 0) {
     const int lane = threadIdx.x & 63;
     int c = s_qn[r];
     const int n = s_ln[r];
@@ -89,6 +115,7 @@ __device__ __forceinline__ void topk_merge_row(int r, uint2* L, int k, uint2* sq
             int a = 0, b = hi;
             while (a < b) { const int mid = (a + b) >> 1; if (sx[mid] < item) a = mid + 1; else b = mid; }
             drop = a < hi && sx[a] == item;
+            if constexpr (SEEN) drop = drop && first[xb + a] <= pos;
         }
         const bool keep = lane < c && !drop;
         c = __popcll(__ballot(keep));
@@ -142,8 +169,10 @@ template <bool STORED, bool EXCL, typename... X>
 __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__ mp, const float* h, int mrows, const int* item_idx,
                                                     long long n_sel, const float* sc, long long ldo, int k, int tpr, uint2* ws,
                                                     X... xs) {
-    static_assert(sizeof...(X) == (EXCL ? 1 : 0), "EXCL takes one TkExcl");
+    constexpr bool EV = tk_is_events<X...>::value;      // g4r_recommend_events: rank counters, session-list exclusions
+    static_assert(sizeof...(X) == ((EXCL || EV) ? 1 : 0), "EXCL takes one TkExcl, the events form one TkEvents");
     const TkExcl ex = tk_excl(xs...);
+    const TkEvents ev = tk_events(xs...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, lg = lane >> 4;
     uint2* s_q = reinterpret_cast<uint2*>(smem);
@@ -152,7 +181,8 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
     unsigned long long* s_thr = reinterpret_cast<unsigned long long*>(s_ln + SC_BM);
     long long* s_xb = reinterpret_cast<long long*>(s_thr + SC_BM);      // (EXCL only)
     int* s_xn = reinterpret_cast<int*>(s_xb + SC_BM);
-    char* tail = EXCL ? reinterpret_cast<char*>(s_xn + SC_BM) : reinterpret_cast<char*>(s_thr + SC_BM);
+    int* s_xp = s_xn + SC_BM;                                           // (EXCL with TkEvents only)
+    char* tail = EXCL ? reinterpret_cast<char*>(s_xn + (EV ? 2 : 1) * SC_BM) : reinterpret_cast<char*>(s_thr + SC_BM);
     float* sA = reinterpret_cast<float*>(tail);
     const int ldk = SC_KC + 2;
     float* sB = sA + SC_BM * ldk;
@@ -165,7 +195,12 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
     const int rbase = blockIdx.y * SC_BM, range = blockIdx.x, R = gridDim.x;
     const long long c0 = (long long)range * tpr * TK_TN, c1 = min(n_sel, c0 + (long long)tpr * TK_TN);
     if (tid < SC_BM) { s_qn[tid] = 0; s_ln[tid] = 0; s_thr[tid] = 0ull; }
-    if constexpr (EXCL)
+    if constexpr (EXCL && EV) {
+        if (tid < SC_BM) {
+            const int4 w = (ev.seen && rbase + tid < mrows) ? ev.seen[rbase + tid] : make_int4(0, 0, 0, 0);
+            s_xb[tid] = w.x; s_xn[tid] = w.y; s_xp[tid] = w.z;
+        }
+    } else if constexpr (EXCL)
         if (tid < SC_BM) {
             const bool on = ex.offs && rbase + tid < mrows;
             const long long b = on ? ex.offs[rbase + tid] : 0ll;
@@ -177,11 +212,28 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
     auto merge_all = [&]() {
         for (int r = wid; r < SC_BM; r += 4)
             if (s_qn[r] > 0) {
-                if constexpr (EXCL) topk_merge_row<true>(r, list(r), k, s_q + r * TK_Q, skq, sl, s_qn, s_ln, s_thr, s_xb[r], s_xn[r], item_idx, ex, sx);
+                if constexpr (EXCL && EV)
+                    topk_merge_row<true, true>(r, list(r), k, s_q + r * TK_Q, skq, sl, s_qn, s_ln, s_thr, s_xb[r], s_xn[r], item_idx, ex, sx, ev.s_first, s_xp[r]);
+                else if constexpr (EXCL) topk_merge_row<true>(r, list(r), k, s_q + r * TK_Q, skq, sl, s_qn, s_ln, s_thr, s_xb[r], s_xn[r], item_idx, ex, sx);
                 else topk_merge_row<false>(r, list(r), k, s_q + r * TK_Q, skq, sl, s_qn, s_ln, s_thr);
             }
         __syncthreads();
     };
+    // rank counters (events form, fused): every lane's own share of its 8 rows' (greater, equal) counts over the whole range
+    constexpr bool RANK = EV && !STORED;
+    float tt[2][4];
+    int cg[2][4], ce[2][4];
+    if constexpr (RANK) {
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const int row = rbase + 32 * wid + 16 * ri + 4 * lg + rg, rc = min(row, mrows - 1);
+                float t = ev.tscore[rc];
+                if (ev.tie_col) t += tie_noise(mp->seed, ev.tie_ctr, row, ev.tie_col[rc]);
+                tt[ri][rg] = t; cg[ri][rg] = 0; ce[ri][rg] = 0;
+            }
+    }
     for (long long n0 = c0; n0 < c1; n0 += TK_TN) {
         float v[2][2][4];      // [ri][cj][rg]: row 32 wid + 16 ri + 4 lg + rg, column n0 + 16 cj + li (the MFMA accumulator layout)
         if constexpr (!STORED) {
@@ -256,6 +308,12 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
 #pragma unroll
                 for (int cj = 0; cj < 2; ++cj) {
                     const long long n = n0 + 16 * cj + li;
+                    if constexpr (RANK) {      // in front of every exclusion: those are applied where a queue is merged
+                        float x = v[ri][cj][rg];
+                        if (ev.tie_col) x += tie_noise(mp->seed, ev.tie_ctr, rbase + r, n + ev.col_off);
+                        cg[ri][rg] += (n < c1 && x > tt[ri][rg]) ? 1 : 0;
+                        ce[ri][rg] += (n < c1 && x == tt[ri][rg]) ? 1 : 0;
+                    }
                     const unsigned long long key = topk_key(v[ri][cj][rg], (unsigned)n);
                     if (rbase + r < mrows && n < c1 && key > t) {
                         const int p = atomicAdd(s_qn + r, 1);
@@ -272,6 +330,22 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
             uint2* L = list(r);
             for (int j = s_ln[r] + lane; j < k; j += 64) L[j] = make_uint2(0u, 0xFFFFFFFFu);
         }
+    if constexpr (RANK) {
+        // the 16 lanes that share a row (same lg) are added up, then one atomic pair per row and workgroup
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                int g = cg[ri][rg], e = ce[ri][rg];
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) { g += __shfl_xor(g, o); e += __shfl_xor(e, o); }
+                const int row = rbase + 32 * wid + 16 * ri + 4 * lg + rg;
+                if (li == 0 && row < mrows) {
+                    if (g) atomicAdd(ev.cnt + 2 * row, g);
+                    if (e) atomicAdd(ev.cnt + 2 * row + 1, e);
+                }
+            }
+    }
 }
 
 // Stage 2.  One workgroup per row: the k-th largest key T of the row's nl * k entries by an MSB-first radix select (eight 8-bit
@@ -279,13 +353,14 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
 // With exclusions (EXCL range kernels) the lists hold eligible entries and pads only; g4r_recommend_step_filtered refuses a row with
 // fewer than k eligible candidate positions, so the union of the row's lists still holds at least k real keys (every eligible
 // position is kept unless k better eligible ones of its range are) and "exactly k at or above T" still holds.
-__global__ __launch_bounds__(256) void k_topk_merge(const uint2* ws, int nl, int k, int* out_cols, float* out_scores) {
+// (topk_merge_lists: the body, for the whole workgroup; L = the row's lists, oc / os = the row's outputs; item_idx != NULL: the
+// item index of the column is written instead of the column -- k_events_merge)
+__device__ __forceinline__ void topk_merge_lists(const uint2* L, int nl, int k, int* oc, float* os, const int* item_idx) {
     __shared__ int hist[256];
     __shared__ int s_digit, s_need, s_cnt;
     __shared__ unsigned long long sk[TK_MAX];
     __shared__ uint2 se[TK_MAX];
     const int tid = threadIdx.x;
-    const uint2* L = ws + (size_t)blockIdx.x * nl * k;
     const int N = nl * k;
     unsigned long long prefix = 0ull, mask = 0ull;
     int need = k;
@@ -337,15 +412,35 @@ __global__ __launch_bounds__(256) void k_topk_merge(const uint2* ws, int nl, int
             __syncthreads();
         }
     if (tid < k) {
-        out_cols[(size_t)blockIdx.x * k + tid] = (int)se[tid].y;
-        out_scores[(size_t)blockIdx.x * k + tid] = __uint_as_float(se[tid].x);
+        oc[tid] = item_idx ? item_idx[se[tid].y] : (int)se[tid].y;
+        os[tid] = __uint_as_float(se[tid].x);
     }
+}
+__global__ __launch_bounds__(256) void k_topk_merge(const uint2* ws, int nl, int k, int* out_cols, float* out_scores) {
+    topk_merge_lists(ws + (size_t)blockIdx.x * nl * k, nl, k, out_cols + (size_t)blockIdx.x * k, out_scores + (size_t)blockIdx.x * k, nullptr);
+}
+// g4r_recommend_events: row r of one step is the event at place[r] of the call's outputs (its slot, or its number within the piece
+// being filled); the row's list (item indices: item_idx maps the columns of a candidate list), its rank and its target score go there
+__global__ __launch_bounds__(256) void k_events_merge(const uint2* ws, int nl, int k, const long long* place, const int* item_idx,
+                                                      const float* ranks, const float* tscore, int* out_items, float* out_scores,
+                                                      float* out_rank, float* out_tscore) {
+    const size_t s = (size_t)place[blockIdx.x];
+    topk_merge_lists(ws + (size_t)blockIdx.x * nl * k, nl, k, out_items + s * k, out_scores + s * k, item_idx);
+    if (threadIdx.x == 0) { out_rank[s] = ranks[blockIdx.x]; out_tscore[s] = tscore[blockIdx.x]; }
+}
+// softmax / softmax_logit: the target score of every row out of the materialised scores (column tcol[r] of row r)
+__global__ __launch_bounds__(256) void k_events_tscore(const float* sc, long long ldo, const int* tcol, int mrows, float* out) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r < mrows) out[r] = sc[(size_t)r * ldo + tcol[r]];
 }
 
 template __global__ void k_topk_range<false, false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
 template __global__ void k_topk_range<true, false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
 template __global__ void k_topk_range<false, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);
 template __global__ void k_topk_range<true, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);
+template __global__ void k_topk_range<false, false, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
+template __global__ void k_topk_range<false, true, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
+template __global__ void k_topk_range<true, true, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
 
 // ---- stateless replay of session histories (g4r_recommend_sessions) ---------------------------------------------------------
 // A chunk's rows are sorted by history length, descending; perm[r] is the chunk row (caller's order) of sorted row r, len[r] its

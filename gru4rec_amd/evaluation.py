@@ -8,12 +8,15 @@ the targets with the > / >= / == counts of :62-65 (mode 'tiebreaking': scores + 
 stream keyed by the model seed, evaluation step, row and candidate column) and adds the hits and reciprocal ranks of every cut-off into device
 accumulators; hidden rows of finished sessions are zeroed / dropped on the device.  `evaluate_gpu_stepwise` is the
 host-driven variant (one `g4r_predict_step` + `g4r_rank_targets` per step), kept as a cross-check.
+
+Not in the reference: `recommend_gpu` runs the same loop (`g4r_recommend_events`) and returns, for every scored event, its top-k
+list, the rank of its target and the target's score; `list_metrics` turns that into recall, MRR, NDCG and item coverage.
 """
 import numpy as np
 import pandas as pd
 
 
-def _prepare_categorical(gru, test_data, items, session_key, item_key, time_key):
+def _prepare_categorical(gru, test_data, items, session_key, item_key, time_key, want_sessions=False):
     """_prepare for tables from eventio.read_events: the inner join on the item id, the (session, time, item id) ordering and
     the session sizes of evaluation.py:86-95 as linear passes over integer arrays."""
     from . import datatools, eventio
@@ -33,12 +36,16 @@ def _prepare_categorical(gru, test_data, items, session_key, item_key, time_key)
         sess, idx = sess[order], idx[order]
     item_idxs = None if items is None else gru.itemidmap[items].values.astype(np.int32)
     offs = datatools.compute_offset(pd.DataFrame({session_key: sess}, copy=False), session_key).astype(np.int64)
+    if want_sessions:
+        return idx.astype(np.int32), item_idxs, offs, sess
     return idx.astype(np.int32), item_idxs, offs
 
 
-def _prepare(gru, test_data, items, session_key, item_key, time_key):
+def _prepare(gru, test_data, items, session_key, item_key, time_key, want_sessions=False):
+    """(item index of every event of the sorted test table, candidate item indices or None, session offsets); want_sessions: + the
+    session id of every event."""
     if isinstance(test_data[item_key].dtype, pd.CategoricalDtype):
-        return _prepare_categorical(gru, test_data, items, session_key, item_key, time_key)
+        return _prepare_categorical(gru, test_data, items, session_key, item_key, time_key, want_sessions)
     lookup = pd.DataFrame({'ItemIdx': gru.itemidmap.values, item_key: gru.itemidmap.index})
     test_data = pd.merge(test_data, lookup, on=item_key, how='inner')
     test_data.sort_values([session_key, time_key, item_key], inplace=True)
@@ -47,6 +54,8 @@ def _prepare(gru, test_data, items, session_key, item_key, time_key):
     sizes = test_data.groupby(session_key).size().values
     offs = np.zeros(len(sizes) + 1, dtype=np.int64)
     offs[1:] = np.cumsum(sizes)
+    if want_sessions:
+        return titems, item_idxs, offs, test_data[session_key].values
     return titems, item_idxs, offs
 
 
@@ -143,3 +152,141 @@ def evaluate_gpu_stepwise(gru, test_data, items=None, session_key='SessionId', i
     rec = (rec / n).tolist()
     mrr = (mrr / n).tolist()
     return rec, mrr
+
+
+# ---------------------------------------------------------------------------------------------- per-event lists (not in the reference)
+def slot_map(offs, batch_size):
+    """(plan, rows): the evaluation plan of sessions with offsets `offs` and, for every (step, row) of it, the row of the sorted
+    test table that is the step's INPUT event (-1 for padding).  The plan builder run on arange(n_rows) in place of the item
+    indices returns exactly that as its in_idx."""
+    from . import _native
+    offs = np.asarray(offs, dtype=np.int64)
+    n_sessions, n_rows = len(offs) - 1, int(offs[-1])
+    rows = _native.build_plan(offs.astype(np.int32), np.arange(n_sessions), np.arange(n_rows, dtype=np.int32), batch_size, 1)
+    T = rows['T']
+    table = rows['in_idx'].astype(np.int64).reshape(T, batch_size)
+    table[np.arange(batch_size)[None, :] >= rows['M'][:T, None]] = -1
+    return rows, table
+
+
+def seen_tables(titems, offs):
+    """The seen-item tables of g4r_recommend_events, linear in the number of events: per session the sorted distinct item indices
+    and, beside each, the position in the session of its first occurrence.  Returns dict(offs int64[n_sessions + 1], items int32,
+    first int32)."""
+    titems = np.asarray(titems, dtype=np.int64)
+    offs = np.asarray(offs, dtype=np.int64)
+    n_sessions = len(offs) - 1
+    sess = np.repeat(np.arange(n_sessions), np.diff(offs))
+    pos = np.arange(len(titems)) - offs[sess]
+    order = np.lexsort((pos, titems, sess))          # by session, then item, then position: the first of every (session, item) run
+    s, it, p = sess[order], titems[order], pos[order]
+    head = np.ones(len(order), dtype=bool)
+    head[1:] = (s[1:] != s[:-1]) | (it[1:] != it[:-1])
+    counts = np.bincount(s[head], minlength=n_sessions)
+    return dict(offs=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), items=it[head].astype(np.int32),
+                first=p[head].astype(np.int32))
+
+
+def recommend_gpu(gru, test_data, k=20, items=None, session_key='SessionId', item_key='ItemId', time_key='Time', batch_size=100,
+                  mode='standard', exclude_seen=False, exclude=None):
+    """The top-k list and the target's rank at EVERY event of a test set, in one device call (g4r_recommend_events): the loop of
+    evaluate_gpu -- same preparation, same plan, same ranks -- that keeps what evaluate_gpu folds into two sums.
+
+    Returns a dict of NumPy arrays with one entry per scored event (every event of the sorted test table that has a successor in
+    its session), in the order of that table:
+      row           index of the input event in the sorted test table (events of unknown items dropped, sorted by session, time, item)
+      session       its session id
+      target        item id of the next event of the session
+      rank          the target's rank among the candidates (`mode` as in evaluate_gpu): sum(rank <= c) / n is evaluate_gpu's recall@c
+      target_score  the target's score
+      items         [n, k] item ids, best first: what recommend_sessions returns for the session's prefix up to the input event
+      scores        [n, k] float32, predict_next_batch's bit patterns
+    items: candidate item ids (default: all); the list is chosen among them, the rank counts them (the target itself is ranked
+    whether listed or not, as in evaluate_gpu).  exclude_seen: an event's list leaves out the items its session has shown up to and
+    including the input event (recommend_sessions' exclude_history); exclude: item ids left out of every list.  Exclusions never
+    change `rank`.  A session with more than G4R_EXCLUDE_MAX distinct items, or exclusions that leave fewer than k candidates at
+    some event, raise ValueError naming the session before anything runs."""
+    from . import _native
+    if gru.error_during_train:
+        raise Exception
+    if mode not in ('standard', 'conservative', 'median', 'tiebreaking'):
+        raise NotImplementedError
+    n_sel = len(gru.itemidmap) if items is None else len(items)
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
+        raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+    k = int(k)
+    if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError('batch_size = %r: it must be a positive integer' % (batch_size,))
+    titems, item_idxs, offs, sess_ids = _prepare(gru, test_data, items, session_key, item_key, time_key, want_sessions=True)
+    n_sessions = len(offs) - 1
+    if n_sessions < batch_size:
+        raise IndexError('fewer test sessions ({}) than batch_size ({})'.format(n_sessions, batch_size))
+    mask = None
+    if exclude is not None:
+        ex = exclude if isinstance(exclude, np.ndarray) else list(exclude)
+        if len(ex):
+            gidx = np.unique(gru.itemidmap[np.ravel(ex)].values.astype(np.int64))
+            mask = np.zeros((len(gru.itemidmap) + 31) // 32, dtype=np.uint32)
+            np.bitwise_or.at(mask, gidx >> 5, np.left_shift(1, gidx & 31).astype(np.uint32))
+    first_sess = sess_ids[offs[:-1]] if n_sessions else np.zeros(0)
+    seen = None
+    if exclude_seen:
+        seen = seen_tables(titems, offs)
+        big = np.flatnonzero(np.diff(seen['offs']) > _native.G4R_EXCLUDE_MAX)
+        if len(big):
+            raise ValueError('exclude_seen: session %s holds %d distinct items, more than G4R_EXCLUDE_MAX = %d'
+                             % (first_sess[big[0]], np.diff(seen['offs'])[big[0]], _native.G4R_EXCLUDE_MAX))
+    model = gru._ensure_model()
+    plan = _native.build_plan(offs.astype(np.int32), np.arange(n_sessions), titems, batch_size, 1)
+    _, table = slot_map(offs, batch_size)
+    # scored events in table order: every row with a successor in its session; slot = its number among them
+    has_next = np.ones(len(titems), dtype=bool)
+    has_next[offs[1:] - 1] = False
+    rows = np.flatnonzero(has_next)
+    number = np.full(len(titems) + 1, -1, dtype=np.int64)
+    number[rows] = np.arange(len(rows))
+    slot = number[table]                       # (table == -1 reads the spare last entry: -1)
+    if seen is not None:
+        row_sess = np.repeat(np.arange(n_sessions), np.diff(offs))
+        safe = np.maximum(table, 0)
+        seen['sess'] = row_sess[safe].astype(np.int32)
+        seen['pos'] = (safe - offs[row_sess[safe]]).astype(np.int32)
+    try:
+        li, ls, rank, ts = model.recommend_events(plan, batch_size, item_idxs, mode, slot, len(rows), k, mask, seen)
+    except _native.NativeError as e:
+        import re
+        hit = re.search(r'session (\d+) has', str(e))
+        if hit:
+            raise ValueError('session %s: %s' % (first_sess[int(hit.group(1))], e)) from None
+        if 'eligible candidate positions' in str(e):
+            raise ValueError(str(e)) from None
+        raise
+    finally:
+        gru.predict = None      # the call used the model's prediction state (see evaluate_gpu)
+    ids = gru.itemidmap.index.values
+    return dict(row=rows, session=np.asarray(sess_ids)[rows], target=ids[titems[rows + 1]], rank=rank, target_score=ts,
+                items=ids[li], scores=ls)
+
+
+def list_metrics(result, cut_off=[5, 10, 20], n_items=None):
+    """Metrics of a recommend_gpu result, per cut-off: dict(recall, mrr, ndcg, coverage), each a list with one entry per cut-off.
+    recall / mrr are evaluate_gpu's (from `rank`); ndcg = mean of 1 / log2(1 + rank) over the events with rank <= cut (one
+    relevant item per event: the ideal DCG is 1); coverage = distinct items in the first `cut` columns of `items` / n_items
+    (None without n_items).  A cut-off above the list length k is refused for coverage only when n_items is given."""
+    cuts = list(cut_off) if isinstance(cut_off, (list, tuple, np.ndarray)) else [cut_off]
+    rank = np.asarray(result['rank'], dtype=np.float64)
+    n = max(len(rank), 1)
+    out = dict(recall=[], mrr=[], ndcg=[], coverage=[])
+    for c in cuts:
+        hit = rank <= c
+        out['recall'].append(float(hit.sum()) / n)
+        out['mrr'].append(float((1.0 / rank[hit]).sum()) / n)
+        out['ndcg'].append(float((1.0 / np.log2(1.0 + rank[hit])).sum()) / n)
+        if n_items is None:
+            out['coverage'].append(None)
+        else:
+            lists = np.asarray(result['items'])
+            if c > lists.shape[1]:
+                raise ValueError('coverage at cut-off %d needs lists of at least that length (k = %d)' % (c, lists.shape[1]))
+            out['coverage'].append(len(np.unique(lists[:, :c])) / float(n_items))
+    return out

@@ -258,6 +258,43 @@ int g4r_evaluate(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, co
                  const int32_t* items, int64_t n_items_sel, const int32_t* cutoffs, int32_t n_cut, int32_t mode,
                  double* recall_sum, double* mrr_sum, int64_t* n_events);
 
+/* not in the reference: g4r_evaluate's test loop returning, for EVERY event, its top-k list, the rank of its target and the
+ * target's score, instead of two sums.  Plan arguments (in_idx ... mode) as in g4r_evaluate; the rank of an event is the value
+ * g4r_evaluate feeds to its sums (same counts, same tie rule, same 'tiebreaking' noise), so sum(rank <= cut) is its recall_sum.
+ * With an element-wise final activation every step makes ONE pass over the candidates' Wy rows, which yields both the rows' k best
+ * and the (greater, equal) counts against the rows' target scores; softmax / softmax_logit materialise the scores first, as
+ * g4r_evaluate and g4r_recommend_step do (two passes and more).
+ *   slot[T * batch]   where the event at (step, row) goes in the outputs; rows >= M[step] are padding (-1, not read).  Every slot
+ *                     is in [0, n_slots) and used at most once; slots no event uses read zero.
+ *   k                 1 <= k <= min(candidates, G4R_TOPK_MAX); the candidates are all items, or `items` (the list is chosen
+ *                     among `items` only, never among the other rows' targets that g4r_evaluate ranks in front of them).
+ *   excl_mask         as in g4r_recommend_step_filtered, NULL = none.
+ *   seen_*            exclusion of the items an event's session has shown up to and including the input event, in linear space:
+ *                     session s (0 <= s < n_seen) has the sorted, duplicate-free item indices seen_items[seen_offs[s] ..
+ *                     seen_offs[s + 1]) (at most G4R_EXCLUDE_MAX) and, beside each, seen_first: the position in the session of
+ *                     the item's first occurrence.  The event at (step, row) belongs to session seen_sess[step * batch + row] and
+ *                     its input is that session's event number seen_pos[..]: an item is excluded iff it is in the session's list
+ *                     with seen_first <= seen_pos.  seen_offs NULL = none.  Exclusions remove items from the list, never from
+ *                     the rank.
+ *   outputs           by slot, any may be NULL: out_items[n_slots * k] item indices (also with `items`), out_scores[n_slots * k]
+ *                     in g4r_recommend_step's order (score descending, equal scores by the lower candidate position, NaN last)
+ *                     and with g4r_predict_step's bit patterns (softmax with `items`: normalised over `items`, as
+ *                     g4r_recommend_step returns them), out_rank[n_slots], out_target_score[n_slots] (the score the rank compared
+ *                     with; softmax with `items`: normalised over [targets | items], as g4r_evaluate ranks it).
+ * Everything is checked before the first launch (the prediction state is untouched by a refused call): sizes, indices, slots, the
+ * tables, and that every session keeps at least k eligible candidate positions at its last event -- the refusal names the session.
+ * Results are written on the device at the event's slot and copied to the host once, at the end; when n_slots * k * 8 bytes exceed
+ * G4R_EVENTS_PIECE_BYTES (G4R_EVENTS_PIECE in the environment overrides it, for tests), in pieces of that many bytes of whole
+ * steps, one synchronisation each.  No host round trip per step.  Uses the prediction state like g4r_evaluate (fresh state, `batch`
+ * rows). */
+#define G4R_EVENTS_PIECE_BYTES (1LL << 30)
+int g4r_recommend_events(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, const uint8_t* reset, const int32_t* M, int64_t T,
+                         int32_t batch, const int64_t* compact_steps, const int32_t* compact_maps, int64_t n_compact,
+                         const int32_t* items, int64_t n_items_sel, int32_t mode, const int64_t* slot, int64_t n_slots, int32_t k,
+                         const uint32_t* excl_mask, const int64_t* seen_offs, const int32_t* seen_items, const int32_t* seen_first,
+                         int64_t n_seen, const int32_t* seen_sess, const int32_t* seen_pos, int32_t* out_items, float* out_scores,
+                         float* out_rank, float* out_target_score);
+
 /* ---- input pipeline: the pandas work in front of fit() for TAB separated files -------------
  * run.py:45-78 `pd.read_csv(sep='\t', usecols, dtype={session: int32, item: str})` + gru4rec.py:534-538
  * `itemids = data[item_key].unique(); itemidmap = Series(arange, index=itemids); data['ItemIdx'] = itemidmap[...]`.

@@ -38,6 +38,8 @@ OPTIONS = [
     ('-pm', '--primary_metric', dict(metavar='METRIC', choices=['recall', 'mrr'], default='recall', help='metric reported on the PRIMARY METRIC line (default recall)')),
     ('-lpm', '--log_primary_metric', dict(action='store_true', help='print the PRIMARY METRIC line after every evaluation')),
     (None, '--sparse_exact', dict(action='store_true', help='with --gpus N: keep the replicas bit-identical by exchanging every rank\'s per-occurrence gradient rows of the item tables every step (one RCCL all-gather) instead of reconciling GPU-local rows every sync_every steps.  REDUCE form: all ranks draw ONE stream of negatives, the gradient rows of a shared negative are summed over the ranks before the optimizer rule and every row is scaled by 1 / N -- the update of one batch of N x batch_size rows, except that a row meets only its own rank\'s in-batch negatives; for catalogues whose exchanged list fits the LDS')),
+    (None, '--save_recs', dict(metavar='PATH', help='with -t (not in the reference): also write the top-k recommendation list, the target\'s rank and score of every test event to PATH as .npz (evaluation.recommend_gpu; several test sets: PATH gets the set\'s number in front of its extension)')),
+    (None, '--recs_k', dict(metavar='K', type=int, default=20, help='list length of --save_recs (default 20)')),
     (None, '--gpus', dict(metavar='N', type=int, default=1, help='train on N GPUs of this node (not in the reference): one process per GPU, sessions sharded over '
                           'the ranks, dense GRU gradients all-reduced by RCCL every step, item rows GPU-local and reconciled every sync_every steps (4 at two ranks, 16 from three on) and at every epoch end; rank 0 saves / evaluates')),
 ]
@@ -151,6 +153,14 @@ def evaluate(model, opts):
             print('Recall@{}: {:.6f} MRR@{}: {:.6f}'.format(cut, scores[0][pos], cut, scores[1][pos]))
         if opts.log_primary_metric:
             print('PRIMARY METRIC: {}'.format(scores[which][0]))
+        if opts.save_recs:
+            import numpy as np
+            recs = evaluation.recommend_gpu(model, events, k=opts.recs_k, batch_size=512, mode=opts.eval_type, item_key=opts.item_key,
+                                            session_key=opts.session_key, time_key=opts.time_key)
+            root, ext = os.path.splitext(opts.save_recs)
+            out = opts.save_recs if len(opts.test) == 1 else '{}.{}{}'.format(root, opts.test.index(fname), ext or '.npz')
+            np.savez(out, **recs)
+            print('Saved the recommendations of {} events to: {}'.format(len(recs['rank']), out))
 
 
 def main(argv=None):
