@@ -21,6 +21,8 @@ ACT_IDS = {'linear': 0, 'relu': 1, 'tanh': 2, 'leaky': 3, 'elu': 4, 'selu': 5, '
 ADAPT_IDS = {'adagrad': 0, 'rmsprop': 1, 'adadelta': 2, 'adam': 3, None: 4}
 RANK_MODES = {'standard': 0, 'conservative': 1, 'median': 2, 'tiebreaking': 3}
 EMBED_CONSTRAINED, EMBED_SEPARATE, EMBED_ONEHOT = 0, 1, 2
+SIM_METRICS = {'dot': 0, 'cosine': 1}      # G4R_SIM_*
+SIM_SPACES = {'output': 0, 'input': 1}     # G4R_SPACE_*
 
 
 class G4RConfig(C.Structure):
@@ -46,7 +48,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_scan_table_release', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -107,6 +109,7 @@ def lib():
     L.g4r_recommend_sessions_scan.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i32, i64p, i32p, C.POINTER(C.c_uint32),
                                               i32p, f32p, C.POINTER(f32p)]
     L.g4r_scan_table_release.argtypes = [vp]
+    L.g4r_similar_items.argtypes = [vp, i32, i32, i32p, i64, i32p, i64, i32, i32, C.POINTER(C.c_uint32), i32p, f32p]
     L.g4r_score_candidates.argtypes = [vp, i32p, i32, i64p, i32p, i32, f32p, i32p]
     L.g4r_score_candidates_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i64p, i32p, i32, f32p, i32p, C.POINTER(f32p)]
     L.g4r_rank_targets.argtypes = [vp, i32p, i32, i64, i32, f32p]
@@ -466,6 +469,28 @@ class Model:
         else:
             _chk(lib().g4r_recommend_sessions_scan(*head, int(oversample), *tail))
         return (cols, scores, hout) if return_hidden else (cols, scores)
+
+    def similar_items(self, q_idx, item_idx=None, k=20, metric='cosine', space='output', exclude_self=True, excl_mask=None):
+        """The k candidates most similar to every query item in the model's own embedding space (g4r_similar_items; stateless):
+        (cols int32[n, k], scores float32[n, k]); cols are positions in item_idx (item indices without it).  excl_mask as in
+        recommend_step_filtered."""
+        qi = np.ascontiguousarray(q_idx, dtype=np.int32)
+        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
+        n_sel = self.cfg.n_items if it is None else len(it)
+        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
+        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
+            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
+        cols = np.empty((len(qi), k), dtype=np.int32)
+        scores = np.empty((len(qi), k), dtype=np.float32)
+        _chk(lib().g4r_similar_items(self.h, SIM_SPACES[space], SIM_METRICS[metric], _i32(qi), len(qi), None if it is None else _i32(it),
+                                     n_sel, k, 1 if exclude_self else 0, None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                     _i32(cols), _f32(scores)))
+        return cols, scores
+
+    def sim_norms(self):
+        """State of the inverse-norm cache of similar_items: (bytes held, valid, builds so far)."""
+        a = self.get_debug('sim_norms', 3)
+        return int(a[0]), bool(a[1]), int(a[2])
 
     @staticmethod
     def _cand_csr(cand_offs, cand_items, rows):

@@ -41,7 +41,8 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            9: "the merge-time exclusion search of g4r_recommend_step_filtered never matches the LAST item of a row's sorted list",
            10: "k_replay_final (g4r_recommend_sessions) reads every row's final state from the buffer of the chunk's LONGEST history",
            11: "k_score_cand (g4r_score_candidates*): a work item past a row's first slice reads the items of the row's first slice",
-           12: "the two-stage top-k (g4r_recommend_*_scan) ranks its candidates by the APPROXIMATE bf16 scores: the fp32 re-scoring is skipped"}
+           12: "the two-stage top-k (g4r_recommend_*_scan) ranks its candidates by the APPROXIMATE bf16 scores: the fp32 re-scoring is skipped",
+           13: "cosine (g4r_similar_items): the candidate's inverse norm is read at the candidate POSITION instead of its item index"}
 
 
 def mutant_path(k):

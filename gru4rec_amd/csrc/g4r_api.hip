@@ -17,6 +17,7 @@
 #include "g4r_topk_kernels.cuh"
 #include "g4r_cand_kernels.cuh"
 #include "g4r_scan_kernels.cuh"
+#include "g4r_sim_kernels.cuh"
 #include "g4r_sync_kernels.cuh"
 #include "g4r_micro_kernels.cuh"
 #include "g4r_wide_kernels.cuh"
@@ -31,6 +32,7 @@ extern "C" {
 #include "g4r_host_plan.hpp"
 #include "g4r_host_step.hpp"
 #include "g4r_host_predict.hpp"
+#include "g4r_host_similar.hpp"
 #include "g4r_host_comm.hpp"
 #include "g4r_host_sync.hpp"
 #include "g4r_host_debug.hpp"

@@ -34,6 +34,12 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
         host[0] = (float)((double)m->s_tab_units * 16.0); host[1] = m->s_tab_valid ? 1.f : 0.f; host[2] = (float)m->s_tab_builds;
         return 0;
     }
+    else if (s == "sim_norms") {      // (bytes the inverse norms of g4r_similar_items hold, 1 if a table's are valid, builds so far)
+        if (count < 3) return fail("count");
+        host[0] = (float)(((m->sim_inv[0] ? 1.0 : 0.0) + (m->sim_inv[1] ? 1.0 : 0.0)) * (double)d.n_items * 4.0);
+        host[1] = (m->sim_valid[0] || m->sim_valid[1]) ? 1.f : 0.f; host[2] = (float)m->sim_builds;
+        return 0;
+    }
     else if (s == "events_launches") {      // the last g4r_recommend_events call: (steps, launches that scan the candidate columns, all launches, pieces)
         if (count < 4) return fail("count");
         host[0] = (float)m->ev_steps; host[1] = (float)m->ev_scans; host[2] = (float)m->ev_launches; host[3] = (float)m->ev_pieces;

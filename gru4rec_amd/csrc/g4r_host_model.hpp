@@ -176,6 +176,15 @@ struct g4r_model {
     int* s_cnt = nullptr;
     int64_t s_cols_cap = 0, s_cnt_cap = 0;
     std::vector<int4> s_work;
+    // item neighbours (g4r_similar_items): the inverse row norms of the item tables (0: Wy, 1: E), built on the first cosine call and
+    // again after anything that may have changed the tables (weights_changed); the query items of one chunk and their rows
+    float* sim_inv[2] = {nullptr, nullptr};
+    bool sim_valid[2] = {false, false};
+    int64_t sim_builds = 0;
+    int* sim_q = nullptr;
+    int64_t sim_q_cap = 0;
+    float* sim_rows = nullptr;                   // [chunk rows][W] the chunk's query rows (k_sim_gather)
+    int64_t sim_rows_cap = 0;
     unsigned tie_ctr = 0;                       // evaluation step counter of the 'tiebreaking' noise stream
     // the last g4r_recommend_events call (g4r_get_debug "events_launches"): its steps, the launches whose grid spans the candidate
     // columns, all its launches, the pieces its lists came back in
@@ -210,8 +219,9 @@ struct g4r_model {
     bool sync_on = false;
 };
 
-// every entry that may rewrite Wy calls this: the bf16 shadow table of the two-stage top-k is rebuilt on its next use
-static inline void weights_changed(g4r_model* m) { m->s_tab_valid = false; }
+// every entry that may rewrite Wy / E calls this: the bf16 shadow table of the two-stage top-k and the inverse norms of
+// g4r_similar_items are rebuilt on their next use
+static inline void weights_changed(g4r_model* m) { m->s_tab_valid = false; m->sim_valid[0] = m->sim_valid[1] = false; }
 
 template <class T>
 static int dalloc(g4r_model* m, T** p, size_t n, bool zero = true) {

@@ -1108,6 +1108,77 @@ class GRU4Rec:
         H = [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(out[1], self.layers)]
         return (res, H) if kk == 0 else (res[0], res[1], H)
 
+    # ------------------------------------------------------------------ item-to-item neighbours (not in the reference)
+    def similar_items(self, item_ids, k=20, metric='cosine', space='output', predict_for_item_ids=None, exclude_self=True, exclude=None):
+        """The k items most similar to each of item_ids in the model's own embedding space:
+        (item_ids[len(item_ids), k], scores[len(item_ids), k] float32).  Not in the reference.
+
+          item_ids   the query items, any number >= 1, duplicates allowed (they give duplicate rows).
+          space      'output': the rows of Wy (layers[-1] wide), the space the sessions' hidden states are scored in.  'input': the
+                     input embedding -- E when embedding > 0, Wy again with constrained_embedding; a one-hot input model has none
+                     (NotImplementedError: use space='output').
+          metric     'dot': sum_d T[q, d] * T[j, d] in fp32.  'cosine': (dot * inv[q]) * inv[j], inv = 1 / sqrt(sum of squares) in
+                     fp32; a zero row has inv = 0 and scores 0 against everything, itself included.
+          predict_for_item_ids  the candidates in the given order (duplicates allowed); None: all items in itemidmap order.
+          exclude_self          skip every candidate position that holds the query item itself.
+          exclude               item ids never returned for any query.
+
+        Row r holds the k best candidates of item_ids[r]: score descending, equal scores by the lower candidate position, NaN last
+        (the order of recommend_next_batch).  The score of a (query, candidate) pair depends on the two rows alone, so it is
+        bit-identical in every call the pair appears in, whatever the other queries, the candidate list or the size of the call.
+        Scoring and selection run on the device: only k entries per row return.  The call is stateless: the prediction state
+        (predict_next_batch / recommend_next_batch) is neither read nor changed.  The items' inverse norms are kept on the device and
+        rebuilt after fit / a parameter upload.  Everything is checked before any device work: an unknown item id raises KeyError; a
+        bad k, metric or space, or a query with fewer than k eligible candidate positions (duplicates count), raises ValueError."""
+        if self.error_during_train:
+            raise Exception
+        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
+        if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
+            raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        if metric not in _native.SIM_METRICS:
+            raise ValueError("metric = %r: it must be 'cosine' or 'dot'" % (metric,))
+        if space not in _native.SIM_SPACES:
+            raise ValueError("space = %r: it must be 'output' or 'input'" % (space,))
+        if space == 'input' and not self.constrained_embedding and not self.embedding:
+            raise NotImplementedError("space='input': a one-hot input model has no input embedding (layer 0 reads a row of Wx per item, "
+                                      "three gates wide); use space='output'")
+        ids = np.ravel(item_ids) if isinstance(item_ids, np.ndarray) else list(item_ids)
+        if len(ids) < 1:
+            raise ValueError('item_ids is empty: at least one query item is needed')
+        qidx = self.itemidmap[ids].values.astype(np.int32)
+        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values.astype(np.int32)
+        n_items = len(self.itemidmap)
+        gidx = np.zeros(0, dtype=np.int64)
+        if exclude is not None:
+            ex = exclude if isinstance(exclude, np.ndarray) else list(exclude)
+            if len(ex):
+                gidx = np.unique(self.itemidmap[np.ravel(ex)].values.astype(np.int64))
+        # eligible candidate positions per query: all - positions of excluded items - (exclude_self) positions of its own item
+        if iidx is None:
+            n_masked, own = len(gidx), np.ones(len(qidx), dtype=np.int64)
+        else:
+            n_masked = int(np.isin(iidx, gidx).sum())
+            own = np.bincount(iidx, minlength=n_items)[qidx]
+        elig = n_sel - n_masked - (np.where(np.isin(qidx, gidx), 0, own) if exclude_self else 0) * np.ones(len(qidx), dtype=np.int64)
+        short = np.flatnonzero(elig < k)
+        if len(short):
+            raise ValueError('query %d (item id %r) has %d eligible candidate positions, fewer than k = %d'
+                             % (short[0], getattr(ids[short[0]], 'item', lambda: ids[short[0]])(), elig[short[0]], k))
+        mask = None
+        if len(gidx):
+            mask = np.zeros((n_items + 31) // 32, dtype=np.uint32)
+            np.bitwise_or.at(mask, gidx >> 5, np.left_shift(1, gidx & 31).astype(np.uint32))
+        m = self._ensure_model()
+        cols, scores = m.similar_items(qidx, iidx, int(k), metric, space, bool(exclude_self), mask)
+        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
+        return cand[cols], scores
+
+    def item_neighbors(self, k=20, metric='cosine', space='output', exclude=None):
+        """The k nearest neighbours of EVERY item: (neighbor_ids[n_items, k], scores[n_items, k] float32), rows in itemidmap order.
+        Not in the reference.  It is similar_items(itemidmap.index, k, metric, space, exclude_self=True, exclude=exclude), bit for
+        bit: the whole n_items x n_items product is scored and selected on the device in chunks of rows, and only the lists return."""
+        return self.similar_items(self.itemidmap.index.values, k=k, metric=metric, space=space, exclude=exclude)
+
     def symbolic_predict(self, X, Y, M, items, batch_size):
         raise NotImplementedError('symbolic_predict builds a Theano graph (gru4rec.py:729-741); the MI355X path '
                                   'exposes the same computation through gru4rec_amd.evaluation.evaluate_gpu')

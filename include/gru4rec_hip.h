@@ -230,6 +230,38 @@ int g4r_recommend_sessions_scan(g4r_model* m, const int64_t* hist_offs, const in
                                 float* const* out_hidden);
 int g4r_scan_table_release(g4r_model* m);
 
+/* not in the reference: item-to-item neighbours in the model's own embedding space -- the k candidates most similar to each of n
+ * query items.  Stateless: the prediction state and the training state are neither read nor changed.
+ *   table T     space = G4R_SPACE_OUTPUT: Wy, rows of layers[n_layers - 1] floats.  G4R_SPACE_INPUT: E when embed_mode is
+ *               G4R_EMBED_SEPARATE (rows of `embedding` floats), Wy when it is G4R_EMBED_CONSTRAINED; a one-hot input model has no
+ *               input embedding and the call is refused with that reason.
+ *   score       of (query item q, candidate item j).  G4R_SIM_DOT: sum_d T[q, d] * T[j, d], fp32 products, fp32 accumulation, one
+ *               chain from zero in ascending d.  G4R_SIM_COSINE: (dot(q, j) * inv[q]) * inv[j], inv[i] = 1 / sqrt(sum_d T[i, d]^2)
+ *               in fp32 (IEEE division and square root), inv[i] = 0 when the sum is 0: a zero row scores 0 against everything,
+ *               itself included.  The score of a pair depends on the values of the two rows only -- not on the candidate's
+ *               position, the other queries of the call, the chunks the call is cut into, or whether item_idx was given -- so it
+ *               is bit-identical wherever the pair appears.
+ *   selection   g4r_recommend_step's order: score descending, equal scores by the lower candidate position, NaN last;
+ *               1 <= k <= min(candidates, G4R_TOPK_MAX).
+ *   candidates  item_idx[n_sel] (duplicates allowed, every position is a candidate), NULL: all items.  out_cols holds positions in
+ *               item_idx, item indices when it is NULL.
+ *   exclusions  exclude_self != 0 skips every candidate position that holds the query's own item; excl_mask is the mask of
+ *               g4r_recommend_step_filtered (NULL = none).  A query with fewer than k eligible positions is refused before any
+ *               launch; the refusal names the query.
+ *   q_idx[n]    query item indices, any n >= 1, duplicates allowed; processed in chunks of rows sized by the library
+ *               (G4R_SIM_CHUNK in the environment forces a smaller chunk, for tests: the results do not depend on it).  Results are
+ *               copied to the host once per chunk; there is no host round trip inside a chunk.
+ * Everything is checked before the first launch.  The inverse norms are cached per table, built on the first cosine call and rebuilt
+ * on the first one after anything that may have changed the tables (g4r_train_steps, g4r_virtual_train_steps, g4r_set_param,
+ * g4r_comm_sync_sparse, g4r_sync_import, g4r_virtual_sync_dense); g4r_get_debug "sim_norms" -> (bytes held, 1 if valid, builds so
+ * far); g4r_destroy frees them. */
+#define G4R_SIM_DOT 0
+#define G4R_SIM_COSINE 1
+#define G4R_SPACE_OUTPUT 0
+#define G4R_SPACE_INPUT 1
+int g4r_similar_items(g4r_model* m, int32_t space, int32_t metric, const int32_t* q_idx, int64_t n, const int32_t* item_idx,
+                      int64_t n_sel, int32_t k, int32_t exclude_self, const uint32_t* excl_mask, int32_t* out_cols, float* out_scores);
+
 /* not in the reference: scores of per-row candidate lists (the re-ranking stage behind a retrieval stage).  Row r's list is the
  * item indices cand_items[cand_offs[r] .. cand_offs[r + 1]) (at least one; cand_offs rises strictly; duplicates allowed, every
  * position is scored), at most G4R_CAND_MAX positions in all.  g4r_score_candidates advances the prediction state exactly as

@@ -43,12 +43,18 @@ OPTIONS = [
     (None, '--gpus', dict(metavar='N', type=int, default=1, help='train on N GPUs of this node (not in the reference): one process per GPU, sessions sharded over '
                           'the ranks, dense GRU gradients all-reduced by RCCL every step, item rows GPU-local and reconciled every sync_every steps (4 at two ranks, 16 from three on) and at every epoch end; rank 0 saves / evaluates')),
 ]
+# item-to-item neighbours (not in the reference): a table of their own, after training or loading
+NEIGHBOR_OPTIONS = [
+    (None, '--save_neighbors', dict(metavar='PATH', help='after training or loading (not in the reference): write every item\'s nearest neighbours in the model\'s output embedding to PATH as .npz -- item_ids, neighbor_ids, scores (GRU4Rec.item_neighbors)')),
+    (None, '--neighbors_k', dict(metavar='K', type=int, default=20, help='neighbours per item of --save_neighbors (default 20)')),
+    (None, '--neighbors_metric', dict(metavar='METRIC', choices=['cosine', 'dot'], default='cosine', help='similarity of --save_neighbors (default cosine)')),
+]
 
 
 def build_parser():
     ap = argparse.ArgumentParser(description='Train a GRU4Rec model on an MI355X (or load one) and report Recall@N / MRR@N.')
     ap.add_argument('path', metavar='PATH', help='training data (.tsv / .txt with TAB separators, or a pickled DataFrame) -- or the model file when -l is given')
-    for short, long_, kw in OPTIONS:
+    for short, long_, kw in OPTIONS + NEIGHBOR_OPTIONS:
         ap.add_argument(*([short, long_] if short else [long_]), **kw)
     return ap
 
@@ -163,6 +169,18 @@ def evaluate(model, opts):
             print('Saved the recommendations of {} events to: {}'.format(len(recs['rank']), out))
 
 
+def save_neighbors(model, opts):
+    import numpy as np
+    if not hasattr(model, 'item_neighbors'):
+        print('ERROR. The model class {} does not support --save_neighbors'.format(type(model).__module__))
+        sys.exit(1)
+    started = time.time()
+    ids, scores = model.item_neighbors(k=opts.neighbors_k, metric=opts.neighbors_metric)
+    np.savez(opts.save_neighbors, item_ids=model.itemidmap.index.values, neighbor_ids=ids, scores=scores)
+    print('Saved the {} nearest neighbours ({}) of {} items to: {} ({:.2f}s)'.format(opts.neighbors_k, opts.neighbors_metric, len(ids),
+                                                                                   opts.save_neighbors, time.time() - started))
+
+
 def main(argv=None):
     opts = build_parser().parse_args(argv)
     sources = [opts.parameter_string is not None, opts.parameter_file is not None, bool(opts.load_model)]
@@ -180,6 +198,8 @@ def main(argv=None):
         model = model_cls.loadmodel(opts.path)
     else:
         model = train(model_cls, opts)
+    if opts.save_neighbors:
+        save_neighbors(model, opts)
     if opts.test is not None:
         evaluate(model, opts)
 
