@@ -42,7 +42,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            10: "k_replay_final (g4r_recommend_sessions) reads every row's final state from the buffer of the chunk's LONGEST history",
            11: "k_score_cand (g4r_score_candidates*): a work item past a row's first slice reads the items of the row's first slice",
            12: "the two-stage top-k (g4r_recommend_*_scan) ranks its candidates by the APPROXIMATE bf16 scores: the fp32 re-scoring is skipped",
-           13: "cosine (g4r_similar_items): the candidate's inverse norm is read at the candidate POSITION instead of its item index"}
+           13: "cosine (g4r_similar_items): the candidate's inverse norm is read at the candidate POSITION instead of its item index",
+           14: "k_rollout_feed (g4r_continue_sessions): the sorted insertion drops an item that sorts ABOVE every item already in the row's "
+               "exclusion list, so it is never excluded and can be generated again"}
 
 
 def mutant_path(k):

@@ -15,6 +15,7 @@
 
 #include "g4r_eval_kernels.cuh"
 #include "g4r_topk_kernels.cuh"
+#include "g4r_rollout_kernels.cuh"
 #include "g4r_cand_kernels.cuh"
 #include "g4r_scan_kernels.cuh"
 #include "g4r_sim_kernels.cuh"

@@ -40,6 +40,11 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
         host[1] = (m->sim_valid[0] || m->sim_valid[1]) ? 1.f : 0.f; host[2] = (float)m->sim_builds;
         return 0;
     }
+    else if (s == "continue_steps") {      // g4r_continue_sessions so far: (calls that passed every check, (chunk, step) chains enqueued); a refused call moves neither
+        if (count < 2) return fail("count");
+        host[0] = (float)m->ro_calls; host[1] = (float)m->ro_steps;
+        return 0;
+    }
     else if (s == "events_launches") {      // the last g4r_recommend_events call: (steps, launches that scan the candidate columns, all launches, pieces)
         if (count < 4) return fail("count");
         host[0] = (float)m->ev_steps; host[1] = (float)m->ev_scans; host[2] = (float)m->ev_launches; host[3] = (float)m->ev_pieces;

@@ -156,6 +156,12 @@ struct g4r_model {
     int *r_in = nullptr, *r_perm = nullptr, *r_len = nullptr;
     float* r_scores = nullptr;
     int64_t r_in_cap = 0, r_scores_cap = 0;
+    // multi-step continuation (g4r_continue_sessions): a chunk's [rows][steps][k] output, the rows' fed-back input items and the current
+    // lengths of their growing exclusion lists (the lists themselves: p_xoffs = every row's begin, p_xitems with slack behind each)
+    int *ro_cols = nullptr, *ro_in = nullptr, *ro_xlen = nullptr;
+    float* ro_scores = nullptr;
+    int64_t ro_cols_cap = 0, ro_scores_cap = 0, ro_in_cap = 0, ro_xlen_cap = 0;
+    int64_t ro_calls = 0, ro_steps = 0;          // g4r_get_debug "continue_steps": calls that passed their checks, (chunk, step) chains enqueued
     // per-row candidate scoring (g4r_score_candidates*): one call's (or chunk's) CSR -- row offsets, candidate item indices, scores
     // in CSR order -- the work items of k_score_cand, the top-k lists of k_cand_pack and the selected (position, score) pairs
     long long* c_offs = nullptr;
@@ -246,6 +252,8 @@ static constexpr auto k_topk_fused = k_topk_range<false, false>;         // scor
 static constexpr auto k_topk_stored = k_topk_range<true, false>;         // selection over p_scores (softmax / softmax_logit)
 static constexpr auto k_topk_fused_x = k_topk_range<false, true, TkExcl>;        // the same two with exclusions (g4r_recommend_step_filtered)
 static constexpr auto k_topk_stored_x = k_topk_range<true, true, TkExcl>;
+static constexpr auto k_topk_fused_g = k_topk_range<false, true, TkGrow>;        // the same two with lists that grow on the device (g4r_continue_sessions)
+static constexpr auto k_topk_stored_g = k_topk_range<true, true, TkGrow>;
 static constexpr auto k_topk_rank = k_topk_range<false, false, TkEvents>;        // g4r_recommend_events: k_topk_fused + the rank counters of k_score_count
 static constexpr auto k_topk_rank_x = k_topk_range<false, true, TkEvents>;       // + the session-list / mask exclusions
 static constexpr auto k_topk_stored_ev = k_topk_range<true, true, TkEvents>;     // softmax / softmax_logit with those exclusions (no counters)

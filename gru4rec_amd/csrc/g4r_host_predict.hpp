@@ -1,6 +1,6 @@
 // g4r_host_predict.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
 // instantiated there).  Holds: prediction and evaluation: g4r_predict_*, g4r_rank_targets, g4r_recommend_step(_filtered),
-// g4r_recommend_sessions, g4r_evaluate, g4r_recommend_events.
+// g4r_recommend_sessions, g4r_continue_sessions, g4r_evaluate, g4r_recommend_events.
 // ------------------------------------------------------------------------------------------------ prediction
 int g4r_predict_begin(g4r_model* m, int32_t batch) {
     if (!m || batch < 1) return fail("bad batch");
@@ -224,9 +224,10 @@ static int recommend_check(g4r_model* m, const int32_t* item_idx, int64_t n_sel,
 }
 
 // selection of rows [0, mrows) of hsrc (the top layer's output) into p_tcols / p_tscores, enqueued only.  scores / ldo: the same
-// rows' materialised scores (softmax / softmax_logit), unused otherwise.  ex (device exclusions) NULL: the unfiltered kernels
+// rows' materialised scores (softmax / softmax_logit), unused otherwise.  ex (device exclusions) NULL: the unfiltered kernels;
+// gx (g4r_continue_sessions, instead of ex): exclusions whose per-row lists grow on the device
 static int topk_select(g4r_model* m, const float* hsrc, int32_t mrows, const int* d_items, int64_t n_sel, int32_t k, const TkExcl* ex,
-                       const float* scores, int64_t ldo) {
+                       const float* scores, int64_t ldo, const TkGrow* gx = nullptr) {
     const DevModel& d = m->dm;
     const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
     // column ranges: (row blocks) x (ranges) workgroups, one per compute unit (the LDS of k_topk_range admits one per CU)
@@ -250,7 +251,13 @@ static int topk_select(g4r_model* m, const float* hsrc, int32_t mrows, const int
         }
     }
     const dim3 grid(R, row_blocks);
-    if (sm && !ex)
+    if (gx && sm)
+        hipLaunchKernelGGL(k_topk_stored_g, grid, dim3(256), TK_SMEM_STORED_X, m->stream, (const DevModel*)m->d_dm, hsrc,
+                           (int)mrows, d_items, (long long)n_sel, scores, (long long)ldo, (int)k, tpr, m->p_topk, *gx);
+    else if (gx)
+        hipLaunchKernelGGL(k_topk_fused_g, grid, dim3(256), TK_SMEM_FUSED_X, m->stream, (const DevModel*)m->d_dm, hsrc,
+                           (int)mrows, d_items, (long long)n_sel, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk, *gx);
+    else if (sm && !ex)
         hipLaunchKernelGGL(k_topk_stored, grid, dim3(256), TK_SMEM_STORED, m->stream, (const DevModel*)m->d_dm, hsrc,
                            (int)mrows, d_items, (long long)n_sel, scores, (long long)ldo, (int)k, tpr, m->p_topk);
     else if (sm)
@@ -334,8 +341,10 @@ int g4r_scan_table_release(g4r_model* m) {
 // topk_select's two-stage twin (element-wise final activations only): rows [0, mrows) of hsrc -> p_tcols / p_tscores, enqueued only,
 // no host synchronisation between the stages.  Stage 1: k_scan_bf16 keeps c candidates per row and range, k_scan_merge the row's c.
 // Stage 2: k_score_cand scores them (fp32, bit-identical to g4r_predict_step), k_scan_pack + k_topk_merge return the k best.
+// gx (g4r_continue_sessions, instead of ex): exclusions whose per-row lists grow on the device; work_ready: k_score_cand's work items
+// of an earlier call with the same mrows and c are still in c_work (nothing is uploaded)
 static int topk_select_scan(g4r_model* m, const float* hsrc, int32_t mrows, const int* d_items, int64_t n_sel, int32_t k, int32_t c,
-                            const TkExcl* ex) {
+                            const TkExcl* ex, const TkGrow* gx = nullptr, bool work_ready = false) {
     if (scan_table_ensure(m)) return -1;
     const int row_blocks = cdiv(mrows, SC_BM);
     const int64_t tiles = (n_sel + SCN_TN - 1) / SCN_TN;
@@ -363,24 +372,36 @@ static int topk_select_scan(g4r_model* m, const float* hsrc, int32_t mrows, cons
         }
     }
     // k_score_cand's work items depend on c and the row count only: row r's list is positions [r c, (r + 1) c)
-    m->s_work.clear();
-    for (int r = 0; r < mrows; ++r)
-        for (int p = 0; p < c; p += CS_SLICE) m->s_work.push_back(make_int4(r, r * c + p, r * c + std::min(p + CS_SLICE, (int)c), r * c));
+    if (!work_ready) {
+        m->s_work.clear();
+        for (int r = 0; r < mrows; ++r)
+            for (int p = 0; p < c; p += CS_SLICE) m->s_work.push_back(make_int4(r, r * c + p, r * c + std::min(p + CS_SLICE, (int)c), r * c));
+    }
     if (cand_reserve(m, &m->c_items, &m->c_items_cap, P) || cand_reserve(m, &m->c_scores, &m->c_scores_cap, P) ||
         cand_reserve(m, &m->c_work, &m->c_work_cap, (int64_t)m->s_work.size()) || cand_reserve(m, &m->c_topk, &m->c_topk_cap, (int64_t)mrows * L) ||
         cand_reserve(m, &m->s_cols, &m->s_cols_cap, P) || cand_reserve(m, &m->s_cnt, &m->s_cnt_cap, (int64_t)mrows))
         return -1;
-    HIPCHK(hipMemcpyAsync(m->c_work, m->s_work.data(), m->s_work.size() * sizeof(int4), hipMemcpyHostToDevice, m->stream));
+    if (!work_ready) HIPCHK(hipMemcpyAsync(m->c_work, m->s_work.data(), m->s_work.size() * sizeof(int4), hipMemcpyHostToDevice, m->stream));
     const dim3 grid(R, row_blocks);
     const TkExcl x = ex ? *ex : TkExcl{nullptr, nullptr, nullptr};
 #define SCAN_LAUNCH(N) hipLaunchKernelGGL(k_scan_bf16<N>, grid, dim3(256), SCN_SMEM, m->stream, (const DevModel*)m->d_dm, hsrc, (int)mrows, d_items, \
                                           (long long)n_sel, (const uint4*)m->s_tab, (int)c, tpr, m->p_topk, x)
-    switch (scan_nch(m->dm)) {
-        case 2: SCAN_LAUNCH(2); break;
-        case 4: SCAN_LAUNCH(4); break;
-        default: SCAN_LAUNCH(8); break;
-    }
+#define SCAN_LAUNCH_G(N) hipLaunchKernelGGL((k_scan_bf16<N, TkGrow>), grid, dim3(256), SCN_SMEM, m->stream, (const DevModel*)m->d_dm, hsrc, (int)mrows, \
+                                            d_items, (long long)n_sel, (const uint4*)m->s_tab, (int)c, tpr, m->p_topk, *gx)
+    if (gx)
+        switch (scan_nch(m->dm)) {
+            case 2: SCAN_LAUNCH_G(2); break;
+            case 4: SCAN_LAUNCH_G(4); break;
+            default: SCAN_LAUNCH_G(8); break;
+        }
+    else
+        switch (scan_nch(m->dm)) {
+            case 2: SCAN_LAUNCH(2); break;
+            case 4: SCAN_LAUNCH(4); break;
+            default: SCAN_LAUNCH(8); break;
+        }
 #undef SCAN_LAUNCH
+#undef SCAN_LAUNCH_G
     hipLaunchKernelGGL(k_scan_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->p_topk, R, (int)c, d_items, m->s_cols, m->c_items,
                        m->c_scores, m->s_cnt);
 #if !(defined(G4R_MUTATE) && G4R_MUTATE == 12)      // test build 12: stage 2 ranks by the approximate scores k_scan_merge left there
@@ -426,12 +447,18 @@ int g4r_recommend_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const
 }
 
 // the exclusion checks shared by g4r_recommend_step_filtered / g4r_recommend_sessions: every row's list is checked, sorted and
-// de-duplicated into offs / items (left empty without excl_offs); a row with fewer than k eligible candidate positions is refused
+// de-duplicated into offs / items (left empty without excl_offs); a row with fewer than k eligible candidate positions is refused.
+// grow (g4r_continue_sessions with no_repeat): the items every row's list will gain on the device, each taking one eligible position
 static int excl_pack(g4r_model* m, int32_t mrows, const int32_t* item_idx, int64_t n_sel, int32_t k, const int64_t* excl_offs,
-                     const int32_t* excl_items, const uint32_t* excl_mask, std::vector<long long>& offs, std::vector<int32_t>& items) {
+                     const int32_t* excl_items, const uint32_t* excl_mask, std::vector<long long>& offs, std::vector<int32_t>& items,
+                     int32_t grow = 0) {
     const int64_t I = m->dm.n_items, nw = (I + 31) / 32;
     offs.clear();
     items.clear();
+    // (without lists every row starts empty: row 0 stands for all of them)
+    if (!excl_offs && grow > G4R_EXCLUDE_MAX)
+        return fail("row 0 excludes 0 distinct items and generates " + std::to_string(grow) + " more (steps - 1), more than G4R_EXCLUDE_MAX = " +
+                    std::to_string(G4R_EXCLUDE_MAX));
     if (excl_offs) {
         if (excl_offs[0] < 0) return fail("excl_offs[0] is negative");
         for (int r = 0; r < mrows; ++r)
@@ -450,6 +477,9 @@ static int excl_pack(g4r_model* m, int32_t mrows, const int32_t* item_idx, int64
             if (items.size() - b > G4R_EXCLUDE_MAX)
                 return fail("row " + std::to_string(r) + " excludes " + std::to_string(items.size() - b) + " distinct items, more than G4R_EXCLUDE_MAX = " +
                             std::to_string(G4R_EXCLUDE_MAX));
+            if (items.size() - b + grow > G4R_EXCLUDE_MAX)
+                return fail("row " + std::to_string(r) + " excludes " + std::to_string(items.size() - b) + " distinct items and generates " +
+                            std::to_string(grow) + " more (steps - 1), more than G4R_EXCLUDE_MAX = " + std::to_string(G4R_EXCLUDE_MAX));
             offs[r + 1] = (long long)items.size();
         }
     }
@@ -487,6 +517,9 @@ static int excl_pack(g4r_model* m, int32_t mrows, const int32_t* item_idx, int64
         if (n_cand - gone < k)
             return fail("row " + std::to_string(r) + " has " + std::to_string(n_cand - gone) + " eligible candidate positions, fewer than k = " +
                         std::to_string(k));
+        if (n_cand - gone - grow < k)
+            return fail("row " + std::to_string(r) + " has " + std::to_string(n_cand - gone) + " eligible candidate positions, fewer than k + steps - 1 = " +
+                        std::to_string(k + grow) + " (every generated item takes one)");
     }
     return 0;
 }
@@ -618,11 +651,13 @@ static int replay_chunk_rows(int32_t n) {
 // The checked histories replayed chunk by chunk (C rows per chunk, replay_chunk_rows).  Per chunk: the rows are sorted by history
 // length and stepped on the replay buffers; score(c0, Cc, perm, hsrc) enqueues what the caller computes from the top layer's output
 // hsrc (sorted row r is session c0 + perm[r]); the final states go to out_hidden (NULL: not wanted); the stream is synchronised once
-// and done(c0, Cc, perm) runs on the host.  Shared by g4r_recommend_sessions and g4r_score_candidates_sessions.
+// and done(c0, Cc, perm) runs on the host.  Shared by g4r_recommend_sessions, g4r_score_candidates_sessions and g4r_continue_sessions.
+// final_half (g4r_continue_sessions): score() leaves there the ping-pong half that holds EVERY row's final state after its rollout
+// (-1: the replay's own rule, each row's in H[len & 1]).
 extern "C++" {      // (this file is included inside extern "C")
 template <class S, class F>
 static int replay_chunks(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, int C, const float* const* h0,
-                         float* const* out_hidden, S score, F done) {
+                         float* const* out_hidden, S score, F done, const int* final_half = nullptr) {
     const DevModel& d = m->dm;
     const int L = d.n_layers;
     const GruBufs rb = replay_bufs(m);
@@ -663,9 +698,10 @@ static int replay_chunks(g4r_model* m, const int64_t* hist_offs, const int32_t* 
         if (score(c0, Cc, (const std::vector<int>&)perm, (const float*)m->rhout[L - 1])) return -1;
         if (out_hidden)
             for (int l = 0; l < L; ++l) {
+                const int fh = final_half ? *final_half : -1;
                 hipLaunchKernelGGL(k_replay_final, dim3(cdiv((long long)Cc * d.D[l], 256)), dim3(256), 0, m->stream, m->rio[l],
-                                   (const float*)m->rH[l][0], (const float*)m->rH[l][1], (const int*)m->r_perm, (const int*)m->r_len,
-                                   Cc, d.D[l], T);
+                                   (const float*)m->rH[l][fh < 0 ? 0 : fh], (const float*)m->rH[l][fh < 0 ? 1 : fh], (const int*)m->r_perm,
+                                   (const int*)m->r_len, Cc, d.D[l], T);
                 HIPCHK(hipMemcpyAsync(out_hidden[l] + (size_t)c0 * d.D[l], m->rio[l], (size_t)Cc * d.D[l] * sizeof(float),
                                       hipMemcpyDeviceToHost, m->stream));
             }
@@ -771,6 +807,130 @@ int g4r_recommend_sessions_scan(g4r_model* m, const int64_t* hist_offs, const in
     if (oversample < 1) return fail("oversample must be at least 1 and k * oversample at most G4R_SCAN_CAND_MAX = " + std::to_string(G4R_SCAN_CAND_MAX));
     return recommend_sessions_run(m, hist_offs, hist_items, n, h0, item_idx, n_sel, k, oversample, excl_offs, excl_items, excl_mask,
                                   out_cols, out_scores, out_hidden);
+}
+
+// ------------------------------------------------------------------------------------------------ multi-step continuation
+// g4r_continue_sessions: g4r_recommend_sessions(_scan) followed, per chunk and on the device, by steps - 1 rounds of
+// (winner -> GRU input -> GRU step -> selection).  One synchronisation and one download per chunk whatever `steps` is.
+int g4r_continue_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                          const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample, int32_t steps, int32_t no_repeat,
+                          const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask, int32_t* out_cols,
+                          float* out_scores, float* const* out_hidden) {
+    // ---- every check before any device work
+    if (recommend_check(m, item_idx, n_sel, k, out_cols, out_scores)) return -1;
+    if (steps < 1) return fail("steps must be at least 1");
+    if (oversample < 0) return fail("oversample must be 0 (the exact selection) or at least 1");
+    int32_t scan_c = 0;
+    if (oversample && scan_check(m, item_idx, n_sel, k, oversample, &scan_c)) return -1;
+    HIPCHK(hipSetDevice(m->cfg.device));
+    if (replay_check(m, hist_offs, hist_items, n, h0, out_hidden)) return -1;
+    const DevModel& d = m->dm;
+    if (!item_idx) n_sel = d.n_items;
+    for (int64_t p = 0; item_idx && p < n_sel; ++p)
+        if (item_idx[p] < 0 || item_idx[p] >= d.n_items) return fail("item index out of range");
+    const bool grow = no_repeat != 0 && steps > 1;      // the lists gain items on the device
+    if (no_repeat && item_idx) {
+        // only then does every generated item take exactly one eligible position
+        std::vector<uint32_t> seen(((size_t)d.n_items + 31) / 32, 0u);
+        for (int64_t p = 0; p < n_sel; ++p) {
+            const int32_t i = item_idx[p];
+            if ((seen[i >> 5] >> (i & 31)) & 1u) return fail("no_repeat needs duplicate-free candidates: item index " + std::to_string(i) + " is listed twice");
+            seen[i >> 5] |= 1u << (i & 31);
+        }
+    }
+    std::vector<long long> xoffs;
+    std::vector<int32_t> xitems;
+    const bool excl = excl_offs || excl_mask || grow;
+    if (excl && excl_pack(m, n, item_idx, n_sel, k, excl_offs, excl_items, excl_mask, xoffs, xitems, grow ? steps - 1 : 0)) return -1;
+    const bool lists = excl_offs || grow;
+    ++m->ro_calls;
+    // ---- buffers and the call-wide uploads
+    const int C = replay_chunk_rows(n);
+    const int L = d.n_layers;
+    const bool sm = (d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT);
+    const int64_t ldo = (n_sel + 3) & ~3LL;
+    if (sm && (int64_t)C * ldo > m->r_scores_cap) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        dfree(m, m->r_scores);
+        m->r_scores = nullptr;
+        m->r_scores_cap = 0;
+        if (dalloc(m, &m->r_scores, (size_t)C * ldo, false)) return -1;
+        m->r_scores_cap = (int64_t)C * ldo;
+    }
+    if (item_idx) {
+        if (cand_reserve(m, &m->p_items, &m->p_items_cap, n_sel)) return -1;
+        HIPCHK(hipMemcpyAsync(m->p_items, item_idx, n_sel * sizeof(int), hipMemcpyHostToDevice, m->stream));
+    }
+    const int64_t per_row = (int64_t)steps * k;
+    if (cand_reserve(m, &m->ro_cols, &m->ro_cols_cap, (int64_t)C * per_row) || cand_reserve(m, &m->ro_scores, &m->ro_scores_cap, (int64_t)C * per_row) ||
+        cand_reserve(m, &m->ro_in, &m->ro_in_cap, (int64_t)C) || (grow && cand_reserve(m, &m->ro_xlen, &m->ro_xlen_cap, (int64_t)C)))
+        return -1;
+    const int* d_items = item_idx ? (const int*)m->p_items : (const int*)nullptr;
+    std::vector<int32_t> tcols((size_t)C * per_row);
+    std::vector<float> tscores((size_t)C * per_row);
+    std::vector<long long> coffs;
+    std::vector<int32_t> citems, clen;
+    const GruBufs rb = replay_bufs(m);
+    int final_half = -1;
+    auto score = [&](int c0, int Cc, const std::vector<int>& perm, const float* hsrc) -> int {
+        TkExcl ex{};
+        TkGrow gx{};
+        if (excl) {
+            // the chunk's lists in sorted row order (each already sorted and de-duplicated by excl_pack); growing lists: the begin of
+            // every row's list (steps - 1 slots of slack behind it) instead of the CSR offsets, the lengths apart
+            const int slack = grow ? steps - 1 : 0;
+            coffs.clear();
+            citems.clear();
+            clen.clear();
+            if (!grow) coffs.push_back(0);
+            if (lists)
+                for (int r = 0; r < Cc; ++r) {
+                    const int i = c0 + perm[r];
+                    if (grow) coffs.push_back((long long)citems.size());
+                    if (excl_offs) citems.insert(citems.end(), xitems.begin() + xoffs[i], xitems.begin() + xoffs[i + 1]);
+                    if (grow) {
+                        clen.push_back(excl_offs ? (int32_t)(xoffs[i + 1] - xoffs[i]) : 0);
+                        citems.insert(citems.end(), (size_t)slack, 0);
+                    } else coffs.push_back((long long)citems.size());
+                }
+            if (excl_upload(m, lists, coffs, citems, excl_mask, &ex)) return -1;
+            if (grow) {
+                HIPCHK(hipMemcpyAsync(m->ro_xlen, clen.data(), (size_t)Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
+                gx = TkGrow{ex.offs, (const int*)m->ro_xlen, ex.items, ex.mask};
+            }
+        }
+        const int T = (int)(hist_offs[c0 + perm[0] + 1] - hist_offs[c0 + perm[0]]);      // the chunk's longest history
+        for (int s = 0; s < steps; ++s) {
+            ++m->ro_steps;
+            if (s == 1) {
+                // every row's state into the half of the longest history: from here on all Cc rows step together
+                for (int l = 0; l < L; ++l)
+                    hipLaunchKernelGGL(k_rollout_align, dim3(cdiv((long long)Cc * d.D[l], 256)), dim3(256), 0, m->stream, m->rH[l][T & 1],
+                                       (const float*)m->rH[l][(T & 1) ^ 1], (const int*)m->r_len, Cc, d.D[l], T);
+            }
+            if (s > 0) gru_step(m, rb, (T + s - 1) & 1, (const int*)m->ro_in, Cc);
+            if (sm) score_rows(m, hsrc, Cc, d_items, n_sel, m->r_scores, ldo);
+            if (scan_c > 0) {
+                if (topk_select_scan(m, hsrc, Cc, d_items, n_sel, k, scan_c, (excl && !grow) ? &ex : nullptr, grow ? &gx : nullptr, s > 0)) return -1;
+            } else if (topk_select(m, hsrc, Cc, d_items, n_sel, k, (excl && !grow) ? &ex : nullptr, (const float*)m->r_scores, ldo, grow ? &gx : nullptr))
+                return -1;
+            const bool last = s == steps - 1;
+            hipLaunchKernelGGL(k_rollout_feed, dim3(Cc), dim3(64), 0, m->stream, (const int*)m->p_tcols, (const float*)m->p_tscores, (int)k, (int)steps,
+                               s, d_items, m->ro_cols, m->ro_scores, last ? (int*)nullptr : m->ro_in, gx.beg,
+                               last ? (int*)nullptr : const_cast<int*>(gx.len), const_cast<int*>(gx.items));      // (gx: all NULL unless the lists grow)
+        }
+        final_half = steps > 1 ? ((T + steps - 1) & 1) : -1;
+        HIPCHK(hipMemcpyAsync(tcols.data(), m->ro_cols, (size_t)Cc * per_row * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(tscores.data(), m->ro_scores, (size_t)Cc * per_row * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        return 0;
+    };
+    auto done = [&](int c0, int Cc, const std::vector<int>& perm) {
+        for (int r = 0; r < Cc; ++r) {
+            memcpy(out_cols + (size_t)(c0 + perm[r]) * per_row, tcols.data() + (size_t)r * per_row, (size_t)per_row * sizeof(int32_t));
+            memcpy(out_scores + (size_t)(c0 + perm[r]) * per_row, tscores.data() + (size_t)r * per_row, (size_t)per_row * sizeof(float));
+        }
+    };
+    return replay_chunks(m, hist_offs, hist_items, n, C, h0, out_hidden, score, done, &final_half);
 }
 
 // ------------------------------------------------------------------------------------------------ per-row candidate lists

@@ -60,9 +60,11 @@ __device__ __forceinline__ float scan_thr_float(unsigned long long key) {
 // ring of 64-column k-chunks, and its rows' survivor queues, thresholds and merges (topk_merge_row, lists of length c) are its own.
 // A score is looked at closely only when it is not below its row's threshold score (one float compare per score).
 // Output: ws[(row * gridDim.x + range) * c + j], as k_topk_range with k = c.
-template <int NCH>
+// E: TkExcl, or TkGrow (g4r_continue_sessions: per-row lists that grow on the device between launches).
+template <int NCH, typename E = TkExcl>
 __global__ __launch_bounds__(256) void k_scan_bf16(const DevModel* __restrict__ mp, const float* h, int mrows, const int* item_idx,
-                                                   long long n_sel, const uint4* tab, int c, int tpr, uint2* ws, TkExcl ex) {
+                                                   long long n_sel, const uint4* tab, int c, int tpr, uint2* ws, E xarg) {
+    const TkExcl ex = tk_excl(xarg);
     constexpr int KS = 4 * NCH;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const DevModel& m = *mp;
@@ -84,10 +86,18 @@ __global__ __launch_bounds__(256) void k_scan_bf16(const DevModel* __restrict__ 
     const int lrow = 32 * wid + r32, grow = rbase + lrow;      // this lane's row: local, global
     if (half == 0) {
         s_qn[lrow] = 0; s_ln[lrow] = 0; s_thr[lrow] = 0ull;
-        const bool on = ex.offs && grow < mrows;
-        const long long b = on ? ex.offs[grow] : 0ll;
-        s_xb[lrow] = b;
-        s_xn[lrow] = on ? (int)(ex.offs[grow + 1] - b) : 0;
+        if constexpr (tk_is_grow<E>::value) {
+            long long b;
+            int n;
+            tk_row_list(xarg, grow, mrows, b, n);
+            s_xb[lrow] = b;
+            s_xn[lrow] = n;
+        } else {
+            const bool on = ex.offs && grow < mrows;
+            const long long b = on ? ex.offs[grow] : 0ll;
+            s_xb[lrow] = b;
+            s_xn[lrow] = on ? (int)(ex.offs[grow + 1] - b) : 0;
+        }
     }
     // B operand: lane l holds h[row l & 31][16 ks + 8 (l >> 5) + j]
     const int D = m.Dtop;
@@ -259,3 +269,6 @@ __global__ __launch_bounds__(256) void k_scan_pack(const float* sc, const int* c
 template __global__ void k_scan_bf16<2>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkExcl);
 template __global__ void k_scan_bf16<4>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkExcl);
 template __global__ void k_scan_bf16<8>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkExcl);
+template __global__ void k_scan_bf16<2, TkGrow>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkGrow);
+template __global__ void k_scan_bf16<4, TkGrow>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkGrow);
+template __global__ void k_scan_bf16<8, TkGrow>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkGrow);

@@ -5,6 +5,7 @@
 //   k_topk_rank    k_topk_fused for g4r_recommend_events: the same scan also counts, per row, the columns whose score is greater
 //                  than / equal to the row's target score (the counters of k_score_all<.., COUNT = true>, finished by k_rank_counts)
 //   k_events_merge k_topk_merge writing its row, the row's rank and target score at the event's place in the call's output
+// The TkGrow instantiations (g4r_continue_sessions) are the EXCL ones reading per-row lists that grow on the device between launches.
 // The EXCL = true instantiations of k_topk_range (behind g4r_recommend_step_filtered) drop excluded items where a survivor queue is
 // merged into its row's list (topk_merge_row): a global bit mask over item indices and a sorted per-row list (at most
 // G4R_EXCLUDE_MAX items).  The EXCL = false instantiations are the unfiltered kernels, instruction for instruction.
@@ -74,6 +75,26 @@ __device__ __forceinline__ TkEvents tk_events(TkExcl) { return TkEvents{}; }
 __device__ __forceinline__ TkEvents tk_events(TkEvents e) { return e; }
 template <typename... X> struct tk_is_events { static constexpr bool value = false; };
 template <> struct tk_is_events<TkEvents> { static constexpr bool value = true; };
+
+// The trailing argument of the g4r_continue_sessions instantiations (k_topk_range<.., true, TkGrow>, k_scan_bf16<.., TkGrow>): TkExcl
+// whose per-row lists GROW on the device between launches.  Row r's sorted, duplicate-free list is items[beg[r] .. beg[r] + len[r]);
+// the host leaves slack behind every list, k_rollout_feed (g4r_rollout_kernels.cuh) inserts into it and bumps len[r].  A type of its
+// own, so that the TkExcl instantiations keep their kernel arguments and their code.
+struct TkGrow { const long long* beg; const int* len; const int* items; const unsigned* mask; };
+__device__ __forceinline__ TkExcl tk_excl(TkGrow g) { return TkExcl{nullptr, g.items, g.mask}; }
+__device__ __forceinline__ TkEvents tk_events(TkGrow) { return TkEvents{}; }
+// row `row`'s list start and length (0, 0 for a row past the call's) as the range kernels stage them
+__device__ __forceinline__ void tk_row_list(const TkGrow& g, int row, int mrows, long long& b, int& n) {
+    const bool on = row < mrows;
+    b = on ? g.beg[row] : 0ll;
+    n = on ? g.len[row] : 0;
+}
+template <typename... X> struct tk_is_grow { static constexpr bool value = false; };
+template <> struct tk_is_grow<TkGrow> { static constexpr bool value = true; };
+__device__ __forceinline__ TkGrow tk_grow() { return TkGrow{}; }
+__device__ __forceinline__ TkGrow tk_grow(TkExcl) { return TkGrow{}; }
+__device__ __forceinline__ TkGrow tk_grow(TkEvents) { return TkGrow{}; }
+__device__ __forceinline__ TkGrow tk_grow(TkGrow g) { return g; }
 
 // One wave merges the survivor queue of local row r into the row's sorted list L (global, length n <= k): the queue is sorted in
 // registers (bitonic over the 64 lanes), then every element's place in the union is its own index plus the number of elements of
@@ -199,6 +220,14 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
         if (tid < SC_BM) {
             const int4 w = (ev.seen && rbase + tid < mrows) ? ev.seen[rbase + tid] : make_int4(0, 0, 0, 0);
             s_xb[tid] = w.x; s_xn[tid] = w.y; s_xp[tid] = w.z;
+        }
+    } else if constexpr (EXCL && tk_is_grow<X...>::value) {
+        if (tid < SC_BM) {
+            long long b;
+            int n;
+            tk_row_list(tk_grow(xs...), rbase + tid, mrows, b, n);
+            s_xb[tid] = b;
+            s_xn[tid] = n;
         }
     } else if constexpr (EXCL)
         if (tid < SC_BM) {
@@ -438,6 +467,8 @@ template __global__ void k_topk_range<false, false>(const DevModel*, const float
 template __global__ void k_topk_range<true, false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
 template __global__ void k_topk_range<false, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);
 template __global__ void k_topk_range<true, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);
+template __global__ void k_topk_range<false, true, TkGrow>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkGrow);
+template __global__ void k_topk_range<true, true, TkGrow>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkGrow);
 template __global__ void k_topk_range<false, false, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
 template __global__ void k_topk_range<false, true, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
 template __global__ void k_topk_range<true, true, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);

@@ -816,9 +816,10 @@ class GRU4Rec:
         seen = self._seen_after(plan) if exclude_seen else None
         return self._pack_exclusions(len(np.ravel(plan[3])), k, cand_idx, seen, 'the items seen', exclude, exclude_per_row)
 
-    def _pack_exclusions(self, rows, k, cand_idx, extra, extra_name, exclude, exclude_per_row):
+    def _pack_exclusions(self, rows, k, cand_idx, extra, extra_name, exclude, exclude_per_row, grow=0):
         """_exclusions for `rows` rows; extra: (rows, item indices) the call adds to the per-row lists (the items seen, the
-        histories) or None; extra_name names them in the G4R_EXCLUDE_MAX error."""
+        histories) or None; extra_name names them in the G4R_EXCLUDE_MAX error.  grow (continue_sessions with no_repeat): the items
+        every row's list gains on the device, one eligible candidate position each."""
         n_items = len(self.itemidmap)
         pr, pi = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
         if exclude_per_row is not None:
@@ -857,6 +858,15 @@ class GRU4Rec:
         short = np.flatnonzero(elig < k)
         if len(short):
             raise ValueError('row %d has %d eligible candidate positions, fewer than k = %d' % (short[0], elig[short[0]], k))
+        if grow:
+            big = np.flatnonzero(counts + grow > _native.G4R_EXCLUDE_MAX)
+            if len(big):
+                raise ValueError('row %d excludes %d distinct items (exclude_per_row and %s) and generates steps - 1 = %d more, more than '
+                                 'G4R_EXCLUDE_MAX = %d' % (big[0], counts[big[0]], extra_name, grow, _native.G4R_EXCLUDE_MAX))
+            short = np.flatnonzero(elig - grow < k)
+            if len(short):
+                raise ValueError('row %d has %d eligible candidate positions, fewer than k + steps - 1 = %d (every generated item takes '
+                                 'one)' % (short[0], elig[short[0]], k + grow))
         offs = items = mask = None
         if extra is not None or exclude_per_row is not None:
             offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
@@ -1008,6 +1018,64 @@ class GRU4Rec:
             out = m.recommend_sessions(offs, hidx, iidx, int(k), xoffs, xitems, mask, hidden=h0, return_hidden=return_hidden)
         else:
             out = m.recommend_sessions(offs, hidx, iidx, int(k), xoffs, xitems, mask, hidden=h0, return_hidden=return_hidden, oversample=over)
+        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
+        if not return_hidden:
+            return cand[out[0]], out[1]
+        return cand[out[0]], out[1], [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(out[2], self.layers)]
+
+    def continue_sessions(self, histories, steps, k=1, no_repeat=True, predict_for_item_ids=None, exclude=None, exclude_per_row=None,
+                          hidden=None, return_hidden=False, scan='fp32', oversample=8):
+        """The next `steps` items of N whole sessions in one stateless call: (item_ids[N, steps, k], scores[N, steps, k] float32),
+        plus the hidden state with return_hidden=True.  Not in the reference.
+
+        The histories are replayed as in recommend_sessions (from zero, or from `hidden`); step 0 selects every row's k best next
+        items; the best one, [:, s, 0], is fed back as the row's next input and step s + 1 selects again: `steps` selections,
+        steps - 1 fed-back items.  [:, :, 0] is the continuation, the other k - 1 columns are the alternatives at that step.  The
+        feedback runs on the device: between steps nothing returns to the host.
+
+        The result equals, item ids, score bits and hidden-state bits, a loop of recommend_sessions calls: the histories with
+        exclude_history=no_repeat first, then steps - 1 times the one-item histories [[previous winner]] from the returned hidden
+        state, with exclude_per_row = (history + generated items so far, when no_repeat) + the caller's exclude_per_row.
+
+          no_repeat        row i never receives an item of histories[i] nor an item it has generated itself.  False: only exclude /
+                           exclude_per_row apply, and a row may loop.
+          return_hidden    also return the state that produced the LAST step's scores: after the history and the steps - 1 fed-back
+                           items (the last winner has not been consumed).  So continue_sessions(h, a + b)[:, a:] equals
+                           continue_sessions([[path[i, a - 1]]], b, hidden=H_a, exclude_per_row=h_i + path[i, :a]).
+          k, predict_for_item_ids, exclude, exclude_per_row, hidden, scan, oversample: as in recommend_sessions, with its refusals.
+                           softmax / softmax_logit scores are not renormalised over the remaining items.
+
+        Everything is checked before any device work and the prediction state is neither read nor changed.  steps must be an integer
+        >= 1.  With no_repeat, predict_for_item_ids must be duplicate-free (every fed-back item then removes exactly one eligible
+        position), every row's distinct excluded items plus steps - 1 must not exceed G4R_EXCLUDE_MAX, and every row must keep at least
+        k eligible candidate positions at the last step (eligible - (steps - 1) >= k: no list ever holds a pad); each failure raises
+        ValueError naming the row."""
+        if self.error_during_train:
+            raise Exception
+        try:
+            steps_ok = not isinstance(steps, bool) and int(steps) == steps and steps >= 1
+        except (TypeError, ValueError):
+            steps_ok = False
+        if not steps_ok:
+            raise ValueError('steps = %r: it must be an integer >= 1' % (steps,))
+        steps = int(steps)
+        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
+        if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
+            raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        over = self._scan_oversample(scan, oversample, k)
+        N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
+        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
+        if no_repeat and iidx is not None and len(np.unique(iidx)) != len(iidx):
+            raise ValueError('no_repeat needs duplicate-free predict_for_item_ids: every generated item must take exactly one candidate '
+                             'position')
+        xoffs = xitems = mask = None
+        if no_repeat or exclude is not None or exclude_per_row is not None:
+            hist_rows = (np.repeat(np.arange(N), lens), hidx) if no_repeat else None
+            xoffs, xitems, mask = self._pack_exclusions(N, int(k), iidx, hist_rows, 'the history', exclude, exclude_per_row,
+                                                        grow=steps - 1 if no_repeat else 0)
+        m = self._ensure_model()
+        out = m.continue_sessions(offs, hidx, iidx, int(k), steps, bool(no_repeat), xoffs, xitems, mask, hidden=h0,
+                                  return_hidden=return_hidden, oversample=over)
         cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
         if not return_hidden:
             return cand[out[0]], out[1]

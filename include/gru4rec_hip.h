@@ -230,6 +230,23 @@ int g4r_recommend_sessions_scan(g4r_model* m, const int64_t* hist_offs, const in
                                 float* const* out_hidden);
 int g4r_scan_table_release(g4r_model* m);
 
+/* not in the reference: multi-step continuation of n whole sessions, stateless.  The arguments of g4r_recommend_sessions_scan
+ * (oversample = 0: the exact selection of g4r_recommend_sessions) plus steps >= 1 and no_repeat; out_cols / out_scores hold
+ * n * steps * k entries, [session][step][rank].  Step 0 is g4r_recommend_sessions(_scan) of the histories.  For s >= 1 the item of
+ * step s - 1's best column (item_idx[column], or the column) is fed to the GRU as the session's next input and the k best are selected
+ * again -- bit for bit what g4r_recommend_sessions(_scan) returns for the one-item history {that item}, started from the state the
+ * previous step left, with the same candidates, mask and lists.  no_repeat != 0: every item fed back is also added to its session's
+ * exclusion list, so it is never returned to that session again (the history itself is excluded only where the caller lists it in
+ * excl_offs / excl_items); it needs a duplicate-free item_idx, at most G4R_EXCLUDE_MAX - (steps - 1) distinct listed items per
+ * session and at least k + steps - 1 eligible candidate positions per session (no list ever holds a pad).  out_hidden receives the
+ * state that produced the LAST step's scores: after the history and the steps - 1 fed-back items; the last winner is not consumed.
+ * Everything is checked before any launch; the prediction state is neither read nor changed.  The feedback runs on the device: one
+ * stream synchronisation and one download per chunk of rows, whatever steps is. */
+int g4r_continue_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                          const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample, int32_t steps, int32_t no_repeat,
+                          const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask, int32_t* out_cols,
+                          float* out_scores, float* const* out_hidden);
+
 /* not in the reference: item-to-item neighbours in the model's own embedding space -- the k candidates most similar to each of n
  * query items.  Stateless: the prediction state and the training state are neither read nor changed.
  *   table T     space = G4R_SPACE_OUTPUT: Wy, rows of layers[n_layers - 1] floats.  G4R_SPACE_INPUT: E when embed_mode is
