@@ -32,7 +32,10 @@ extern "C" {
 #include "g4r_host_create.hpp"
 #include "g4r_host_plan.hpp"
 #include "g4r_host_step.hpp"
+#include "g4r_host_topk.hpp"
 #include "g4r_host_predict.hpp"
+#include "g4r_host_sessions.hpp"
+#include "g4r_host_events.hpp"
 #include "g4r_host_similar.hpp"
 #include "g4r_host_comm.hpp"
 #include "g4r_host_sync.hpp"

@@ -31,7 +31,7 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     }
     else if (s == "scan_table") {      // (bytes the bf16 shadow table holds, 1 if it is valid, builds so far)
         if (count < 3) return fail("count");
-        host[0] = (float)((double)m->s_tab_units * 16.0); host[1] = m->s_tab_valid ? 1.f : 0.f; host[2] = (float)m->s_tab_builds;
+        host[0] = (float)((double)m->s_tab.cap * 16.0); host[1] = m->s_tab_valid ? 1.f : 0.f; host[2] = (float)m->s_tab_builds;
         return 0;
     }
     else if (s == "sim_norms") {      // (bytes the inverse norms of g4r_similar_items hold, 1 if a table's are valid, builds so far)

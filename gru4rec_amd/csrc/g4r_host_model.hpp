@@ -74,6 +74,16 @@ struct StepKernels {
     int finish_rows;                      // k_finish_rows: layer 0's dy from K-slice partial sums, ahead of k_update / k_dense_grad
 };
 
+// A device array that only grows: what the inference entries keep between calls (g4r_model's p_*, r_*, ro_*, c_*, s_*, sim_*), sized by
+// need, never by a batch.  reserve() is defined below, next to dalloc / dfree.  (The reconciliation keeps a separate kind, with
+// headroom and a pinned-host form: g4r_model::Scratch / scratch_ensure, g4r_host_sync.hpp.)
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    int64_t cap = 0;      // elements
+    int reserve(g4r_model* m, int64_t n);
+};
+
 struct g4r_model {
     g4r_config cfg;
     DevModel dm;                 // host master copy of the device-resident model descriptor
@@ -132,19 +142,19 @@ struct g4r_model {
     float* pH[G4R_MAX_LAYERS][2] = {{nullptr}};
     float* phout[G4R_MAX_LAYERS] = {nullptr};
     float *pVc[G4R_MAX_LAYERS] = {nullptr}, *pz[G4R_MAX_LAYERS] = {nullptr}, *pHr[G4R_MAX_LAYERS] = {nullptr};
-    int *p_in = nullptr, *p_items = nullptr, *p_tgt = nullptr, *p_keep = nullptr;
+    int *p_in = nullptr, *p_tgt = nullptr, *p_keep = nullptr;
+    DevBuf<int> p_items;                         // the candidate items of one call (cand_upload)
     unsigned char* p_zero = nullptr;
-    float *p_scores = nullptr, *p_ranks = nullptr;
+    float* p_ranks = nullptr;
+    DevBuf<float> p_scores;
     int* p_cnt = nullptr;                        // [pbatch][2] streamed (greater, equal) counts of the evaluation
-    int64_t p_scores_cap = 0, p_items_cap = 0, p_nsel = 0, p_ldo = 0;
-    uint2* p_topk = nullptr;                     // [rows][ranges][k] per-range lists of g4r_recommend_step (k_topk_range)
-    int* p_tcols = nullptr;                      // [rows][k] its result
-    float* p_tscores = nullptr;
-    int64_t p_topk_cap = 0, p_tout_cap = 0;
-    long long* p_xoffs = nullptr;                // exclusions of g4r_recommend_step_filtered: [rows + 1] offsets into p_xitems,
-    int* p_xitems = nullptr;                     // the rows' sorted item lists,
-    unsigned* p_xmask = nullptr;                 // the global item bit mask
-    int64_t p_xoffs_cap = 0, p_xitems_cap = 0, p_xmask_cap = 0;
+    int64_t p_nsel = 0, p_ldo = 0;
+    DevBuf<uint2> p_topk;                        // [rows][ranges][k] per-range lists of g4r_recommend_step (k_topk_range)
+    DevBuf<int> p_tcols;                         // [rows][k] its result (the two are reserved together)
+    DevBuf<float> p_tscores;
+    DevBuf<long long> p_xoffs;                   // exclusions of g4r_recommend_step_filtered: [rows + 1] offsets into p_xitems,
+    DevBuf<int> p_xitems;                        // the rows' sorted item lists,
+    DevBuf<unsigned> p_xmask;                    // the global item bit mask
     // stateless replay of g4r_recommend_sessions, apart from the prediction state above: per layer a hidden ping-pong, the output,
     // the GRU scratch and the staging of the supplied initial / the final rows (chunk order), all for r_cap rows; the step-major
     // input items, the sort map and lengths of a chunk; its own score matrix (softmax / softmax_logit)
@@ -153,44 +163,39 @@ struct g4r_model {
     float* rhout[G4R_MAX_LAYERS] = {nullptr};
     float *rVc[G4R_MAX_LAYERS] = {nullptr}, *rz[G4R_MAX_LAYERS] = {nullptr}, *rHr[G4R_MAX_LAYERS] = {nullptr};
     float* rio[G4R_MAX_LAYERS] = {nullptr};
-    int *r_in = nullptr, *r_perm = nullptr, *r_len = nullptr;
-    float* r_scores = nullptr;
-    int64_t r_in_cap = 0, r_scores_cap = 0;
+    int *r_perm = nullptr, *r_len = nullptr;
+    DevBuf<int> r_in;
+    DevBuf<float> r_scores;
     // multi-step continuation (g4r_continue_sessions): a chunk's [rows][steps][k] output, the rows' fed-back input items and the current
     // lengths of their growing exclusion lists (the lists themselves: p_xoffs = every row's begin, p_xitems with slack behind each)
-    int *ro_cols = nullptr, *ro_in = nullptr, *ro_xlen = nullptr;
-    float* ro_scores = nullptr;
-    int64_t ro_cols_cap = 0, ro_scores_cap = 0, ro_in_cap = 0, ro_xlen_cap = 0;
+    DevBuf<int> ro_cols, ro_in, ro_xlen;
+    DevBuf<float> ro_scores;
     int64_t ro_calls = 0, ro_steps = 0;          // g4r_get_debug "continue_steps": calls that passed their checks, (chunk, step) chains enqueued
     // per-row candidate scoring (g4r_score_candidates*): one call's (or chunk's) CSR -- row offsets, candidate item indices, scores
     // in CSR order -- the work items of k_score_cand, the top-k lists of k_cand_pack and the selected (position, score) pairs
-    long long* c_offs = nullptr;
-    int* c_items = nullptr;
-    float* c_scores = nullptr;
-    int4* c_work = nullptr;
-    uint2* c_topk = nullptr;
-    int* c_tpos = nullptr;
-    float* c_tscores = nullptr;
-    int64_t c_offs_cap = 0, c_items_cap = 0, c_scores_cap = 0, c_work_cap = 0, c_topk_cap = 0, c_tpos_cap = 0, c_tscores_cap = 0;
+    DevBuf<long long> c_offs;
+    DevBuf<int> c_items;
+    DevBuf<float> c_scores;
+    DevBuf<int4> c_work;
+    DevBuf<uint2> c_topk;
+    DevBuf<int> c_tpos;
+    DevBuf<float> c_tscores;
     // two-stage top-k (g4r_recommend_step_scan / g4r_recommend_sessions_scan): the bf16 shadow table of Wy in MFMA fragment order
     // (g4r_scan_kernels.cuh), built on first use and again after anything that may have changed Wy (weights_changed); the
     // candidates' columns and counts of one call or chunk; the host copy of k_score_cand's work items
-    uint4* s_tab = nullptr;
-    int64_t s_tab_units = 0, s_tab_builds = 0;
+    DevBuf<uint4> s_tab;                         // (cap: 16-byte units)
+    int64_t s_tab_builds = 0;
     bool s_tab_valid = false;
-    int* s_cols = nullptr;
-    int* s_cnt = nullptr;
-    int64_t s_cols_cap = 0, s_cnt_cap = 0;
+    DevBuf<int> s_cols;
+    DevBuf<int> s_cnt;
     std::vector<int4> s_work;
     // item neighbours (g4r_similar_items): the inverse row norms of the item tables (0: Wy, 1: E), built on the first cosine call and
     // again after anything that may have changed the tables (weights_changed); the query items of one chunk and their rows
     float* sim_inv[2] = {nullptr, nullptr};
     bool sim_valid[2] = {false, false};
     int64_t sim_builds = 0;
-    int* sim_q = nullptr;
-    int64_t sim_q_cap = 0;
-    float* sim_rows = nullptr;                   // [chunk rows][W] the chunk's query rows (k_sim_gather)
-    int64_t sim_rows_cap = 0;
+    DevBuf<int> sim_q;
+    DevBuf<float> sim_rows;                      // [chunk rows][W] the chunk's query rows (k_sim_gather)
     unsigned tie_ctr = 0;                       // evaluation step counter of the 'tiebreaking' noise stream
     // the last g4r_recommend_events call (g4r_get_debug "events_launches"): its steps, the launches whose grid spans the candidate
     // columns, all its launches, the pieces its lists came back in
@@ -219,6 +224,7 @@ struct g4r_model {
     int sync_every_dev = 0;                      // > 0: g4r_train_steps reconciles the (dense-form) item tables itself every that many steps
     int64_t since_sync = 0, n_dev_syncs = 0;
     // scratch of the packed-parts reconciliation, kept between calls (a call used to pay five hipMalloc / hipFree pairs)
+    // (the inference entries' grow-only arrays are another kind: DevBuf, above)
     struct Scratch { void* p = nullptr; size_t cap = 0; bool host = false; };
     Scratch sc_ids, sc_blk, sc_cnt, sc_all, sc_send, sc_pack, sc_recv, sc_hall;      // sc_hall: pinned host copy of the gathered id lists
     float* d_dense[2] = {nullptr, nullptr};      // dense reconciliation buffers [n_items][sum of plane widths + 1] per table group (small catalogues)
@@ -245,6 +251,37 @@ static void dfree(g4r_model* m, void* p) {
     if (it != m->allocs.end()) m->allocs.erase(it);
     (void)hipFree(p);
 }
+// Room for n elements; the contents are not kept.  The stream is drained before the old array goes (kernels enqueued on it may still
+// read it), and the handle forgets the array before the new one is asked for: a failed hipMalloc leaves p = NULL, cap = 0, which the
+// next call's reserve() sees, never a freed pointer that passes the capacity test.
+template <class T>
+int DevBuf<T>::reserve(g4r_model* m, int64_t n) {
+    if (n <= cap) return 0;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    dfree(m, p);
+    p = nullptr; cap = 0;
+    if (dalloc(m, &p, (size_t)n, false)) return -1;
+    cap = n;
+    return 0;
+}
+// The device temporaries of one call (g4r_evaluate, g4r_recommend_events): get() is dalloc; all of them are freed when the owner goes
+// out of scope, whichever return ends the call
+struct CallTemps {
+    g4r_model* m;
+    std::vector<void*> held;
+    explicit CallTemps(g4r_model* m_) : m(m_) {}
+    CallTemps(const CallTemps&) = delete;
+    CallTemps& operator=(const CallTemps&) = delete;
+    ~CallTemps() { for (void* q : held) dfree(m, q); }
+    template <class T>
+    int get(T** p, size_t n, bool zero = true) {
+        if (dalloc(m, p, n, zero)) return -1;
+        held.push_back(*p);
+        return 0;
+    }
+};
+// softmax / softmax_logit: a score needs its whole row (maximum, sum); the other final activations are element-wise (gru4rec.py:499-500)
+static inline bool is_softmax(const DevModel& d) { return d.final_act == G4R_ACT_SOFTMAX || d.final_act == G4R_ACT_SOFTMAX_LOGIT; }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static constexpr auto k_score_store = k_score_all<32, false>;     // scores -> memory
 static constexpr auto k_score_count = k_score_all<32, true>;      // scores compared with the row's target on the fly

@@ -32,7 +32,7 @@ static int sim_norms_ensure(g4r_model* m, int tab, const float* T, int W) {
 
 int g4r_similar_items(g4r_model* m, int32_t space, int32_t metric, const int32_t* q_idx, int64_t n, const int32_t* item_idx, int64_t n_sel,
                       int32_t k, int32_t exclude_self, const uint32_t* excl_mask, int32_t* out_cols, float* out_scores) {
-    // ---- every check before any device work
+    // ---- every check before any device work (cand_upload, among them, stages the candidate items: no state to advance)
     if (!m || !q_idx || !out_cols || !out_scores) return fail("null argument");
     if (metric != G4R_SIM_DOT && metric != G4R_SIM_COSINE) return fail("metric must be G4R_SIM_DOT (0) or G4R_SIM_COSINE (1)");
     const float* T = nullptr;
@@ -48,8 +48,9 @@ int g4r_similar_items(g4r_model* m, int32_t space, int32_t metric, const int32_t
     if (n_cand > INT32_MAX) return fail("more than 2^31 - 1 candidates");
     for (int64_t i = 0; i < n; ++i)
         if (q_idx[i] < 0 || q_idx[i] >= I) return fail("query item index out of range (query " + std::to_string(i) + ")");
-    for (int64_t p = 0; item_idx && p < n_sel; ++p)
-        if (item_idx[p] < 0 || item_idx[p] >= I) return fail("item index out of range");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    const int* d_items = nullptr;
+    if (cand_upload(m, item_idx, &n_sel, &d_items)) return -1;
     // eligible candidate positions of a query: all - the positions of masked items - (exclude_self) the positions of its own item
     auto masked = [&](int32_t i) { return excl_mask && ((excl_mask[i >> 5] >> (i & 31)) & 1u); };
     int64_t n_masked = 0;
@@ -84,55 +85,35 @@ int g4r_similar_items(g4r_model* m, int32_t space, int32_t metric, const int32_t
                         " eligible candidate positions, fewer than k = " + std::to_string(k));
     }
     // ---- buffers and the call-wide uploads
-    HIPCHK(hipSetDevice(m->cfg.device));
     const int env_c = env_int("G4R_SIM_CHUNK", 0);
     const int C = (int)std::min<int64_t>(n, env_c > 0 ? std::min(env_c, G4R_SIM_CHUNK_ROWS) : G4R_SIM_CHUNK_ROWS);
     const bool cosine = metric == G4R_SIM_COSINE;
     if (cosine && sim_norms_ensure(m, tab, T, W)) return -1;
-    const int* d_items = nullptr;
-    if (item_idx) {
-        if (cand_reserve(m, &m->p_items, &m->p_items_cap, n_sel)) return -1;
-        HIPCHK(hipMemcpyAsync(m->p_items, item_idx, n_sel * sizeof(int), hipMemcpyHostToDevice, m->stream));
-        d_items = m->p_items;
-    }
     TkExcl ex{};
     if (excl_mask && excl_upload(m, false, std::vector<long long>(), std::vector<int32_t>(), excl_mask, &ex)) return -1;
-    // geometry of a chunk of `rows` rows: row blocks x column ranges, about one workgroup per compute unit
-    const int64_t tiles = (n_cand + TK_TN - 1) / TK_TN;
-    auto geometry = [&](int rows, int* RB, int* tpr, int* R) {
-        *RB = cdiv(rows, SC_BM);
-        const int64_t R0 = std::min<int64_t>(std::max(1, m->n_cu / *RB), tiles);
-        *tpr = (int)((tiles + R0 - 1) / R0);
-        *R = (int)((tiles + *tpr - 1) / *tpr);
-    };
-    if (cand_reserve(m, &m->sim_q, &m->sim_q_cap, (int64_t)C) || cand_reserve(m, &m->sim_rows, &m->sim_rows_cap, (int64_t)C * W)) return -1;
-    if ((int64_t)C * k > m->p_tout_cap) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(m, m->p_tcols); dfree(m, m->p_tscores);
-        m->p_tcols = nullptr; m->p_tscores = nullptr;
-        m->p_tout_cap = 0;
-        if (dalloc(m, &m->p_tcols, (size_t)C * k, false) || dalloc(m, &m->p_tscores, (size_t)C * k, false)) return -1;
-        m->p_tout_cap = (int64_t)C * k;
-    }
+    if (m->sim_q.reserve(m, (int64_t)C) || m->sim_rows.reserve(m, (int64_t)C * W) || m->p_tcols.reserve(m, (int64_t)C * k) ||
+        m->p_tscores.reserve(m, (int64_t)C * k))
+        return -1;
     // ---- chunk by chunk: upload the query items, gather their rows, scan, merge, copy the chunk's rows back (one synchronisation per chunk)
     for (int64_t c0 = 0; c0 < n; c0 += C) {
         const int Cc = (int)std::min<int64_t>(C, n - c0);
-        int RB, tpr, R;
-        geometry(Cc, &RB, &tpr, &R);
-        if (cand_reserve(m, &m->p_topk, &m->p_topk_cap, (int64_t)Cc * R * k)) return -1;      // (grows on the first chunk at most, and on a shorter last one)
-        HIPCHK(hipMemcpyAsync(m->sim_q, q_idx + c0, Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
-        hipLaunchKernelGGL(k_sim_gather, dim3(cdiv((long long)Cc * (W / 4), 256)), dim3(256), 0, m->stream, T, W, (const int*)m->sim_q, Cc, m->sim_rows);
+        // row blocks x column ranges, about one workgroup per compute unit
+        const TkRanges g = tk_ranges(m, Cc, n_cand, TK_TN);
+        const int RB = g.row_blocks, tpr = g.tpr, R = g.R;
+        if (m->p_topk.reserve(m, (int64_t)Cc * R * k)) return -1;      // (grows on the first chunk at most, and on a shorter last one)
+        HIPCHK(hipMemcpyAsync(m->sim_q.p, q_idx + c0, Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
+        hipLaunchKernelGGL(k_sim_gather, dim3(cdiv((long long)Cc * (W / 4), 256)), dim3(256), 0, m->stream, T, W, (const int*)m->sim_q.p, Cc, m->sim_rows.p);
         const dim3 grid((unsigned)(R * RB));
         if (cosine)
-            hipLaunchKernelGGL(k_sim_range<true>, grid, dim3(256), SIM_SMEM, m->stream, T, W, (int)I, (const int*)m->sim_q, (const float*)m->sim_rows, Cc, d_items,
-                               (long long)n_cand, (const float*)m->sim_inv[tab], ex.mask, exclude_self ? 1 : 0, (int)k, tpr, R, RB, m->p_topk);
+            hipLaunchKernelGGL(k_sim_range<true>, grid, dim3(256), SIM_SMEM, m->stream, T, W, (int)I, (const int*)m->sim_q.p, (const float*)m->sim_rows.p, Cc, d_items,
+                               (long long)n_cand, (const float*)m->sim_inv[tab], ex.mask, exclude_self ? 1 : 0, (int)k, tpr, R, RB, m->p_topk.p);
         else
-            hipLaunchKernelGGL(k_sim_range<false>, grid, dim3(256), SIM_SMEM, m->stream, T, W, (int)I, (const int*)m->sim_q, (const float*)m->sim_rows, Cc, d_items,
-                               (long long)n_cand, (const float*)nullptr, ex.mask, exclude_self ? 1 : 0, (int)k, tpr, R, RB, m->p_topk);
-        hipLaunchKernelGGL(k_topk_merge, dim3(Cc), dim3(256), 0, m->stream, (const uint2*)m->p_topk, R, (int)k, m->p_tcols, m->p_tscores);
+            hipLaunchKernelGGL(k_sim_range<false>, grid, dim3(256), SIM_SMEM, m->stream, T, W, (int)I, (const int*)m->sim_q.p, (const float*)m->sim_rows.p, Cc, d_items,
+                               (long long)n_cand, (const float*)nullptr, ex.mask, exclude_self ? 1 : 0, (int)k, tpr, R, RB, m->p_topk.p);
+        hipLaunchKernelGGL(k_topk_merge, dim3(Cc), dim3(256), 0, m->stream, (const uint2*)m->p_topk.p, R, (int)k, m->p_tcols.p, m->p_tscores.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out_cols + c0 * k, m->p_tcols, (size_t)Cc * k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipMemcpyAsync(out_scores + c0 * k, m->p_tscores, (size_t)Cc * k * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(out_cols + c0 * k, m->p_tcols.p, (size_t)Cc * k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(out_scores + c0 * k, m->p_tscores.p, (size_t)Cc * k * sizeof(float), hipMemcpyDeviceToHost, m->stream));
         HIPCHK(hipStreamSynchronize(m->stream));
     }
     return 0;

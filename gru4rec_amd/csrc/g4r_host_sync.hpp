@@ -56,6 +56,7 @@ int g4r_sync_enable(g4r_model* m) {
 
 // sorted ids of the rows of `group` this rank rewrote since the last reconciliation
 // grow-only scratch (device, or pinned host memory): 0 / -1
+// (the inference entries' grow-only device arrays are another kind: DevBuf, g4r_host_model.hpp)
 static int scratch_ensure(g4r_model::Scratch& sc, size_t bytes, bool host = false) {
     if (bytes == 0) bytes = 16;
     if (sc.p && sc.cap >= bytes) return 0;

@@ -1,4 +1,4 @@
-"""The scan tests must be able to FAIL: mutant 12 (gru4rec_amd/build.py MUTANTS, -DG4R_MUTATE=12 in g4r_host_predict.hpp) skips the
+"""The scan tests must be able to FAIL: mutant 12 (gru4rec_amd/build.py MUTANTS, -DG4R_MUTATE=12 in g4r_host_topk.hpp) skips the
 fp32 re-scoring of the two-stage top-k, so its second stage ranks -- and returns -- the approximate bf16 scores of the first.  The
 tests that compare returned scores with predict_next_batch bit for bit, and the certified-equality test, run in a child process with
 G4R_LIB pointing at it and have to come back red; the argument test, which launches nothing, stays green on it, and on the product
