@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get('G4R_LIB') or os.path.join(_HERE, 'libgru4rec_hip.so')
 
 G4R_MAX_LAYERS = 8
 G4R_TOPK_MAX = 256      # largest k of g4r_recommend_step
+G4R_BEAM_MAX = 32       # widest beam of g4r_beam_sessions
+BEAM_COMBINE = {'sum': 0, 'product': 1}      # G4R_BEAM_*
 G4R_EXCLUDE_MAX = 1024  # most distinct items one row of g4r_recommend_step_filtered may exclude
 G4R_CAND_MAX = 2 ** 31 - 256  # most candidate positions of one g4r_score_candidates* call
 G4R_SCAN_CAND_MAX = 1024  # most candidates per row (k * oversample) of g4r_recommend_step_scan / g4r_recommend_sessions_scan
@@ -48,13 +50,30 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
 ]
 
 _lib = None
+
+
+def beam_backtrack(parent, cols, step_scores):
+    """The paths of g4r_beam_sessions' final beams out of its back-pointer records ([n, steps, beams] each: beam i of step s extends
+    beam parent[n, s, i] of step s - 1 by cols[n, s, i], scored step_scores[n, s, i]): (paths[n, beams, steps] in the dtype of cols,
+    scores float32[n, beams, steps]), final beam i read backwards from the last step."""
+    parent, cols, step_scores = np.asarray(parent), np.asarray(cols), np.asarray(step_scores)
+    n, steps, beams = parent.shape
+    paths = np.empty((n, beams, steps), dtype=cols.dtype)
+    scores = np.empty((n, beams, steps), dtype=np.float32)
+    row = np.arange(n)[:, None]
+    cur = np.tile(np.arange(beams), (n, 1))
+    for s in range(steps - 1, -1, -1):
+        paths[:, :, s] = cols[row, s, cur]
+        scores[:, :, s] = step_scores[row, s, cur]
+        cur = parent[row, s, cur]
+    return paths, scores
 
 
 class NativeError(RuntimeError):
@@ -110,6 +129,8 @@ def lib():
                                               i32p, f32p, C.POINTER(f32p)]
     L.g4r_continue_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i32, i32, i32, i64p, i32p,
                                         C.POINTER(C.c_uint32), i32p, f32p, C.POINTER(f32p)]
+    L.g4r_beam_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i32, i32, i32, i32, i64p, i32p,
+                                    C.POINTER(C.c_uint32), i32p, i32p, f32p, f32p, i32p]
     L.g4r_scan_table_release.argtypes = [vp]
     L.g4r_similar_items.argtypes = [vp, i32, i32, i32p, i64, i32p, i64, i32, i32, C.POINTER(C.c_uint32), i32p, f32p]
     L.g4r_score_candidates.argtypes = [vp, i32p, i32, i64p, i32p, i32, f32p, i32p]
@@ -513,6 +534,52 @@ class Model:
             None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)), _i32(cols), _f32(scores),
             None if hout is None else P(*[_f32(h) for h in hout])))
         return (cols, scores, hout) if return_hidden else (cols, scores)
+
+    def beam_sessions(self, hist_offs, hist_items, item_idx=None, beams=4, steps=1, no_repeat=True, combine='sum', excl_offs=None,
+                      excl_items=None, excl_mask=None, hidden=None, oversample=None):
+        """Beam search over the continuations of whole sessions (g4r_beam_sessions).  Arguments as in continue_sessions, with
+        k = beams, and combine ('sum' / 'product').  Returns the raw back-pointer records (parent int32[n, steps, beams], cols
+        int32[n, steps, beams], step_scores float32[n, steps, beams]) and (path_scores float32[n, beams], scale_exp int32[n]) after
+        the last step; beam_backtrack turns the records into paths."""
+        offs = np.ascontiguousarray(hist_offs, dtype=np.int64)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32)
+        n = len(offs) - 1
+        if n < 1 or offs[0] < 0 or offs[-1] > len(hi):
+            raise ValueError('hist_offs must hold n + 1 >= 2 offsets into hist_items')
+        steps, beams = int(steps), int(beams)
+        if steps < 1:
+            raise ValueError('steps must be at least 1')
+        if not 1 <= beams <= G4R_BEAM_MAX:
+            raise ValueError('beams must be in [1, %d]' % G4R_BEAM_MAX)
+        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
+        n_sel = self.cfg.n_items if it is None else len(it)
+        xo = None if excl_offs is None else np.ascontiguousarray(excl_offs, dtype=np.int64)
+        xi = np.ascontiguousarray(np.zeros(0) if excl_items is None else excl_items, dtype=np.int32)
+        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
+        if xo is not None and (len(xo) != n + 1 or xo[-1] > len(xi) or xo[0] < 0):
+            raise ValueError('excl_offs must hold n + 1 offsets into excl_items')
+        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
+            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
+        h0 = None
+        if hidden is not None:
+            if len(hidden) != len(self.layers):
+                raise ValueError('hidden holds %d arrays, one per layer (%d) is needed' % (len(hidden), len(self.layers)))
+            h0 = [np.ascontiguousarray(h, dtype=np.float32) for h in hidden]
+            for l, h in enumerate(h0):
+                if h.shape != (n, self.layers[l]):
+                    raise ValueError('hidden[%d] has shape %s, (%d, %d) is needed' % (l, h.shape, n, self.layers[l]))
+        P = C.POINTER(C.c_float) * len(self.layers)
+        parent = np.empty((n, steps, beams), dtype=np.int32)
+        cols = np.empty((n, steps, beams), dtype=np.int32)
+        step_scores = np.empty((n, steps, beams), dtype=np.float32)
+        path_scores = np.empty((n, beams), dtype=np.float32)
+        scale_exp = np.empty(n, dtype=np.int32)
+        _chk(lib().g4r_beam_sessions(
+            self.h, _i64(offs), _i32(hi), n, None if h0 is None else P(*[_f32(h) for h in h0]), None if it is None else _i32(it), n_sel,
+            beams, 0 if oversample is None else int(oversample), steps, 1 if no_repeat else 0, BEAM_COMBINE[combine],
+            None if xo is None else _i64(xo), _i32(xi), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)),
+            _i32(parent), _i32(cols), _f32(step_scores), _f32(path_scores), _i32(scale_exp)))
+        return parent, cols, step_scores, path_scores, scale_exp
 
     def similar_items(self, q_idx, item_idx=None, k=20, metric='cosine', space='output', exclude_self=True, excl_mask=None):
         """The k candidates most similar to every query item in the model's own embedding space (g4r_similar_items; stateless):

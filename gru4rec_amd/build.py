@@ -44,7 +44,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            12: "the two-stage top-k (g4r_recommend_*_scan) ranks its candidates by the APPROXIMATE bf16 scores: the fp32 re-scoring is skipped",
            13: "cosine (g4r_similar_items): the candidate's inverse norm is read at the candidate POSITION instead of its item index",
            14: "k_rollout_feed (g4r_continue_sessions): the sorted insertion drops an item that sorts ABOVE every item already in the row's "
-               "exclusion list, so it is never excluded and can be generated again"}
+               "exclusion list, so it is never excluded and can be generated again",
+           15: "k_beam_advance (g4r_beam_sessions) reads the hidden state of beam row i ITSELF instead of the row of its parent: a new beam "
+               "carries on from the wrong state wherever the selection re-parents"}
 
 
 def mutant_path(k):

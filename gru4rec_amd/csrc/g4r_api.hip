@@ -16,6 +16,7 @@
 #include "g4r_eval_kernels.cuh"
 #include "g4r_topk_kernels.cuh"
 #include "g4r_rollout_kernels.cuh"
+#include "g4r_beam_kernels.cuh"
 #include "g4r_cand_kernels.cuh"
 #include "g4r_scan_kernels.cuh"
 #include "g4r_sim_kernels.cuh"
@@ -35,6 +36,7 @@ extern "C" {
 #include "g4r_host_topk.hpp"
 #include "g4r_host_predict.hpp"
 #include "g4r_host_sessions.hpp"
+#include "g4r_host_beam.hpp"
 #include "g4r_host_events.hpp"
 #include "g4r_host_similar.hpp"
 #include "g4r_host_comm.hpp"

@@ -171,6 +171,11 @@ struct g4r_model {
     DevBuf<int> ro_cols, ro_in, ro_xlen;
     DevBuf<float> ro_scores;
     int64_t ro_calls = 0, ro_steps = 0;          // g4r_get_debug "continue_steps": calls that passed their checks, (chunk, step) chains enqueued
+    // beam search (g4r_beam_sessions; rows = a chunk's beam rows): the beams' GRU input items; (parent, item) of the step's new beams; the
+    // begin of every beam row's exclusion list, the two list buffers the lists alternate between and the lengths in each; what a chunk
+    // downloads, as 4-byte words: [steps][rows] parent | column | step score, [rows] path score, [sessions] scale_exp
+    DevBuf<int> bm_in, bm_sel, bm_xlen, bm_xitems, bm_out;
+    DevBuf<long long> bm_beg;
     // per-row candidate scoring (g4r_score_candidates*): one call's (or chunk's) CSR -- row offsets, candidate item indices, scores
     // in CSR order -- the work items of k_score_cand, the top-k lists of k_cand_pack and the selected (position, score) pairs
     DevBuf<long long> c_offs;

@@ -139,6 +139,19 @@ static void excl_chunk(const std::vector<long long>& xoffs, const std::vector<in
     }
 }
 
+// no_repeat (g4r_continue_sessions, g4r_beam_sessions) needs duplicate-free candidates (item_idx, range-checked; NULL: all items):
+// only then does every generated item take exactly one eligible position
+static int no_repeat_check(g4r_model* m, const int32_t* item_idx, int64_t n_sel) {
+    if (!item_idx) return 0;
+    std::vector<uint32_t> seen(((size_t)m->dm.n_items + 31) / 32, 0u);
+    for (int64_t p = 0; p < n_sel; ++p) {
+        const int32_t i = item_idx[p];
+        if ((seen[i >> 5] >> (i & 31)) & 1u) return fail("no_repeat needs duplicate-free candidates: item index " + std::to_string(i) + " is listed twice");
+        seen[i >> 5] |= 1u << (i & 31);
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ selection after a replay
 // The body of g4r_recommend_sessions(_scan) and g4r_continue_sessions; the caller has run recommend_check and its own refusals.
 // oversample 0: the exact selection, otherwise the two-stage one.
@@ -162,15 +175,7 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
     const bool rollout = steps > 0;
     const int n_step = std::max(steps, 1);
     const bool grow = no_repeat != 0 && steps > 1;      // the lists gain items on the device
-    if (no_repeat && item_idx) {
-        // only then does every generated item take exactly one eligible position
-        std::vector<uint32_t> seen(((size_t)d.n_items + 31) / 32, 0u);
-        for (int64_t p = 0; p < n_sel; ++p) {
-            const int32_t i = item_idx[p];
-            if ((seen[i >> 5] >> (i & 31)) & 1u) return fail("no_repeat needs duplicate-free candidates: item index " + std::to_string(i) + " is listed twice");
-            seen[i >> 5] |= 1u << (i & 31);
-        }
-    }
+    if (no_repeat && no_repeat_check(m, item_idx, n_sel)) return -1;
     std::vector<long long> xoffs;
     std::vector<int32_t> xitems;
     const bool excl = excl_offs || excl_mask || grow;

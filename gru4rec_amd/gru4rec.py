@@ -1081,6 +1081,80 @@ class GRU4Rec:
             return cand[out[0]], out[1]
         return cand[out[0]], out[1], [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(out[2], self.layers)]
 
+    def beam_sessions(self, histories, steps, beams=4, no_repeat=True, predict_for_item_ids=None, exclude=None, exclude_per_row=None,
+                      hidden=None, combine=None, scan='fp32', oversample=8):
+        """Beam search over the next `steps` items of N whole sessions in one stateless call: (paths[N, beams, steps] item ids, best
+        path first, path_scores[N, beams] float32, step_scores[N, beams, steps] float32 -- the step score of every item on the path
+        -- and scale_exp[N] int32).  Not in the reference.  continue_sessions feeds back only the best item of every step; this call
+        keeps `beams` partial paths per session alive and scores each path as a whole.
+
+        The result equals, item ids, score bits and scale_exp, a host loop of recommend_sessions calls.  Step 0 is
+        recommend_sessions(histories, k=beams, exclude_history=no_repeat, ...): beam i is column i, its path score that score.  At
+        every later step each beam b is one recommend_sessions([[its last item]], k=beams, hidden=<its own state>) row, excluded
+        items as below; candidate (b, j) with step score x has the path score
+          combine='sum'      fl32(cum_b + x)   (the default, except for softmax scores);
+          combine='product'  fl32(cum_b * x), a result of magnitude below 2^-126 replaced by 0.0; allowed only, and the default,
+                             for final_act softmax / softmax_logit, whose scores are probabilities;
+        and the `beams` best of the session's beams x beams candidates -- path score descending, equal scores by the lower
+        b * beams + j, NaN last -- become the new beams, each with its parent's path plus the item and the state its parent's call
+        returned.  'product' rescales after every selection: with m the new beam 0's path score (finite, > 0) = g * 2^e, 1 <= g < 2,
+        the session's path scores are multiplied by 2^-e and e is added to scale_exp, so path probability = path_scores *
+        2.0 ** scale_exp however many steps there are ('sum': scale_exp is 0).  softmax scores are not renormalised over the
+        remaining items.
+
+          no_repeat        a path never holds an item of its session's history nor an item twice: a beam's exclusions are the
+                           caller's plus the history and its own path.  False: only exclude / exclude_per_row apply.
+          beams            an integer in [1, min(number of candidates, G4R_BEAM_MAX = 32)].
+          predict_for_item_ids, exclude, exclude_per_row, hidden, scan, oversample: as in continue_sessions with k = beams, with its
+                           refusals (duplicate-free candidates under no_repeat, excluded items + steps - 1 <= G4R_EXCLUDE_MAX, at
+                           least beams eligible positions left at the last step, a bad `hidden`, an empty history: ValueError
+                           naming the row where there is one; an unknown id: KeyError).
+
+        beams=1 is continue_sessions(k=1)'s path; steps=1 is recommend_sessions(k=beams).  Everything is checked before any device
+        work and the prediction state is neither read nor changed.  The paths are rebuilt on the host from the back-pointers the
+        device returns (_native.beam_backtrack)."""
+        if self.error_during_train:
+            raise Exception
+        try:
+            steps_ok = not isinstance(steps, bool) and int(steps) == steps and steps >= 1
+        except (TypeError, ValueError):
+            steps_ok = False
+        if not steps_ok:
+            raise ValueError('steps = %r: it must be an integer >= 1' % (steps,))
+        steps = int(steps)
+        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
+        try:
+            beams_ok = not isinstance(beams, bool) and int(beams) == beams and 1 <= beams <= min(n_sel, _native.G4R_BEAM_MAX)
+        except (TypeError, ValueError):
+            beams_ok = False
+        if not beams_ok:
+            raise ValueError('beams = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (beams, n_sel, _native.G4R_BEAM_MAX))
+        beams = int(beams)
+        softmax = self._final[0] in (_native.ACT_IDS['softmax'], _native.ACT_IDS['softmax_logit'])      # (is_softmax of the C side)
+        if combine is None:
+            combine = 'product' if softmax else 'sum'
+        if combine not in ('sum', 'product'):
+            raise ValueError("combine = %r: it must be None, 'sum' or 'product'" % (combine,))
+        if combine == 'product' and not softmax:
+            raise ValueError("combine='product' multiplies probabilities: it needs final_act softmax / softmax_logit, not %r" % self.final_act)
+        over = self._scan_oversample(scan, oversample, beams)
+        N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
+        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
+        if no_repeat and iidx is not None and len(np.unique(iidx)) != len(iidx):
+            raise ValueError('no_repeat needs duplicate-free predict_for_item_ids: every generated item must take exactly one candidate '
+                             'position')
+        xoffs = xitems = mask = None
+        if no_repeat or exclude is not None or exclude_per_row is not None:
+            hist_rows = (np.repeat(np.arange(N), lens), hidx) if no_repeat else None
+            xoffs, xitems, mask = self._pack_exclusions(N, beams, iidx, hist_rows, 'the history', exclude, exclude_per_row,
+                                                        grow=steps - 1 if no_repeat else 0)
+        m = self._ensure_model()
+        parent, cols, sscores, path_scores, scale_exp = m.beam_sessions(offs, hidx, iidx, beams, steps, bool(no_repeat), combine, xoffs,
+                                                                        xitems, mask, hidden=h0, oversample=over)
+        paths, step_scores = _native.beam_backtrack(parent, cols, sscores)
+        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
+        return cand[paths], path_scores, step_scores, scale_exp
+
     # ------------------------------------------------------------------ per-row candidate lists (not in the reference)
     def _candidate_csr(self, candidates, rows, k):
         """Checks and packs the `candidates` argument of score_candidates*: (offsets int64[rows + 1], item indices int32, the

@@ -247,6 +247,34 @@ int g4r_continue_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t*
                           const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask, int32_t* out_cols,
                           float* out_scores, float* const* out_hidden);
 
+/* not in the reference: beam search over the continuations of n whole sessions, stateless.  The arguments of g4r_continue_sessions with
+ * k = beams (1 <= beams <= min(candidates, G4R_BEAM_MAX)) plus `combine`.  Step 0 is g4r_recommend_sessions(_scan) of the histories with
+ * k = beams: beam i of a session is column i, its path score that column's score.  For s >= 1 every beam's last item is fed to the GRU
+ * from the beam's own state and its `beams` best next items are selected -- bit for bit g4r_recommend_sessions(_scan) of the one-item
+ * history {that item} from that state, with the same candidates, mask and lists (no_repeat != 0: plus the items of the beam's own
+ * path).  Of the session's beams x beams extensions (beam b, column j, step score x) the `beams` best by path score become the new
+ * beams, each with the state its parent's step left:
+ *   G4R_BEAM_SUM      path score = fl32(parent's path score + x);
+ *   G4R_BEAM_PRODUCT  path score = fl32(parent's path score * x), a result of magnitude below 2^-126 (NaN is not) replaced by 0.0;
+ *                     only for softmax / softmax_logit final activations (probabilities);
+ *   order             path score descending, equal scores by the lower b * beams + j, NaN last.
+ * G4R_BEAM_PRODUCT rescales after every step's selection, step 0 included: with m the new beam 0's path score, finite and > 0,
+ * m = g * 2^e, 1 <= g < 2, every path score of the session is multiplied by 2^-e (exact) and e is added to the session's scale_exp:
+ * path probability = path score * 2^scale_exp for any number of steps.  (G4R_BEAM_SUM leaves scale_exp 0.)
+ * Outputs: the back-pointer records out_parent / out_cols / out_step_scores[n * steps * beams], [session][step][beam]: beam i of step s
+ * extends beam out_parent of step s - 1 (step 0: i itself) by the candidate position out_cols (item index when item_idx is NULL)
+ * whose step score is out_step_scores; out_path_scores[n * beams] and out_scale_exp[n] after the last step, best beam first.  The path
+ * of a final beam is read backwards through out_parent.  The refusals of g4r_continue_sessions apply with k = beams; everything is
+ * checked before any launch; the prediction state is neither read nor changed.  Selection, re-parenting and the list upkeep run on
+ * the device: one stream synchronisation and one download per chunk of sessions, whatever steps and beams are. */
+#define G4R_BEAM_MAX 32
+#define G4R_BEAM_SUM 0
+#define G4R_BEAM_PRODUCT 1
+int g4r_beam_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                      const int32_t* item_idx, int64_t n_sel, int32_t beams, int32_t oversample, int32_t steps, int32_t no_repeat,
+                      int32_t combine, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
+                      int32_t* out_parent, int32_t* out_cols, float* out_step_scores, float* out_path_scores, int32_t* out_scale_exp);
+
 /* not in the reference: item-to-item neighbours in the model's own embedding space -- the k candidates most similar to each of n
  * query items.  Stateless: the prediction state and the training state are neither read nor changed.
  *   table T     space = G4R_SPACE_OUTPUT: Wy, rows of layers[n_layers - 1] floats.  G4R_SPACE_INPUT: E when embed_mode is
