@@ -46,7 +46,10 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            14: "k_rollout_feed (g4r_continue_sessions): the sorted insertion drops an item that sorts ABOVE every item already in the row's "
                "exclusion list, so it is never excluded and can be generated again",
            15: "k_beam_advance (g4r_beam_sessions) reads the hidden state of beam row i ITSELF instead of the row of its parent: a new beam "
-               "carries on from the wrong state wherever the selection re-parents"}
+               "carries on from the wrong state wherever the selection re-parents",
+           16: "the owner walk of k_sparse_update_generic drops the first hit of every pass after the first (an item with more than 64 "
+               "earlier occurrences in a step loses one of them per later pass)",
+           17: "opt_rule's new second statistic (adadelta's update average, Adam's mean) x 1.01"}
 
 
 def mutant_path(k):

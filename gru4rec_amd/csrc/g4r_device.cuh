@@ -47,6 +47,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #else
 #define G4R_MUT_XSCALE(x) (x)
 #endif
+#if defined(G4R_MUTATE) && G4R_MUTATE == 16      // test build: the owner walk of k_sparse_update_generic drops the first hit of every pass after
+// the first (an item with more than 64 earlier occurrences in a step loses one of them per later pass)
+#define G4R_MUT_PASS_SKIP(pass, ri) ((pass) > 0 && (ri) == 0)
+#else
+#define G4R_MUT_PASS_SKIP(pass, ri) false
+#endif
+#if defined(G4R_MUTATE) && G4R_MUTATE == 17      // test build: opt_rule's new second statistic (adadelta's update average, Adam's mean) x 1.01
+#define G4R_MUT_STAT2(x) ((x) * 1.01f)
+#else
+#define G4R_MUT_STAT2(x) (x)
+#endif
 
 // Philox stream ids (counter word 3); twin of oracle/philox.py
 #define G4R_STREAM_SAMPLE 0x53414D50u

@@ -103,6 +103,7 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
         }
         return 0;
     }
+    else if (s == "generic") { if (count < 1) return fail("count"); host[0] = (float)d.generic; return 0; }      // 1: the generic optimizer path (raw gradients -> opt_rule: k_sparse_update_generic, dense_apply_elem)
     else if (s == "score_b_split") { if (count < 1) return fail("count"); host[0] = (float)k.score_a_host; return 0; }      // 1: k_score_b's role A runs in the top layer's k_gru_dy launch (graph / eager steps; per-kernel profiling keeps it in k_score_b)
     else if (s == "n_cu") { if (count < 1) return fail("count"); host[0] = (float)m->n_cu; return 0; }      // the CU count the choice was made for
     else if (s == "ksplit") { if (count < 1) return fail("count"); host[0] = (float)d.ksplit; return 0; }

@@ -126,12 +126,12 @@ __device__ __forceinline__ OptOut opt_rule(int adapt, float v1, float v3, bool d
         o.G = S * sc; o.gl = gk * sc; o.A = an;
     } else if (adapt == G4R_ADAPT_ADADELTA) {
         const float an = v1 * a0 + (1.f - v1) * Q, r = (u0 + eps) / (an + eps), sc = sqrtf(r);
-        o.U = v1 * u0 + (1.f - v1) * r * Q;
+        o.U = G4R_MUT_STAT2(v1 * u0 + (1.f - v1) * r * Q);
         o.G = S * sc; o.gl = gk * sc; o.A = an;
     } else if (adapt == G4R_ADAPT_ADAM) {
         const float an = v3 * a0 + (1.f - v3) * Q, mn = v1 * u0 + (1.f - v1) * (dense ? S : Q), cn = c0 + 1.f;
         const float corr = 1.f - powf(v1, cn), out = (mn / corr) / (sqrtf(an / corr) + eps);
-        o.G = fn * out; o.gl = out; o.A = an; o.U = mn; o.C = cn;
+        o.G = fn * out; o.gl = out; o.A = an; o.U = G4R_MUT_STAT2(mn); o.C = cn;
     } else if (adapt == G4R_ADAPT_NONE) {
         o.G = S; o.gl = gk; o.A = a0;
     } else {
@@ -1049,7 +1049,7 @@ __global__ __launch_bounds__(SP_WAVES * 64, MAXCH == 1 ? 4 : 2) void k_sparse_up
                 for (int u = 0; u < NB; ++u) {
                     const int ri = i0 + u * RPI + sub;
                     const bool lr_u = __shfl(lastrow, min(ri, cnt - 1) & 63) != 0;
-                    if (ri < cnt) {
+                    if (ri < cnt && !G4R_MUT_PASS_SKIP(pass, ri)) {
 #pragma unroll
                         for (int q = 0; q < MAXCH; ++q) {
                             add4(S[q], g[u][q]); add4(Q[q], sq(g[u][q]));

@@ -492,6 +492,9 @@ class OracleGRU4Rec:
             for g in (dSx, dSy, dSBy):
                 sq = sq + (g.astype(self.dtype) ** 2).sum(dtype=self.dtype)
             norm = np.sqrt(sq)
+            if dbg is not None:      # the step's global gradient norm and whether it was clipped (tests choose caps from it)
+                dbg['grad_norm'] = float(norm)
+                dbg['clipped'] = bool(norm >= self.grad_cap)
             if norm >= self.grad_cap:
                 c = dt(self.grad_cap) / norm
                 dense_grads = [(i,) + tuple(None if g is None else (g * c).astype(self.dtype) for g in gs) for (i, *gs) in dense_grads]

@@ -10,6 +10,9 @@ mutant; every one of those runs has to come back red, and the tensor it names ha
             the exact-shape tests that compare the rows of kink items apart (round 5 left those rows out; now they are bounded)
   mutant 8  k_update_l's owner scan skips the last id of every 1024-id slice after the first -> dWy of the hot-item case of
             test_gpu_lean_edges.py (an item with > 1024 earlier occurrences in a step loses one of them)
+  mutant 16 k_sparse_update_generic's owner walk drops the first hit of every pass after the first -> dWy of the hot rows of
+            test_gpu_generic_edges.py::test_hot_items (an item with > 64 earlier occurrences loses one per later pass)
+  mutant 17 opt_rule's new second statistic x 1.01 -> acc2_* of an adadelta and of an adam case; rmsprop (no such statistic) passes
 
 (Round 2's `atol = 1e-4` on every tensor let an accumulator that is wrong by 100 x pass.)  The same selection runs green on the
 product library in the ordinary suite."""
@@ -88,6 +91,38 @@ def test_mutant_8_turns_the_hot_item_case_red(mutants, tmp_path):
             lines = open(rep).read().splitlines()
             state = {ln[:28].strip(): ln.rstrip().endswith('FAIL') for ln in lines if 'worst/tol' in ln}
             assert state['hot dWy'], state
+
+
+def _child(lib, sel, rep):
+    env = dict(os.environ, G4R_LIB=lib, G4R_PARITY_REPORT=rep)
+    r = subprocess.run([sys.executable, '-m', 'pytest', sel, '-x', '-q', '-p', 'no:cacheprovider'], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=900)
+    lines = open(rep).read().splitlines() if os.path.exists(rep) else []
+    return r, {ln[:28].strip(): ln[:ln.find('(hot row')].rstrip().endswith('FAIL') if '(hot row' in ln else ln.rstrip().endswith('FAIL')
+               for ln in lines if 'worst/tol' in ln or 'counters:' in ln}
+
+
+def test_mutant_16_turns_the_generic_hot_item_case_red(mutants, tmp_path):
+    """The owner walk of k_sparse_update_generic loses the first hit of its second and third pass: the hot-item case must fail on
+    dWy of the hot rows (item 0 loses two of ~150 occurrences, item 1 one of ~85); a width-boundary case in which no item has more
+    than 64 occurrences must still pass."""
+    r, state = _child(mutants[16], 'tests/test_gpu_generic_edges.py::test_hot_items[40-sgd_mom]', str(tmp_path / 'hot.txt'))
+    assert r.returncode == 1, 'mutant 16 passed the hot-item case:\n%s' % (r.stdout + r.stderr)[-3000:]
+    assert state['hot sgd_mom D=40 dWy hot0'] and state['hot sgd_mom D=40 dWy hot1'], state
+    r, state = _child(mutants[16], 'tests/test_gpu_generic_edges.py::test_row_width[64-rmsprop]', str(tmp_path / 'width.txt'))
+    assert r.returncode == 0, 'mutant 16 on a case without a second pass: rc %d\n%s' % (r.returncode, (r.stdout + r.stderr)[-3000:])
+
+
+def test_mutant_17_turns_the_second_statistic_red(mutants, tmp_path):
+    """opt_rule's new second statistic x 1.01: an adadelta and an adam case must fail on acc2_* (sparse rows and dense tensors: one rule),
+    a rmsprop case (no second statistic) must still pass."""
+    for opt in ('adadelta', 'adam'):
+        r, state = _child(mutants[17], 'tests/test_gpu_generic_edges.py::test_row_width[260-%s]' % opt, str(tmp_path / (opt + '.txt')))
+        assert r.returncode == 1, 'mutant 17 passed the %s case:\n%s' % (opt, (r.stdout + r.stderr)[-3000:])
+        tag = '%s D=260' % opt
+        assert state[tag + ' acc2_Wy'] and state[tag + ' acc2_By'] and state[tag + ' acc2_Wh0'], state
+    r, state = _child(mutants[17], 'tests/test_gpu_generic_edges.py::test_row_width[260-rmsprop]', str(tmp_path / 'rms.txt'))
+    assert r.returncode == 0, 'mutant 17 on rmsprop: rc %d\n%s' % (r.returncode, (r.stdout + r.stderr)[-3000:])
 
 
 def test_product_library_is_not_a_mutant():

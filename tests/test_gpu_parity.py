@@ -159,9 +159,10 @@ def kink_twin(o):
     return t
 
 
-def oracle_steps(o, plan, T, full_batch=None, twin=None):
+def oracle_steps(o, plan, T, full_batch=None, twin=None, record=None):
     """The oracle over steps 0 .. T-1 of the plan: (per-step costs, items on the final activation's kink in any of the steps).
-    twin (kink_twin) runs the same steps on the other slope."""
+    twin (kink_twin) runs the same steps on the other slope.  record: a list that receives, per step, the global gradient norm
+    and whether it was clipped (grad_cap > 0)."""
     costs, kink = [], set()
     for t in range(T):
         M = int(plan['M'][t]) if full_batch is None else full_batch
@@ -169,6 +170,8 @@ def oracle_steps(o, plan, T, full_batch=None, twin=None):
         costs.append(cost)
         if dbg is not None:
             kink |= kink_items(o, dbg)
+            if record is not None:
+                record.append(dict(grad_norm=dbg.get('grad_norm'), clipped=dbg.get('clipped')))
         if twin is not None:
             _, dbg2 = twin.train_step(plan['in_idx'][t], plan['out_idx'][t], M, plan['reset'][t], return_debug=True)
             if dbg2 is not None:
@@ -190,16 +193,29 @@ def between(name, got, a, b, rtol, atol_rel, errs, floor=0.0):
         errs.append('%s: outside [min, max] of the two slopes by %.3e (scale %.3e, worst / tolerance %.2f)' % (name, float(excess.max()), scale, worst))
 
 
-def compare_params(o, m, errs, tag, Mrows=None, loosen=1.0, init=None, skip_items=(), twin=None):
+def compare_params(o, m, errs, tag, Mrows=None, loosen=1.0, init=None, skip_items=(), twin=None, leave_rows=()):
     """Parameters as updates against their initial values (o.init0, taken by make_pair), accumulators / velocities against their
     own scale.  loosen widens every bound by that factor (runs of many steps).  skip_items (kink_items) + twin (kink_twin, stepped
     by oracle_steps): the rows of items with a score on the final activation's kink are compared apart -- every element must lie
     between the oracle's two slopes (the run on `o` and the run on `twin`), with the same tolerance outside that interval; a row
-    that is wrong by more than the kink explains fails like any other."""
+    that is wrong by more than the kink explains fails like any other.
+    Everything the optimizer keeps is compared, for every tensor: the second statistic acc2_* (adadelta's update average, Adam's
+    mean) with the accumulators' bound, Adam's step counters cnt_* for equality (small integers held as floats), the velocities
+    vel_* with vel_Wy's bound.  leave_rows: rows of Wy / By and of their accumulators, second statistics and bias velocity that the
+    caller compares itself, against another reference (test_gpu_generic_edges.py: hot items against the float64 oracle)."""
     I = o.n_items
     Mrows = o.batch_size if Mrows is None else Mrows
     init = init if init is not None else o.init0
     PR, PA, AR, AA = 1e-3 * loosen, 1e-4 * loosen, 2e-4 * loosen, 1e-5 * loosen
+    two, counted, mom = o.adapt in ('adadelta', 'adam'), o.adapt == 'adam', o.momentum > 0
+
+    def same(name, got, want):
+        got, want = np.asarray(got), np.asarray(want)
+        ok = bool(np.array_equal(got, want))
+        report('%-28s counters: %d of %d differ, max %d  %s' % (name, int((got != want).sum()), got.size, int(np.max(want)) if want.size else 0,
+                                                                'ok' if ok else 'FAIL'))
+        if not ok:
+            errs.append(name)
 
     def upd(name, got, want, w0):
         w0 = np.asarray(w0, dtype=np.float64)
@@ -217,13 +233,28 @@ def compare_params(o, m, errs, tag, Mrows=None, loosen=1.0, init=None, skip_item
         for n in ('Wx', 'Wh', 'Wrz', 'Bh'):
             shape = {'Wx': (n_in, 3 * D), 'Wh': (D, D), 'Wrz': (D, 2 * D), 'Bh': (3 * D,)}[n]
             close_rel('%s acc_%s%d' % (tag, n, i), m.get_param('acc_' + n, shape, i), o.acc[n][i], AR, AA, errs)
+            if two:
+                close_rel('%s acc2_%s%d' % (tag, n, i), m.get_param('acc2_' + n, shape, i), o.acc2[n][i], AR, AA, errs)
+            if counted:
+                same('%s cnt_%s%d' % (tag, n, i), m.get_param('cnt_' + n, shape, i), o.cnt[n][i])
+            if mom:
+                close_rel('%s vel_%s%d' % (tag, n, i), m.get_param('vel_' + n, shape, i), o.vel[n][i], PR, PA, errs)
     keep = np.ones(I, dtype=bool)
     keep[list(skip_items)] = False
+    keep[list(leave_rows)] = False
     upd('%s dWy' % tag, m.get_param('Wy', (I, o.layers[-1]))[keep], o.Wy[keep], init['Wy'][keep])
     upd('%s dBy' % tag, m.get_param('By', (I,))[keep], o.By[keep], init['By'][keep])
     close_rel('%s acc_Wy' % tag, m.get_param('acc_Wy', (I, o.layers[-1]))[keep], o.acc['Wy'][keep], AR, AA, errs)
     close_rel('%s acc_By' % tag, m.get_param('acc_By', (I,))[keep], o.acc['By'][keep], AR, AA, errs)
-    rows = sorted(int(i) for i in skip_items)
+    if two:
+        close_rel('%s acc2_Wy' % tag, m.get_param('acc2_Wy', (I, o.layers[-1]))[keep], o.acc2['Wy'][keep], AR, AA, errs)
+        close_rel('%s acc2_By' % tag, m.get_param('acc2_By', (I,))[keep], o.acc2['By'][keep], AR, AA, errs)
+    if counted:      # (the counters do not depend on the slope: kink rows included)
+        same('%s cnt_Wy' % tag, m.get_param('cnt_Wy', (I, o.layers[-1])), o.cnt['Wy'])
+        same('%s cnt_By' % tag, m.get_param('cnt_By', (I,)), o.cnt['By'])
+    if mom:
+        close_rel('%s vel_By' % tag, m.get_param('vel_By', (I,))[keep], o.vel['By'][keep], PR, PA, errs)
+    rows = sorted(int(i) for i in skip_items if int(i) not in set(int(r) for r in leave_rows))
     if rows:
         assert twin is not None, 'kink items need the twin oracle (kink_twin)'
         gWy, gBy = m.get_param('Wy', (I, o.layers[-1]))[rows], m.get_param('By', (I,))[rows]
@@ -233,9 +264,20 @@ def compare_params(o, m, errs, tag, Mrows=None, loosen=1.0, init=None, skip_item
         between('%s dBy (kink rows)' % tag, gBy - b0, o.By[rows] - b0, twin.By[rows] - b0, PR, PA, errs, fl(o.By[rows]))
         between('%s acc_Wy (kink rows)' % tag, m.get_param('acc_Wy', (I, o.layers[-1]))[rows], o.acc['Wy'][rows], twin.acc['Wy'][rows], AR, AA, errs)
         between('%s acc_By (kink rows)' % tag, m.get_param('acc_By', (I,))[rows], o.acc['By'][rows], twin.acc['By'][rows], AR, AA, errs)
+        if two:
+            between('%s acc2_Wy (kink rows)' % tag, m.get_param('acc2_Wy', (I, o.layers[-1]))[rows], o.acc2['Wy'][rows], twin.acc2['Wy'][rows], AR, AA, errs)
+            between('%s acc2_By (kink rows)' % tag, m.get_param('acc2_By', (I,))[rows], o.acc2['By'][rows], twin.acc2['By'][rows], AR, AA, errs)
+        if mom:
+            between('%s vel_By (kink rows)' % tag, m.get_param('vel_By', (I,))[rows], o.vel['By'][rows], twin.vel['By'][rows], PR, PA, errs)
     if o.E is not None:
         upd('%s dE' % tag, m.get_param('E', (I, o.embedding)), o.E, init['E'])
         close_rel('%s acc_E' % tag, m.get_param('acc_E', (I, o.embedding)), o.acc['E'], AR, AA, errs)
+        if two:
+            close_rel('%s acc2_E' % tag, m.get_param('acc2_E', (I, o.embedding)), o.acc2['E'], AR, AA, errs)
+        if counted:
+            same('%s cnt_E' % tag, m.get_param('cnt_E', (I, o.embedding)), o.cnt['E'])
+        if mom:
+            close_rel('%s vel_E' % tag, m.get_param('vel_E', (I, o.embedding)), o.vel['E'], PR, PA, errs)
     if o.momentum > 0:
         close_rel('%s vel_Wy' % tag, m.get_param('vel_Wy', (I, o.layers[-1])), o.vel['Wy'], PR, PA, errs)
 
