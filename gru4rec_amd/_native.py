@@ -56,6 +56,10 @@ SYMBOLS = [
     'g4r_events_copy', 'g4r_events_free',
 ]
 
+# the pointer types of the ABI
+f32p, f64p, i32p, i64p, u8p, u32p = (C.POINTER(t) for t in (C.c_float, C.c_double, C.c_int32, C.c_int64, C.c_uint8, C.c_uint32))
+f32pp = C.POINTER(f32p)      # one float array per layer
+
 _lib = None
 
 
@@ -89,8 +93,7 @@ def lib():
         raise NativeError('libgru4rec_hip.so is not built (%s). Run `python -c "import __graft_entry__ as g; '
                           'g.build()"` -- the MI355X path has no CPU fallback.' % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, f32p = C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_float)
-    i32p, i64p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     L.g4r_device_count.restype = C.c_int
     L.g4r_last_error.restype = C.c_char_p
     L.g4r_version.restype = C.c_char_p
@@ -114,32 +117,29 @@ def lib():
     L.g4r_global_step.restype = i64
     L.g4r_refills.argtypes, L.g4r_refills.restype = [vp], i64
     L.g4r_set_step_counters.argtypes = [vp, i64, i64]
-    L.g4r_kernel_time.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), i64p]
+    L.g4r_kernel_time.argtypes = [vp, i32, C.POINTER(C.c_char_p), f64p, i64p]
     L.g4r_profile.argtypes = [vp, i32]
     L.g4r_reset_hidden.argtypes = [vp]
     L.g4r_predict_begin.argtypes = [vp, i32]
     L.g4r_predict_hidden.argtypes = [vp, u8p, i32, i32p, i32]
     L.g4r_predict_step.argtypes = [vp, i32p, i32, i32p, i64, f32p]
     L.g4r_recommend_step.argtypes = [vp, i32p, i32, i32p, i64, i32, i32p, f32p]
-    L.g4r_recommend_step_filtered.argtypes = [vp, i32p, i32, i32p, i64, i32, i64p, i32p, C.POINTER(C.c_uint32), i32p, f32p]
-    L.g4r_recommend_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i64p, i32p, C.POINTER(C.c_uint32), i32p,
-                                         f32p, C.POINTER(f32p)]
-    L.g4r_recommend_step_scan.argtypes = [vp, i32p, i32, i32p, i64, i32, i32, i64p, i32p, C.POINTER(C.c_uint32), i32p, f32p]
-    L.g4r_recommend_sessions_scan.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i32, i64p, i32p, C.POINTER(C.c_uint32),
-                                              i32p, f32p, C.POINTER(f32p)]
-    L.g4r_continue_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i32, i32, i32, i64p, i32p,
-                                        C.POINTER(C.c_uint32), i32p, f32p, C.POINTER(f32p)]
-    L.g4r_beam_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i32p, i64, i32, i32, i32, i32, i32, i64p, i32p,
-                                    C.POINTER(C.c_uint32), i32p, i32p, f32p, f32p, i32p]
+    L.g4r_recommend_step_filtered.argtypes = [vp, i32p, i32, i32p, i64, i32, i64p, i32p, u32p, i32p, f32p]
+    L.g4r_recommend_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i64p, i32p, u32p, i32p, f32p, f32pp]
+    L.g4r_recommend_step_scan.argtypes = [vp, i32p, i32, i32p, i64, i32, i32, i64p, i32p, u32p, i32p, f32p]
+    L.g4r_recommend_sessions_scan.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i64p, i32p, u32p, i32p, f32p,
+                                              f32pp]
+    L.g4r_continue_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i32, i64p, i32p, u32p, i32p, f32p, f32pp]
+    L.g4r_beam_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i32, i32, i64p, i32p, u32p, i32p, i32p,
+                                    f32p, f32p, i32p]
     L.g4r_scan_table_release.argtypes = [vp]
-    L.g4r_similar_items.argtypes = [vp, i32, i32, i32p, i64, i32p, i64, i32, i32, C.POINTER(C.c_uint32), i32p, f32p]
+    L.g4r_similar_items.argtypes = [vp, i32, i32, i32p, i64, i32p, i64, i32, i32, u32p, i32p, f32p]
     L.g4r_score_candidates.argtypes = [vp, i32p, i32, i64p, i32p, i32, f32p, i32p]
-    L.g4r_score_candidates_sessions.argtypes = [vp, i64p, i32p, i32, C.POINTER(f32p), i64p, i32p, i32, f32p, i32p, C.POINTER(f32p)]
+    L.g4r_score_candidates_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i64p, i32p, i32, f32p, i32p, f32pp]
     L.g4r_rank_targets.argtypes = [vp, i32p, i32, i64, i32, f32p]
-    L.g4r_evaluate.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32p, i32, i32,
-                               C.POINTER(C.c_double), C.POINTER(C.c_double), i64p]
+    L.g4r_evaluate.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32p, i32, i32, f64p, f64p, i64p]
     L.g4r_recommend_events.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32, i64p, i64, i32,
-                                       C.POINTER(C.c_uint32), i64p, i32p, i32p, i64, i32p, i32p, i32p, f32p, f32p, f32p]
+                                       u32p, i64p, i32p, i32p, i64, i32p, i32p, i32p, f32p, f32p, f32p]
     L.g4r_comm_unique_id.argtypes = [C.c_char_p]
     L.g4r_comm_init.argtypes = [vp, C.c_char_p, i32, i32]
     L.g4r_comm_sync_sparse.argtypes = [vp]
@@ -157,12 +157,12 @@ def lib():
     L.g4r_sync_enable.argtypes = [vp]
     L.g4r_sync_row_floats.argtypes, L.g4r_sync_row_floats.restype = [vp, i32], i64
     L.g4r_sync_export.argtypes, L.g4r_sync_export.restype = [vp, i32, i32p, f32p, i64], i64
-    L.g4r_sync_import.argtypes = [vp, i32, i32, i64p, C.POINTER(i32p), C.POINTER(f32p)]
+    L.g4r_sync_import.argtypes = [vp, i32, i32, i64p, C.POINTER(i32p), f32pp]
     L.g4r_get_debug.argtypes = [vp, C.c_char_p, f32p, i64]
     L.g4r_selftest_mfma.argtypes = [f32p]
     L.g4r_stress_start.argtypes = [i32, i64, i32, C.POINTER(vp)]
     L.g4r_stress_stop.argtypes = [vp]
-    L.g4r_bench_rows.argtypes = [i32, i64, i32, i64, i32, i32, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.g4r_bench_rows.argtypes = [i32, i64, i32, i64, i32, i32, C.c_uint64, f64p, f64p]
     L.g4r_events_load.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
     for fn in (L.g4r_events_rows, L.g4r_events_items, L.g4r_events_item_bytes):
         fn.argtypes, fn.restype = [vp], i64
@@ -184,20 +184,98 @@ def _chk(rc):
         raise NativeError(lib().g4r_last_error().decode())
 
 
-def _f32(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
+def _ptr(ptr):
+    """The converter of an array to a pointer of type ptr to its data; None stays None (NULL)."""
+    return lambda a: None if a is None else a.ctypes.data_as(ptr)
 
 
-def _i32(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
+_f32, _f64, _i32, _i64, _u8, _u32 = (_ptr(t) for t in (f32p, f64p, i32p, i64p, u8p, u32p))
 
 
-def _i64(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int64))
+# -- the argument families of the inference entries.  Every array a packer returns has to stay referenced until the C call returns.
+def _arr(a, dtype):
+    return None if a is None else np.ascontiguousarray(a, dtype=dtype)
 
 
-def _u8(a):
-    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+def _cand(item_idx, n_items):
+    """item_idx as (int32 array or None, number of candidates): without it the candidates are all items."""
+    if item_idx is None:
+        return None, n_items
+    it = np.ascontiguousarray(item_idx, dtype=np.int32)
+    return it, len(it)
+
+
+def _hist(hist_offs, hist_items):
+    """The history CSR of the session entries: (offsets int64[n + 1], item indices int32, n)."""
+    offs = np.ascontiguousarray(hist_offs, dtype=np.int64)
+    items = np.ascontiguousarray(hist_items, dtype=np.int32)
+    n = len(offs) - 1
+    if n < 1 or offs[0] < 0 or offs[-1] > len(items):
+        raise ValueError('hist_offs must hold n + 1 >= 2 offsets into hist_items')
+    return offs, items, n
+
+
+def _mask(excl_mask, n_items):
+    mask = _arr(excl_mask, np.uint32)
+    if mask is not None and len(mask) < (n_items + 31) // 32:
+        raise ValueError('excl_mask must hold ceil(n_items / 32) words')
+    return mask
+
+
+def _excl(rows, excl_offs, excl_items, excl_mask, n_items, rows_word):
+    """The exclusions of a call with `rows` rows: (offsets int64[rows + 1] or None, item indices int32 -- empty without lists,
+    never None --, mask words uint32 or None).  rows_word: what the refusal calls the rows ('rows' / 'n')."""
+    offs = _arr(excl_offs, np.int64)
+    items = np.ascontiguousarray(np.zeros(0) if excl_items is None else excl_items, dtype=np.int32)
+    if offs is not None and (len(offs) != rows + 1 or offs[-1] > len(items) or offs[0] < 0):
+        raise ValueError('excl_offs must hold %s + 1 offsets into excl_items' % rows_word)
+    return offs, items, _mask(excl_mask, n_items)
+
+
+def _layer_pointers(arrays):
+    return (f32p * len(arrays))(*[_f32(a) for a in arrays])
+
+
+def _hidden_in(hidden, n, layers):
+    """The initial hidden state of a session entry: (float32 arrays [n, layers[l]], float*[len(layers)] over them); (None, None)
+    without one."""
+    if hidden is None:
+        return None, None
+    if len(hidden) != len(layers):
+        raise ValueError('hidden holds %d arrays, one per layer (%d) is needed' % (len(hidden), len(layers)))
+    h0 = [np.ascontiguousarray(h, dtype=np.float32) for h in hidden]
+    for l, h in enumerate(h0):
+        if h.shape != (n, layers[l]):
+            raise ValueError('hidden[%d] has shape %s, (%d, %d) is needed' % (l, h.shape, n, layers[l]))
+    return h0, _layer_pointers(h0)
+
+
+def _hidden_out(n, layers, want):
+    """Room for the hidden state a session entry returns, as _hidden_in; (None, None) when it is not wanted."""
+    if not want:
+        return None, None
+    hout = [np.empty((n, D), dtype=np.float32) for D in layers]
+    return hout, _layer_pointers(hout)
+
+
+def _topk_out(shape):
+    return np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.float32)
+
+
+def _plan(plan, dummy_batch=None):
+    """The arrays of a plan for g4r_set_plan / g4r_evaluate / g4r_recommend_events, in the order the entries take them: (in_idx,
+    out_idx, reset, M, compact_steps, compact_maps, n_compact).  A plan without compaction tables (n_compact == 0) has None (NULL)
+    for the two -- what g4r_set_plan takes -- or, with dummy_batch, one zeroed entry and one zeroed row of that width, which the
+    other two entries want."""
+    nc = int(plan.get('n_compact', 0))
+    if nc:
+        cs, cm = np.ascontiguousarray(plan['compact_steps'], dtype=np.int64), np.ascontiguousarray(plan['compact_maps'], dtype=np.int32)
+    elif dummy_batch is None:
+        cs = cm = None
+    else:
+        cs, cm = np.zeros(1, dtype=np.int64), np.zeros((1, dummy_batch), dtype=np.int32)
+    ii, oi, mm = (np.ascontiguousarray(plan[key], dtype=np.int32) for key in ('in_idx', 'out_idx', 'M'))
+    return ii, oi, np.ascontiguousarray(plan['reset'], dtype=np.uint8), mm, cs, cm, nc
 
 
 IO_UNSUPPORTED = 1      # G4R_IO_UNSUPPORTED
@@ -220,7 +298,7 @@ def load_events(path, session_col, item_col, time_col=None, threads=0):
         time = None if kind == 0 else np.empty(n, dtype=np.int64 if kind == 1 else np.float64)
         off = np.empty(k + 1, dtype=np.int64)
         raw = C.create_string_buffer(max(int(nb), 1))
-        _chk(L.g4r_events_copy(h, _i32(session), _i32(item_idx), None if time is None else time.ctypes.data_as(C.c_void_p),
+        _chk(L.g4r_events_copy(h, _i32(session), _i32(item_idx), _ptr(C.c_void_p)(time),
                                _i64(off), raw))
     finally:
         L.g4r_events_free(h)
@@ -327,10 +405,8 @@ class Model:
     # -- sampling
     def set_popularity(self, cum_p, lq_tgt=None, lq_smp=None):
         p = np.ascontiguousarray(cum_p, dtype=np.float32)
-        a = None if lq_tgt is None else np.ascontiguousarray(lq_tgt, dtype=np.float32)
-        b = None if lq_smp is None else np.ascontiguousarray(lq_smp, dtype=np.float32)
-        _chk(lib().g4r_set_popularity(self.h, _f32(p), None if a is None else _f32(a),
-                                      None if b is None else _f32(b), p.size))
+        a, b = _arr(lq_tgt, np.float32), _arr(lq_smp, np.float32)
+        _chk(lib().g4r_set_popularity(self.h, _f32(p), _f32(a), _f32(b), p.size))
 
     def sample_store_rows(self):
         return int(lib().g4r_sample_store_rows(self.h))
@@ -347,16 +423,9 @@ class Model:
 
     # -- plan + training
     def set_plan(self, plan):
-        nc = int(plan.get('n_compact', 0))
-        cs = np.ascontiguousarray(plan['compact_steps'], dtype=np.int64) if nc else None
-        cm = np.ascontiguousarray(plan['compact_maps'], dtype=np.int32) if nc else None
-        ii = np.ascontiguousarray(plan['in_idx'], dtype=np.int32)
-        oi = np.ascontiguousarray(plan['out_idx'], dtype=np.int32)
-        rs = np.ascontiguousarray(plan['reset'], dtype=np.uint8)
-        mm = np.ascontiguousarray(plan['M'], dtype=np.int32)
-        _chk(lib().g4r_set_plan(self.h, _i32(ii), _i32(oi), _u8(rs), _i32(mm), len(mm),
-                                None if cs is None else _i64(cs), None if cm is None else _i32(cm), nc))
-        self.T = len(mm)
+        in_idx, out_idx, reset, M, cs, cm, nc = _plan(plan)
+        _chk(lib().g4r_set_plan(self.h, _i32(in_idx), _i32(out_idx), _u8(reset), _i32(M), len(M), _i64(cs), _i32(cm), nc))
+        self.T = len(M)
 
     def train_steps(self, t0, n):
         _chk(lib().g4r_train_steps(self.h, t0, n))
@@ -401,29 +470,23 @@ class Model:
         _chk(lib().g4r_predict_begin(self.h, batch))
 
     def predict_hidden(self, zero_mask=None, keep_rows=None):
-        z = None if zero_mask is None else np.ascontiguousarray(zero_mask, dtype=np.uint8)
-        k = None if keep_rows is None else np.ascontiguousarray(keep_rows, dtype=np.int32)
-        _chk(lib().g4r_predict_hidden(self.h, None if z is None else _u8(z), 0 if z is None else len(z), None if k is None else _i32(k),
-                                      0 if k is None else len(k)))
+        z, k = _arr(zero_mask, np.uint8), _arr(keep_rows, np.int32)
+        _chk(lib().g4r_predict_hidden(self.h, _u8(z), 0 if z is None else len(z), _i32(k), 0 if k is None else len(k)))
 
     def predict_step(self, in_idx, item_idx=None, want_scores=True):
         ii = np.ascontiguousarray(in_idx, dtype=np.int32)
-        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
-        n_sel = self.cfg.n_items if it is None else len(it)
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
         out = np.empty((len(ii), n_sel), dtype=np.float32) if want_scores else None
-        _chk(lib().g4r_predict_step(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel,
-                                    None if out is None else _f32(out)))
+        _chk(lib().g4r_predict_step(self.h, _i32(ii), len(ii), _i32(it), n_sel, _f32(out)))
         return out
 
     def recommend_step(self, in_idx, item_idx=None, k=20):
         """The k best candidates of every row of the scores predict_step would return (g4r_recommend_step; same hidden-state
         update): (cols int32[rows, k], scores float32[rows, k]); cols are positions in item_idx (item indices without it)."""
         ii = np.ascontiguousarray(in_idx, dtype=np.int32)
-        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
-        n_sel = self.cfg.n_items if it is None else len(it)
-        cols = np.empty((len(ii), k), dtype=np.int32)
-        scores = np.empty((len(ii), k), dtype=np.float32)
-        _chk(lib().g4r_recommend_step(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k, _i32(cols), _f32(scores)))
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        cols, scores = _topk_out((len(ii), k))
+        _chk(lib().g4r_recommend_step(self.h, _i32(ii), len(ii), _i32(it), n_sel, k, _i32(cols), _f32(scores)))
         return cols, scores
 
     def recommend_step_filtered(self, in_idx, item_idx=None, k=20, excl_offs=None, excl_items=None, excl_mask=None, oversample=None):
@@ -433,23 +496,15 @@ class Model:
         oversample (an integer >= 1): the two-stage selection instead (g4r_recommend_step_scan): a bf16 scan keeps k * oversample
         candidates per row, which are re-ranked by their exact fp32 scores."""
         ii = np.ascontiguousarray(in_idx, dtype=np.int32)
-        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
-        n_sel = self.cfg.n_items if it is None else len(it)
-        offs = None if excl_offs is None else np.ascontiguousarray(excl_offs, dtype=np.int64)
-        xi = np.ascontiguousarray(np.zeros(0) if excl_items is None else excl_items, dtype=np.int32)
-        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
-        if offs is not None and (len(offs) != len(ii) + 1 or offs[-1] > len(xi) or offs[0] < 0):
-            raise ValueError('excl_offs must hold rows + 1 offsets into excl_items')
-        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
-            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
-        cols = np.empty((len(ii), k), dtype=np.int32)
-        scores = np.empty((len(ii), k), dtype=np.float32)
-        tail = (None if offs is None else _i64(offs), _i32(xi), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)),
-                _i32(cols), _f32(scores))
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        xo, xi, mask = _excl(len(ii), excl_offs, excl_items, excl_mask, self.cfg.n_items, 'rows')
+        cols, scores = _topk_out((len(ii), k))
+        head = (self.h, _i32(ii), len(ii), _i32(it), n_sel, k)
+        tail = (_i64(xo), _i32(xi), _u32(mask), _i32(cols), _f32(scores))
         if oversample is None:
-            _chk(lib().g4r_recommend_step_filtered(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k, *tail))
+            _chk(lib().g4r_recommend_step_filtered(*head, *tail))
         else:
-            _chk(lib().g4r_recommend_step_scan(self.h, _i32(ii), len(ii), None if it is None else _i32(it), n_sel, k, int(oversample), *tail))
+            _chk(lib().g4r_recommend_step_scan(*head, int(oversample), *tail))
         return cols, scores
 
     def recommend_sessions(self, hist_offs, hist_items, item_idx=None, k=20, excl_offs=None, excl_items=None, excl_mask=None,
@@ -458,35 +513,14 @@ class Model:
         hist_items[hist_offs[i]:hist_offs[i + 1]] (item indices), started from hidden (a list of float32[n, layers[l]], None = zeros).
         Exclusions as in recommend_step_filtered, one list per session.  Returns (cols, scores), + the list of hidden states after
         the last items with return_hidden=True.  oversample: as in recommend_step_filtered (g4r_recommend_sessions_scan)."""
-        offs = np.ascontiguousarray(hist_offs, dtype=np.int64)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32)
-        n = len(offs) - 1
-        if n < 1 or offs[0] < 0 or offs[-1] > len(hi):
-            raise ValueError('hist_offs must hold n + 1 >= 2 offsets into hist_items')
-        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
-        n_sel = self.cfg.n_items if it is None else len(it)
-        xo = None if excl_offs is None else np.ascontiguousarray(excl_offs, dtype=np.int64)
-        xi = np.ascontiguousarray(np.zeros(0) if excl_items is None else excl_items, dtype=np.int32)
-        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
-        if xo is not None and (len(xo) != n + 1 or xo[-1] > len(xi) or xo[0] < 0):
-            raise ValueError('excl_offs must hold n + 1 offsets into excl_items')
-        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
-            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
-        h0 = None
-        if hidden is not None:
-            if len(hidden) != len(self.layers):
-                raise ValueError('hidden holds %d arrays, one per layer (%d) is needed' % (len(hidden), len(self.layers)))
-            h0 = [np.ascontiguousarray(h, dtype=np.float32) for h in hidden]
-            for l, h in enumerate(h0):
-                if h.shape != (n, self.layers[l]):
-                    raise ValueError('hidden[%d] has shape %s, (%d, %d) is needed' % (l, h.shape, n, self.layers[l]))
-        hout = [np.empty((n, D), dtype=np.float32) for D in self.layers] if return_hidden else None
-        P = C.POINTER(C.c_float) * len(self.layers)
-        cols = np.empty((n, k), dtype=np.int32)
-        scores = np.empty((n, k), dtype=np.float32)
-        head = (self.h, _i64(offs), _i32(hi), n, None if h0 is None else P(*[_f32(h) for h in h0]), None if it is None else _i32(it), n_sel, k)
-        tail = (None if xo is None else _i64(xo), _i32(xi), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)), _i32(cols),
-                _f32(scores), None if hout is None else P(*[_f32(h) for h in hout]))
+        offs, hi, n = _hist(hist_offs, hist_items)
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        xo, xi, mask = _excl(n, excl_offs, excl_items, excl_mask, self.cfg.n_items, 'n')
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        hout, houtp = _hidden_out(n, self.layers, return_hidden)
+        cols, scores = _topk_out((n, k))
+        head = (self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, k)
+        tail = (_i64(xo), _i32(xi), _u32(mask), _i32(cols), _f32(scores), houtp)
         if oversample is None:
             _chk(lib().g4r_recommend_sessions(*head, *tail))
         else:
@@ -499,40 +533,17 @@ class Model:
         (g4r_continue_sessions).  Arguments as in recommend_sessions; no_repeat adds every fed-back item to its session's exclusion
         list.  Returns (cols int32[n, steps, k], scores float32[n, steps, k]), + the hidden states that produced the last step's
         scores with return_hidden=True."""
-        offs = np.ascontiguousarray(hist_offs, dtype=np.int64)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32)
-        n = len(offs) - 1
-        if n < 1 or offs[0] < 0 or offs[-1] > len(hi):
-            raise ValueError('hist_offs must hold n + 1 >= 2 offsets into hist_items')
+        offs, hi, n = _hist(hist_offs, hist_items)
         steps = int(steps)
         if steps < 1:
             raise ValueError('steps must be at least 1')
-        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
-        n_sel = self.cfg.n_items if it is None else len(it)
-        xo = None if excl_offs is None else np.ascontiguousarray(excl_offs, dtype=np.int64)
-        xi = np.ascontiguousarray(np.zeros(0) if excl_items is None else excl_items, dtype=np.int32)
-        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
-        if xo is not None and (len(xo) != n + 1 or xo[-1] > len(xi) or xo[0] < 0):
-            raise ValueError('excl_offs must hold n + 1 offsets into excl_items')
-        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
-            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
-        h0 = None
-        if hidden is not None:
-            if len(hidden) != len(self.layers):
-                raise ValueError('hidden holds %d arrays, one per layer (%d) is needed' % (len(hidden), len(self.layers)))
-            h0 = [np.ascontiguousarray(h, dtype=np.float32) for h in hidden]
-            for l, h in enumerate(h0):
-                if h.shape != (n, self.layers[l]):
-                    raise ValueError('hidden[%d] has shape %s, (%d, %d) is needed' % (l, h.shape, n, self.layers[l]))
-        hout = [np.empty((n, D), dtype=np.float32) for D in self.layers] if return_hidden else None
-        P = C.POINTER(C.c_float) * len(self.layers)
-        cols = np.empty((n, steps, k), dtype=np.int32)
-        scores = np.empty((n, steps, k), dtype=np.float32)
-        _chk(lib().g4r_continue_sessions(
-            self.h, _i64(offs), _i32(hi), n, None if h0 is None else P(*[_f32(h) for h in h0]), None if it is None else _i32(it), n_sel, k,
-            0 if oversample is None else int(oversample), steps, 1 if no_repeat else 0, None if xo is None else _i64(xo), _i32(xi),
-            None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)), _i32(cols), _f32(scores),
-            None if hout is None else P(*[_f32(h) for h in hout])))
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        xo, xi, mask = _excl(n, excl_offs, excl_items, excl_mask, self.cfg.n_items, 'n')
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        hout, houtp = _hidden_out(n, self.layers, return_hidden)
+        cols, scores = _topk_out((n, steps, k))
+        _chk(lib().g4r_continue_sessions(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, k, 0 if oversample is None else int(oversample),
+                                         steps, 1 if no_repeat else 0, _i64(xo), _i32(xi), _u32(mask), _i32(cols), _f32(scores), houtp))
         return (cols, scores, hout) if return_hidden else (cols, scores)
 
     def beam_sessions(self, hist_offs, hist_items, item_idx=None, beams=4, steps=1, no_repeat=True, combine='sum', excl_offs=None,
@@ -541,44 +552,22 @@ class Model:
         k = beams, and combine ('sum' / 'product').  Returns the raw back-pointer records (parent int32[n, steps, beams], cols
         int32[n, steps, beams], step_scores float32[n, steps, beams]) and (path_scores float32[n, beams], scale_exp int32[n]) after
         the last step; beam_backtrack turns the records into paths."""
-        offs = np.ascontiguousarray(hist_offs, dtype=np.int64)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32)
-        n = len(offs) - 1
-        if n < 1 or offs[0] < 0 or offs[-1] > len(hi):
-            raise ValueError('hist_offs must hold n + 1 >= 2 offsets into hist_items')
+        offs, hi, n = _hist(hist_offs, hist_items)
         steps, beams = int(steps), int(beams)
         if steps < 1:
             raise ValueError('steps must be at least 1')
         if not 1 <= beams <= G4R_BEAM_MAX:
             raise ValueError('beams must be in [1, %d]' % G4R_BEAM_MAX)
-        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
-        n_sel = self.cfg.n_items if it is None else len(it)
-        xo = None if excl_offs is None else np.ascontiguousarray(excl_offs, dtype=np.int64)
-        xi = np.ascontiguousarray(np.zeros(0) if excl_items is None else excl_items, dtype=np.int32)
-        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
-        if xo is not None and (len(xo) != n + 1 or xo[-1] > len(xi) or xo[0] < 0):
-            raise ValueError('excl_offs must hold n + 1 offsets into excl_items')
-        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
-            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
-        h0 = None
-        if hidden is not None:
-            if len(hidden) != len(self.layers):
-                raise ValueError('hidden holds %d arrays, one per layer (%d) is needed' % (len(hidden), len(self.layers)))
-            h0 = [np.ascontiguousarray(h, dtype=np.float32) for h in hidden]
-            for l, h in enumerate(h0):
-                if h.shape != (n, self.layers[l]):
-                    raise ValueError('hidden[%d] has shape %s, (%d, %d) is needed' % (l, h.shape, n, self.layers[l]))
-        P = C.POINTER(C.c_float) * len(self.layers)
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        xo, xi, mask = _excl(n, excl_offs, excl_items, excl_mask, self.cfg.n_items, 'n')
+        h0, h0p = _hidden_in(hidden, n, self.layers)
         parent = np.empty((n, steps, beams), dtype=np.int32)
-        cols = np.empty((n, steps, beams), dtype=np.int32)
-        step_scores = np.empty((n, steps, beams), dtype=np.float32)
+        cols, step_scores = _topk_out((n, steps, beams))
         path_scores = np.empty((n, beams), dtype=np.float32)
         scale_exp = np.empty(n, dtype=np.int32)
-        _chk(lib().g4r_beam_sessions(
-            self.h, _i64(offs), _i32(hi), n, None if h0 is None else P(*[_f32(h) for h in h0]), None if it is None else _i32(it), n_sel,
-            beams, 0 if oversample is None else int(oversample), steps, 1 if no_repeat else 0, BEAM_COMBINE[combine],
-            None if xo is None else _i64(xo), _i32(xi), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)),
-            _i32(parent), _i32(cols), _f32(step_scores), _f32(path_scores), _i32(scale_exp)))
+        _chk(lib().g4r_beam_sessions(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, beams, 0 if oversample is None else int(oversample),
+                                     steps, 1 if no_repeat else 0, BEAM_COMBINE[combine], _i64(xo), _i32(xi), _u32(mask), _i32(parent),
+                                     _i32(cols), _f32(step_scores), _f32(path_scores), _i32(scale_exp)))
         return parent, cols, step_scores, path_scores, scale_exp
 
     def similar_items(self, q_idx, item_idx=None, k=20, metric='cosine', space='output', exclude_self=True, excl_mask=None):
@@ -586,16 +575,11 @@ class Model:
         (cols int32[n, k], scores float32[n, k]); cols are positions in item_idx (item indices without it).  excl_mask as in
         recommend_step_filtered."""
         qi = np.ascontiguousarray(q_idx, dtype=np.int32)
-        it = None if item_idx is None else np.ascontiguousarray(item_idx, dtype=np.int32)
-        n_sel = self.cfg.n_items if it is None else len(it)
-        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
-        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
-            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
-        cols = np.empty((len(qi), k), dtype=np.int32)
-        scores = np.empty((len(qi), k), dtype=np.float32)
-        _chk(lib().g4r_similar_items(self.h, SIM_SPACES[space], SIM_METRICS[metric], _i32(qi), len(qi), None if it is None else _i32(it),
-                                     n_sel, k, 1 if exclude_self else 0, None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                     _i32(cols), _f32(scores)))
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        mask = _mask(excl_mask, self.cfg.n_items)
+        cols, scores = _topk_out((len(qi), k))
+        _chk(lib().g4r_similar_items(self.h, SIM_SPACES[space], SIM_METRICS[metric], _i32(qi), len(qi), _i32(it), n_sel, k,
+                                     1 if exclude_self else 0, _u32(mask), _i32(cols), _f32(scores)))
         return cols, scores
 
     def sim_norms(self):
@@ -625,34 +609,20 @@ class Model:
         ii = np.ascontiguousarray(in_idx, dtype=np.int32)
         offs, items = self._cand_csr(cand_offs, cand_items, len(ii))
         scores, pos = self._cand_out(offs, k)
-        _chk(lib().g4r_score_candidates(self.h, _i32(ii), len(ii), _i64(offs), _i32(items), k, _f32(scores),
-                                        None if pos is None else _i32(pos)))
+        _chk(lib().g4r_score_candidates(self.h, _i32(ii), len(ii), _i64(offs), _i32(items), k, _f32(scores), _i32(pos)))
         return scores if k == 0 else (pos, scores)
 
     def score_candidates_sessions(self, hist_offs, hist_items, cand_offs, cand_items, k=0, hidden=None, return_hidden=False):
         """score_candidates after replaying whole session histories, without the prediction state (g4r_score_candidates_sessions):
         histories and hidden as in recommend_sessions, one candidate list per session.  Returns what score_candidates returns,
         + the list of hidden states after the last items with return_hidden=True."""
-        ho = np.ascontiguousarray(hist_offs, dtype=np.int64)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32)
-        n = len(ho) - 1
-        if n < 1 or ho[0] < 0 or ho[-1] > len(hi):
-            raise ValueError('hist_offs must hold n + 1 >= 2 offsets into hist_items')
+        ho, hi, n = _hist(hist_offs, hist_items)
         offs, items = self._cand_csr(cand_offs, cand_items, n)
-        h0 = None
-        if hidden is not None:
-            if len(hidden) != len(self.layers):
-                raise ValueError('hidden holds %d arrays, one per layer (%d) is needed' % (len(hidden), len(self.layers)))
-            h0 = [np.ascontiguousarray(h, dtype=np.float32) for h in hidden]
-            for l, h in enumerate(h0):
-                if h.shape != (n, self.layers[l]):
-                    raise ValueError('hidden[%d] has shape %s, (%d, %d) is needed' % (l, h.shape, n, self.layers[l]))
-        hout = [np.empty((n, D), dtype=np.float32) for D in self.layers] if return_hidden else None
-        P = C.POINTER(C.c_float) * len(self.layers)
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        hout, houtp = _hidden_out(n, self.layers, return_hidden)
         scores, pos = self._cand_out(offs, k)
-        _chk(lib().g4r_score_candidates_sessions(self.h, _i64(ho), _i32(hi), n, None if h0 is None else P(*[_f32(h) for h in h0]),
-                                                 _i64(offs), _i32(items), k, _f32(scores), None if pos is None else _i32(pos),
-                                                 None if hout is None else P(*[_f32(h) for h in hout])))
+        _chk(lib().g4r_score_candidates_sessions(self.h, _i64(ho), _i32(hi), n, h0p, _i64(offs), _i32(items), k, _f32(scores), _i32(pos),
+                                                 houtp))
         out = scores if k == 0 else (pos, scores)
         return (out, hout) if return_hidden else out
 
@@ -665,20 +635,15 @@ class Model:
     # -- multi-GPU
     def evaluate(self, plan, batch, items, cutoffs, mode):
         """Whole evaluation in one call (g4r_evaluate).  Returns (recall_sum[n_cut], mrr_sum[n_cut], n_events)."""
-        T = int(plan['T'])
         cuts = np.ascontiguousarray(cutoffs, dtype=np.int32)
         rec = np.zeros(len(cuts), dtype=np.float64)
         mrr = np.zeros(len(cuts), dtype=np.float64)
         n = C.c_int64(0)
-        it = None if items is None else np.ascontiguousarray(items, dtype=np.int32)
-        nc = int(plan.get('n_compact', 0))
-        cs = np.ascontiguousarray(plan['compact_steps'], dtype=np.int64) if nc else np.zeros(1, dtype=np.int64)
-        cm = np.ascontiguousarray(plan['compact_maps'], dtype=np.int32) if nc else np.zeros((1, batch), dtype=np.int32)
-        arr = {k: np.ascontiguousarray(plan[k]) for k in ('in_idx', 'out_idx', 'reset', 'M')}
-        _chk(lib().g4r_evaluate(self.h, _i32(arr['in_idx']), _i32(arr['out_idx']), _u8(arr['reset']), _i32(arr['M']), T, batch,
-                                _i64(cs), _i32(cm), nc, None if it is None else _i32(it), 0 if it is None else len(it),
-                                _i32(cuts), len(cuts), RANK_MODES[mode], rec.ctypes.data_as(C.POINTER(C.c_double)),
-                                mrr.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        it = _arr(items, np.int32)
+        in_idx, out_idx, reset, M, cs, cm, nc = _plan(plan, batch)
+        _chk(lib().g4r_evaluate(self.h, _i32(in_idx), _i32(out_idx), _u8(reset), _i32(M), int(plan['T']), batch, _i64(cs), _i32(cm), nc,
+                                _i32(it), 0 if it is None else len(it), _i32(cuts), len(cuts), RANK_MODES[mode], _f64(rec), _f64(mrr),
+                                C.byref(n)))
         return rec, mrr, int(n.value)
 
     def recommend_events(self, plan, batch, items, mode, slot, n_slots, k, excl_mask=None, seen=None, want_lists=True):
@@ -687,36 +652,26 @@ class Model:
         evaluation.seen_tables plus 'sess' / 'pos' int32[T, batch].  Returns (items int32[n_slots, k], scores float32[n_slots, k],
         rank float32[n_slots], target_score float32[n_slots]); items / scores are None with want_lists=False."""
         T = int(plan['T'])
-        it = None if items is None else np.ascontiguousarray(items, dtype=np.int32)
-        nc = int(plan.get('n_compact', 0))
-        cs = np.ascontiguousarray(plan['compact_steps'], dtype=np.int64) if nc else np.zeros(1, dtype=np.int64)
-        cm = np.ascontiguousarray(plan['compact_maps'], dtype=np.int32) if nc else np.zeros((1, batch), dtype=np.int32)
-        arr = {key: np.ascontiguousarray(plan[key]) for key in ('in_idx', 'out_idx', 'reset', 'M')}
+        it = _arr(items, np.int32)
+        in_idx, out_idx, reset, M, cs, cm, nc = _plan(plan, batch)
         sl = np.ascontiguousarray(slot, dtype=np.int64)
         if sl.size != T * batch:
             raise ValueError('slot must hold T * batch = %d entries' % (T * batch))
-        mask = None if excl_mask is None else np.ascontiguousarray(excl_mask, dtype=np.uint32)
-        if mask is not None and len(mask) < (self.cfg.n_items + 31) // 32:
-            raise ValueError('excl_mask must hold ceil(n_items / 32) words')
-        u32p = C.POINTER(C.c_uint32)
+        mask = _mask(excl_mask, self.cfg.n_items)
         if seen is None:
             st = (None, None, None, 0, None, None)
-            keep = ()
         else:
-            keep = (np.ascontiguousarray(seen['offs'], dtype=np.int64), np.ascontiguousarray(seen['items'], dtype=np.int32),
-                    np.ascontiguousarray(seen['first'], dtype=np.int32), np.ascontiguousarray(seen['sess'], dtype=np.int32),
-                    np.ascontiguousarray(seen['pos'], dtype=np.int32))
-            if keep[3].size != T * batch or keep[4].size != T * batch or len(keep[1]) != len(keep[2]) or keep[0][-1] > len(keep[1]):
+            so, si, sf, ss, sp = (np.ascontiguousarray(seen[key], dtype=t) for key, t in (
+                ('offs', np.int64), ('items', np.int32), ('first', np.int32), ('sess', np.int32), ('pos', np.int32)))
+            if ss.size != T * batch or sp.size != T * batch or len(si) != len(sf) or so[-1] > len(si):
                 raise ValueError('seen tables: sess / pos must hold T * batch entries, items / first one entry per offset')
-            st = (_i64(keep[0]), _i32(keep[1]), _i32(keep[2]), len(keep[0]) - 1, _i32(keep[3]), _i32(keep[4]))
-        oi = np.empty((n_slots, k), dtype=np.int32) if want_lists else None
-        os_ = np.empty((n_slots, k), dtype=np.float32) if want_lists else None
+            st = (_i64(so), _i32(si), _i32(sf), len(so) - 1, _i32(ss), _i32(sp))
+        oi, os_ = _topk_out((n_slots, k)) if want_lists else (None, None)
         rk = np.empty(n_slots, dtype=np.float32)
         ts = np.empty(n_slots, dtype=np.float32)
-        _chk(lib().g4r_recommend_events(self.h, _i32(arr['in_idx']), _i32(arr['out_idx']), _u8(arr['reset']), _i32(arr['M']), T, batch,
-                                        _i64(cs), _i32(cm), nc, None if it is None else _i32(it), 0 if it is None else len(it),
-                                        RANK_MODES[mode], _i64(sl), n_slots, k, None if mask is None else mask.ctypes.data_as(u32p), *st,
-                                        None if oi is None else _i32(oi), None if os_ is None else _f32(os_), _f32(rk), _f32(ts)))
+        _chk(lib().g4r_recommend_events(self.h, _i32(in_idx), _i32(out_idx), _u8(reset), _i32(M), T, batch, _i64(cs), _i32(cm), nc,
+                                        _i32(it), 0 if it is None else len(it), RANK_MODES[mode], _i64(sl), n_slots, k, _u32(mask), *st,
+                                        _i32(oi), _f32(os_), _f32(rk), _f32(ts)))
         return oi, os_, rk, ts
 
     def events_launches(self):
@@ -783,8 +738,8 @@ class Model:
         counts = np.array([len(p[0]) for p in parts], dtype=np.int64)
         ids = [np.ascontiguousarray(p[0], dtype=np.int32) for p in parts]
         rows = [np.ascontiguousarray(p[1], dtype=np.float32) for p in parts]
-        pi = (C.POINTER(C.c_int32) * n)(*[_i32(a) for a in ids])
-        pr = (C.POINTER(C.c_float) * n)(*[_f32(a) for a in rows])
+        pi = (i32p * n)(*[_i32(a) for a in ids])
+        pr = (f32p * n)(*[_f32(a) for a in rows])
         _chk(lib().g4r_sync_import(self.h, group, n, _i64(counts), pi, pr))
 
     def comm_min(self, value):

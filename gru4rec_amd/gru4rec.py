@@ -73,6 +73,37 @@ def _markers(*names):
     return out
 
 
+def _check_k(k, n_sel=None, name='k', cap=_native.G4R_TOPK_MAX, bools=False, own_errors=False):
+    """The k (or beams) of a selection, checked, as an int: an integer in [1, min(n_sel, cap)]; n_sel None (score_candidates*, whose
+    lists have their own lengths and whose k may also be None): in [1, cap].  bools: True counts as 1.  own_errors: what int() itself
+    refuses (a string, None) is refused with this message too; otherwise int's own ValueError / TypeError is let through."""
+    try:
+        ok = (bools or not isinstance(k, bool)) and int(k) == k and 1 <= k <= (cap if n_sel is None else min(n_sel, cap))
+    except (TypeError, ValueError):
+        if not own_errors:
+            raise
+        ok = False
+    if not ok and n_sel is None:
+        raise ValueError('%s = %r: it must be None or an integer in [1, %d]' % (name, k, cap))
+    if not ok:
+        raise ValueError('%s = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (name, k, n_sel, cap))
+    return int(k)
+
+
+def _check_steps(steps):
+    try:
+        ok = not isinstance(steps, bool) and int(steps) == steps and steps >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('steps = %r: it must be an integer >= 1' % (steps,))
+    return int(steps)
+
+
+def _scan_kw(over):      # the keyword of the device model's two-stage selection; the exact one is called without it
+    return {} if over is None else dict(oversample=over)
+
+
 class GRU4Rec:
     """Same constructor arguments and defaults as the reference (gru4rec.py:97-101)."""
 
@@ -833,11 +864,7 @@ class GRU4Rec:
         if extra is not None:
             pr.append(np.asarray(extra[0], dtype=np.int64))
             pi.append(np.asarray(extra[1], dtype=np.int64))
-        gidx = np.zeros(0, dtype=np.int64)
-        if exclude is not None:
-            ex = exclude if isinstance(exclude, np.ndarray) else list(exclude)
-            if len(ex):
-                gidx = np.unique(self.itemidmap[np.ravel(ex)].values.astype(np.int64))
+        gidx, mask = self._global_exclude(exclude)
         key = np.unique(np.concatenate(pr) * n_items + np.concatenate(pi))
         r, it = key // n_items, key % n_items
         counts = np.bincount(r, minlength=rows)
@@ -867,14 +894,49 @@ class GRU4Rec:
             if len(short):
                 raise ValueError('row %d has %d eligible candidate positions, fewer than k + steps - 1 = %d (every generated item takes '
                                  'one)' % (short[0], elig[short[0]], k + grow))
-        offs = items = mask = None
+        offs = items = None
         if extra is not None or exclude_per_row is not None:
             offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
             items = it.astype(np.int32)
-        if len(gidx):
-            mask = np.zeros((n_items + 31) // 32, dtype=np.uint32)
-            np.bitwise_or.at(mask, gidx >> 5, np.left_shift(1, gidx & 31).astype(np.uint32))
         return offs, items, mask
+
+    def _global_exclude(self, exclude):
+        """`exclude`, the item ids excluded in every row, as (their distinct item indices, sorted, int64; the bit mask of
+        g4r_recommend_step_filtered over them, None when there are none)."""
+        gidx, mask = np.zeros(0, dtype=np.int64), None
+        if exclude is not None:
+            ex = exclude if isinstance(exclude, np.ndarray) else list(exclude)
+            if len(ex):
+                gidx = np.unique(self.itemidmap[np.ravel(ex)].values.astype(np.int64))
+                mask = np.zeros((len(self.itemidmap) + 31) // 32, dtype=np.uint32)
+                np.bitwise_or.at(mask, gidx >> 5, np.left_shift(1, gidx & 31).astype(np.uint32))
+        return gidx, mask
+
+    def _session_exclusions(self, N, lens, hidx, k, iidx, history, exclude, exclude_per_row, steps=None):
+        """_pack_exclusions for a stateless call over N histories (lengths lens, item indices hidx).  history: every row's list holds
+        its own history (exclude_history, no_repeat).  steps (None: the call generates nothing): with history, every row's list gains
+        steps - 1 generated items on the device, which needs duplicate-free candidates."""
+        if steps is not None and history and iidx is not None and len(np.unique(iidx)) != len(iidx):
+            raise ValueError('no_repeat needs duplicate-free predict_for_item_ids: every generated item must take exactly one candidate '
+                             'position')
+        if not history and exclude is None and exclude_per_row is None:
+            return None, None, None
+        hist_rows = (np.repeat(np.arange(N), lens), hidx) if history else None
+        return self._pack_exclusions(N, k, iidx, hist_rows, 'the history', exclude, exclude_per_row,
+                                     grow=steps - 1 if steps is not None and history else 0)
+
+    def _n_candidates(self, predict_for_item_ids):
+        return len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
+
+    def _candidates(self, predict_for_item_ids):
+        """The candidates of a call: (their item indices, None for all items; their ids in candidate order).  An unknown id raises
+        KeyError here, which is why the k check, which comes first, takes the count from _n_candidates."""
+        if predict_for_item_ids is None:
+            return None, self.itemidmap.index.values
+        return self.itemidmap[predict_for_item_ids].values, np.asarray(predict_for_item_ids)
+
+    def _unpad_hidden(self, H):      # the states a device call returned (4-padded columns) in the layout of `hidden`
+        return [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(H, self.layers)]
 
     def predict_next_batch(self, session_ids, input_item_ids, predict_for_item_ids=None, batch=100):
         """Scores for the next item of every session in the batch.  Rows: items, columns: batch events."""
@@ -936,23 +998,17 @@ class GRU4Rec:
         advances exactly as with scan='fp32'.  The bf16 copy of Wy is built on the first such call and after every change of Wy."""
         if self.error_during_train:
             raise Exception
-        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
-        if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
-            raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        k = _check_k(k, self._n_candidates(predict_for_item_ids), bools=True)
         over = self._scan_oversample(scan, oversample, k)
         plan = self._predict_plan(session_ids, input_item_ids, batch)
-        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
+        iidx, cand = self._candidates(predict_for_item_ids)
         filtered = exclude_seen or exclude is not None or exclude_per_row is not None
-        if filtered:
-            offs, items, mask = self._exclusions(plan, int(k), iidx, exclude_seen, exclude, exclude_per_row)
+        excl = self._exclusions(plan, k, iidx, exclude_seen, exclude, exclude_per_row) if filtered else ()
         m, in_idxs = self._predict_rows(session_ids, input_item_ids, batch, plan=plan)
-        if over is not None:
-            cols, scores = m.recommend_step_filtered(in_idxs, iidx, int(k), *((offs, items, mask) if filtered else ()), oversample=over)
-        elif filtered:
-            cols, scores = m.recommend_step_filtered(in_idxs, iidx, int(k), offs, items, mask)
+        if filtered or over is not None:
+            cols, scores = m.recommend_step_filtered(in_idxs, iidx, k, *excl, **_scan_kw(over))
         else:
-            cols, scores = m.recommend_step(in_idxs, iidx, int(k))
-        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
+            cols, scores = m.recommend_step(in_idxs, iidx, k)      # (the unfiltered exact selection is an entry of its own)
         return cand[cols], scores
 
     def _session_inputs(self, histories, hidden):
@@ -1003,25 +1059,16 @@ class GRU4Rec:
         dtype) raises ValueError, an unknown item id KeyError, and the k / exclusion checks are those of recommend_next_batch."""
         if self.error_during_train:
             raise Exception
-        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
-        if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
-            raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        k = _check_k(k, self._n_candidates(predict_for_item_ids), bools=True)
         over = self._scan_oversample(scan, oversample, k)
         N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
-        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
-        xoffs = xitems = mask = None
-        if exclude_history or exclude is not None or exclude_per_row is not None:
-            hist_rows = (np.repeat(np.arange(N), lens), hidx) if exclude_history else None
-            xoffs, xitems, mask = self._pack_exclusions(N, int(k), iidx, hist_rows, 'the history', exclude, exclude_per_row)
+        iidx, cand = self._candidates(predict_for_item_ids)
+        excl = self._session_exclusions(N, lens, hidx, k, iidx, exclude_history, exclude, exclude_per_row)
         m = self._ensure_model()
-        if over is None:
-            out = m.recommend_sessions(offs, hidx, iidx, int(k), xoffs, xitems, mask, hidden=h0, return_hidden=return_hidden)
-        else:
-            out = m.recommend_sessions(offs, hidx, iidx, int(k), xoffs, xitems, mask, hidden=h0, return_hidden=return_hidden, oversample=over)
-        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
+        out = m.recommend_sessions(offs, hidx, iidx, k, *excl, hidden=h0, return_hidden=return_hidden, **_scan_kw(over))
         if not return_hidden:
             return cand[out[0]], out[1]
-        return cand[out[0]], out[1], [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(out[2], self.layers)]
+        return cand[out[0]], out[1], self._unpad_hidden(out[2])
 
     def continue_sessions(self, histories, steps, k=1, no_repeat=True, predict_for_item_ids=None, exclude=None, exclude_per_row=None,
                           hidden=None, return_hidden=False, scan='fp32', oversample=8):
@@ -1052,34 +1099,17 @@ class GRU4Rec:
         ValueError naming the row."""
         if self.error_during_train:
             raise Exception
-        try:
-            steps_ok = not isinstance(steps, bool) and int(steps) == steps and steps >= 1
-        except (TypeError, ValueError):
-            steps_ok = False
-        if not steps_ok:
-            raise ValueError('steps = %r: it must be an integer >= 1' % (steps,))
-        steps = int(steps)
-        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
-        if int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
-            raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        steps = _check_steps(steps)
+        k = _check_k(k, self._n_candidates(predict_for_item_ids), bools=True)
         over = self._scan_oversample(scan, oversample, k)
         N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
-        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
-        if no_repeat and iidx is not None and len(np.unique(iidx)) != len(iidx):
-            raise ValueError('no_repeat needs duplicate-free predict_for_item_ids: every generated item must take exactly one candidate '
-                             'position')
-        xoffs = xitems = mask = None
-        if no_repeat or exclude is not None or exclude_per_row is not None:
-            hist_rows = (np.repeat(np.arange(N), lens), hidx) if no_repeat else None
-            xoffs, xitems, mask = self._pack_exclusions(N, int(k), iidx, hist_rows, 'the history', exclude, exclude_per_row,
-                                                        grow=steps - 1 if no_repeat else 0)
+        iidx, cand = self._candidates(predict_for_item_ids)
+        excl = self._session_exclusions(N, lens, hidx, k, iidx, no_repeat, exclude, exclude_per_row, steps=steps)
         m = self._ensure_model()
-        out = m.continue_sessions(offs, hidx, iidx, int(k), steps, bool(no_repeat), xoffs, xitems, mask, hidden=h0,
-                                  return_hidden=return_hidden, oversample=over)
-        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
+        out = m.continue_sessions(offs, hidx, iidx, k, steps, bool(no_repeat), *excl, hidden=h0, return_hidden=return_hidden, oversample=over)
         if not return_hidden:
             return cand[out[0]], out[1]
-        return cand[out[0]], out[1], [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(out[2], self.layers)]
+        return cand[out[0]], out[1], self._unpad_hidden(out[2])
 
     def beam_sessions(self, histories, steps, beams=4, no_repeat=True, predict_for_item_ids=None, exclude=None, exclude_per_row=None,
                       hidden=None, combine=None, scan='fp32', oversample=8):
@@ -1115,21 +1145,8 @@ class GRU4Rec:
         device returns (_native.beam_backtrack)."""
         if self.error_during_train:
             raise Exception
-        try:
-            steps_ok = not isinstance(steps, bool) and int(steps) == steps and steps >= 1
-        except (TypeError, ValueError):
-            steps_ok = False
-        if not steps_ok:
-            raise ValueError('steps = %r: it must be an integer >= 1' % (steps,))
-        steps = int(steps)
-        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
-        try:
-            beams_ok = not isinstance(beams, bool) and int(beams) == beams and 1 <= beams <= min(n_sel, _native.G4R_BEAM_MAX)
-        except (TypeError, ValueError):
-            beams_ok = False
-        if not beams_ok:
-            raise ValueError('beams = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (beams, n_sel, _native.G4R_BEAM_MAX))
-        beams = int(beams)
+        steps = _check_steps(steps)
+        beams = _check_k(beams, self._n_candidates(predict_for_item_ids), name='beams', cap=_native.G4R_BEAM_MAX, own_errors=True)
         softmax = self._final[0] in (_native.ACT_IDS['softmax'], _native.ACT_IDS['softmax_logit'])      # (is_softmax of the C side)
         if combine is None:
             combine = 'product' if softmax else 'sum'
@@ -1139,20 +1156,12 @@ class GRU4Rec:
             raise ValueError("combine='product' multiplies probabilities: it needs final_act softmax / softmax_logit, not %r" % self.final_act)
         over = self._scan_oversample(scan, oversample, beams)
         N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
-        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values
-        if no_repeat and iidx is not None and len(np.unique(iidx)) != len(iidx):
-            raise ValueError('no_repeat needs duplicate-free predict_for_item_ids: every generated item must take exactly one candidate '
-                             'position')
-        xoffs = xitems = mask = None
-        if no_repeat or exclude is not None or exclude_per_row is not None:
-            hist_rows = (np.repeat(np.arange(N), lens), hidx) if no_repeat else None
-            xoffs, xitems, mask = self._pack_exclusions(N, beams, iidx, hist_rows, 'the history', exclude, exclude_per_row,
-                                                        grow=steps - 1 if no_repeat else 0)
+        iidx, cand = self._candidates(predict_for_item_ids)
+        excl = self._session_exclusions(N, lens, hidx, beams, iidx, no_repeat, exclude, exclude_per_row, steps=steps)
         m = self._ensure_model()
-        parent, cols, sscores, path_scores, scale_exp = m.beam_sessions(offs, hidx, iidx, beams, steps, bool(no_repeat), combine, xoffs,
-                                                                        xitems, mask, hidden=h0, oversample=over)
+        parent, cols, sscores, path_scores, scale_exp = m.beam_sessions(offs, hidx, iidx, beams, steps, bool(no_repeat), combine, *excl,
+                                                                        hidden=h0, oversample=over)
         paths, step_scores = _native.beam_backtrack(parent, cols, sscores)
-        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
         return cand[paths], path_scores, step_scores, scale_exp
 
     # ------------------------------------------------------------------ per-row candidate lists (not in the reference)
@@ -1181,14 +1190,13 @@ class GRU4Rec:
         if lens.sum() > _native.G4R_CAND_MAX:
             raise ValueError('%d candidate positions in one call: at most G4R_CAND_MAX = %d' % (lens.sum(), _native.G4R_CAND_MAX))
         if k is not None:
-            if isinstance(k, bool) or int(k) != k or not 1 <= k <= _native.G4R_TOPK_MAX:
-                raise ValueError('k = %r: it must be None or an integer in [1, %d]' % (k, _native.G4R_TOPK_MAX))
+            k = _check_k(k)
             short = np.flatnonzero(lens < k)
             if len(short):
                 raise ValueError('candidate list %d holds %d positions, fewer than k = %d' % (short[0], lens[short[0]], k))
         cidx = self.itemidmap[flat].values.astype(np.int32)
         offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        return offs, cidx, flat, width, 0 if k is None else int(k)
+        return offs, cidx, flat, width, k or 0
 
     @staticmethod
     def _candidate_result(out, offs, flat, width, k):
@@ -1247,7 +1255,7 @@ class GRU4Rec:
         if not return_hidden:
             return self._candidate_result(out, offs, flat, width, kk)
         res = self._candidate_result(out[0], offs, flat, width, kk)
-        H = [np.ascontiguousarray(_strip_cols(h, 1, D, _pad4(D))) for h, D in zip(out[1], self.layers)]
+        H = self._unpad_hidden(out[1])
         return (res, H) if kk == 0 else (res[0], res[1], H)
 
     # ------------------------------------------------------------------ item-to-item neighbours (not in the reference)
@@ -1274,9 +1282,8 @@ class GRU4Rec:
         bad k, metric or space, or a query with fewer than k eligible candidate positions (duplicates count), raises ValueError."""
         if self.error_during_train:
             raise Exception
-        n_sel = len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
-        if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
-            raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+        n_sel = self._n_candidates(predict_for_item_ids)
+        k = _check_k(k, n_sel)
         if metric not in _native.SIM_METRICS:
             raise ValueError("metric = %r: it must be 'cosine' or 'dot'" % (metric,))
         if space not in _native.SIM_SPACES:
@@ -1288,31 +1295,23 @@ class GRU4Rec:
         if len(ids) < 1:
             raise ValueError('item_ids is empty: at least one query item is needed')
         qidx = self.itemidmap[ids].values.astype(np.int32)
-        iidx = None if predict_for_item_ids is None else self.itemidmap[predict_for_item_ids].values.astype(np.int32)
-        n_items = len(self.itemidmap)
-        gidx = np.zeros(0, dtype=np.int64)
-        if exclude is not None:
-            ex = exclude if isinstance(exclude, np.ndarray) else list(exclude)
-            if len(ex):
-                gidx = np.unique(self.itemidmap[np.ravel(ex)].values.astype(np.int64))
+        iidx, cand = self._candidates(predict_for_item_ids)
+        if iidx is not None:
+            iidx = iidx.astype(np.int32)
+        gidx, mask = self._global_exclude(exclude)
         # eligible candidate positions per query: all - positions of excluded items - (exclude_self) positions of its own item
         if iidx is None:
             n_masked, own = len(gidx), np.ones(len(qidx), dtype=np.int64)
         else:
             n_masked = int(np.isin(iidx, gidx).sum())
-            own = np.bincount(iidx, minlength=n_items)[qidx]
+            own = np.bincount(iidx, minlength=len(self.itemidmap))[qidx]
         elig = n_sel - n_masked - (np.where(np.isin(qidx, gidx), 0, own) if exclude_self else 0) * np.ones(len(qidx), dtype=np.int64)
         short = np.flatnonzero(elig < k)
         if len(short):
             raise ValueError('query %d (item id %r) has %d eligible candidate positions, fewer than k = %d'
                              % (short[0], getattr(ids[short[0]], 'item', lambda: ids[short[0]])(), elig[short[0]], k))
-        mask = None
-        if len(gidx):
-            mask = np.zeros((n_items + 31) // 32, dtype=np.uint32)
-            np.bitwise_or.at(mask, gidx >> 5, np.left_shift(1, gidx & 31).astype(np.uint32))
         m = self._ensure_model()
-        cols, scores = m.similar_items(qidx, iidx, int(k), metric, space, bool(exclude_self), mask)
-        cand = self.itemidmap.index.values if predict_for_item_ids is None else np.asarray(predict_for_item_ids)
+        cols, scores = m.similar_items(qidx, iidx, k, metric, space, bool(exclude_self), mask)
         return cand[cols], scores
 
     def item_neighbors(self, k=20, metric='cosine', space='output', exclude=None):

@@ -221,3 +221,16 @@ def test_rescale_rule():
         cum, e = rescale(combine_scores(cum, f(3 * 2.0 ** -10), 'product'))
         scale += e
     assert scale < -126 and 1 <= cum[0] < 2
+
+
+def test_what_beams_is_taken_as():
+    """2.0 counts as 2 (the device receives an int); True, 2.5, a string, None, 0 and number of candidates + 1 are all refused with
+    the call's own message."""
+    g = _model()
+    cand = ids(40, 7, 41, 3, 9)
+    paths, path_scores, _, _ = g.beam_sessions([ids(1)], 2, beams=2.0, predict_for_item_ids=cand)
+    got = g._model.calls[-1]['beams']
+    assert got == 2 and type(got) is int and paths.shape == (1, 2, 2) and path_scores.shape == (1, 2)
+    for beams in (True, 2.5, 'a', None, 0, 6):
+        refused(g, ValueError, r'beams = %r: it must be an integer in \[1, min\(number of candidates = 5, %d\)\]' % (beams, BMAX),
+                [ids(1)], 2, beams=beams, predict_for_item_ids=cand)

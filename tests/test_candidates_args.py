@@ -205,3 +205,28 @@ def test_sessions_refusals_and_the_untouched_prediction_state():
     assert_same_state(before[:4] + (after[4],), after)
     g.error_during_train = True
     _refused_sessions(g, Exception)
+
+
+def test_what_k_is_taken_as():
+    """None is the scores of every position; 2.0 counts as 2 (the device receives an int); True, 2.5, 0 and G4R_TOPK_MAX + 1 are
+    refused with the call's own message, a k above a list's length with the list's; a string fails inside int(), with int's own
+    error.  The same for the two calls."""
+    g = _model()
+    cand = [ids(40, 7, 41, 3, 9)]
+    calls = (('cand', lambda **kw: g.score_candidates(np.array([1]), ids(10), cand, batch=1, **kw)),
+             ('cand_sessions', lambda **kw: g.score_candidates_sessions([ids(10)], cand, **kw)))
+    for kind, f in calls:
+        scores = f(k=None)
+        assert g._model.last(kind)[1]['k'] == 0 and len(scores) == 1 and scores[0].shape == (5,)
+        items, scores = f(k=2.0)
+        got = g._model.last(kind)[1]['k']
+        assert got == 2 and type(got) is int and items.shape == scores.shape == (1, 2)
+        n = len(g._model.calls)
+        for k in (True, 2.5, 0, _native.G4R_TOPK_MAX + 1):
+            with pytest.raises(ValueError, match='k = %r: it must be None or an integer in' % (k,)):
+                f(k=k)
+        with pytest.raises(ValueError, match='candidate list 0 holds 5 positions, fewer than k = 6'):
+            f(k=6)
+        with pytest.raises(ValueError, match='invalid literal'):
+            f(k='a')
+        assert len(g._model.calls) == n

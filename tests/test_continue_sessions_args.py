@@ -246,3 +246,18 @@ def test_the_prediction_state_is_untouched():
     assert after[4] == before[4] + 1 and g._model.calls[-1][0] == 'continue'
     assert_same_state(before[:4] + (0,), after[:4] + (0,))
     assert pickle.dumps(g) == blob
+
+
+def test_what_k_is_taken_as():
+    """True counts as 1 and 2.0 as 2 (the device receives an int); 2.5, 0 and number of candidates + 1 are refused with the call's own
+    message; a string and None fail inside int(), with int's own error."""
+    g = _model()
+    cand = ids(40, 7, 41, 3, 9)
+    for k, want in ((True, 1), (2.0, 2)):
+        items, scores = g.continue_sessions([ids(1)], 2, k=k, predict_for_item_ids=cand)
+        got = g._model.last('continue')[1]['k']
+        assert got == want and type(got) is int and items.shape == scores.shape == (1, 2, want)
+    for k in (2.5, 0, 6):
+        _refused(g, ValueError, match='k = %r: it must be an integer in' % (k,), histories=[ids(1)], k=k, predict_for_item_ids=cand)
+    _refused(g, ValueError, match='invalid literal', histories=[ids(1)], k='a', predict_for_item_ids=cand)
+    _refused(g, TypeError, histories=[ids(1)], k=None, predict_for_item_ids=cand)

@@ -223,3 +223,22 @@ def test_exclude_max_names_the_history():
     with pytest.raises(ValueError, match='the history'):
         g.recommend_sessions([ids(*range(1025))], exclude_history=True)
     assert _native.G4R_EXCLUDE_MAX == 1024
+
+
+def test_what_k_is_taken_as():
+    """True counts as 1 and 2.0 as 2 (the device receives an int); 2.5, 0 and number of candidates + 1 are refused with the call's own
+    message; a string and None fail inside int(), with int's own error."""
+    g = _model()
+    cand = ids(40, 7, 41, 3, 9)
+    for k, want in ((True, 1), (2.0, 2)):
+        items, scores = g.recommend_sessions([ids(1)], k=k, predict_for_item_ids=cand)
+        got = g._model.last('sessions')[1]['k']
+        assert got == want and type(got) is int and items.shape == scores.shape == (1, want)
+    before = state(g)
+    for k in (2.5, 0, 6):
+        with pytest.raises(ValueError, match='k = %r: it must be an integer in' % (k,)):
+            g.recommend_sessions([ids(1)], k=k, predict_for_item_ids=cand)
+    with pytest.raises(ValueError, match='invalid literal'):
+        g.recommend_sessions([ids(1)], k='a', predict_for_item_ids=cand)
+    _refused(g, TypeError, histories=[ids(1)], k=None, predict_for_item_ids=cand)
+    assert_same_state(before, state(g))

@@ -133,3 +133,23 @@ def test_config_struct_size_is_unchanged():
 
 def test_mutant_13_is_listed():
     assert 13 in g4r_build.MUTANTS and 'POSITION' in g4r_build.MUTANTS[13]
+
+
+def test_what_k_is_taken_as():
+    """2.0 counts as 2; True, 2.5, 0 and number of candidates + 1 are refused with the call's own message; a string and None fail
+    inside int(), with int's own error."""
+    g = _model_without_device()
+    cand = np.array([1000, 1005, 1005, 1007, 1009])
+    with pytest.raises(AssertionError, match='touched the device'):
+        g.similar_items([1001], k=2.0, predict_for_item_ids=cand)
+    for k in (True, 2.5, 0, 6):
+        with pytest.raises(ValueError, match='k = %r: it must be an integer in' % (k,)):
+            g.similar_items([1001], k=k, predict_for_item_ids=cand)
+    with pytest.raises(ValueError, match='invalid literal'):
+        g.similar_items([1001], k='a', predict_for_item_ids=cand)
+    with pytest.raises(TypeError):
+        g.similar_items([1001], k=None, predict_for_item_ids=cand)
+    with pytest.raises(ValueError, match='invalid literal'):
+        g.item_neighbors(k='a')
+    with pytest.raises(TypeError):
+        g.item_neighbors(k=None)

@@ -12,39 +12,13 @@ and so run on the parent commit too (the baselines): --loop-only times the host 
 512 x beams rows with k = beams, the same GRU steps and selections per step without k_beam_select / k_beam_advance."""
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
-import pandas as pd
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from gru4rec_amd import _native  # noqa: E402
-from gru4rec_amd.gru4rec import GRU4Rec  # noqa: E402
+from bench_common import as_gru4rec, serving_model
 
 N_ITEMS, UNITS, ROWS = 37_483, 100, 512
-
-
-def model(I, D, rng):
-    """A GRU4Rec around a device model with random weights (no fit: only the serving path is timed)."""
-    g = GRU4Rec(layers=[D], final_act='linear', loss='bpr-max')
-    g.itemidmap = pd.Series(data=np.arange(I), index=np.arange(I) + 1000, name='ItemIdx')
-    g.n_items = I
-    g.error_during_train = False
-    m = _native.Model(n_items=I, layers=[D], batch_size=ROWS, n_sample=0, loss=_native.LOSS_IDS['bpr-max'], final_act=_native.ACT_IDS['linear'],
-                      hidden_act=_native.ACT_IDS['tanh'], embed_mode=0, embedding=0, learning_rate=0.1, sample_store=0, seed=1, device=0,
-                      rank=0, nranks=1, use_graph=0)
-    blk = 4093
-    m.set_param('Wy', np.tile((rng.randn(blk, D) * 0.1).astype(np.float32), (I // blk + 1, 1))[:I])     # (a random block, repeated)
-    m.set_param('By', (rng.randn(I) * 0.1).astype(np.float32))
-    m.set_param('Wx', (rng.randn(D, 3 * D) * 0.05).astype(np.float32))
-    m.set_param('Wh', (rng.randn(D, D) * 0.05).astype(np.float32))
-    m.set_param('Wrz', (rng.randn(D, 2 * D) * 0.05).astype(np.float32))
-    m.set_param('Bh', (rng.randn(3 * D) * 0.1).astype(np.float32))
-    g._model = m
-    return g
 
 
 def host_loop(g, hists, steps, W):
@@ -91,7 +65,7 @@ def main():
     ap.add_argument('--floor', action='store_true', help='time continue_sessions on 512 x beams rows, k = beams (works there too)')
     a = ap.parse_args()
     rng = np.random.RandomState(0)
-    g = model(N_ITEMS, UNITS, rng)
+    g = as_gru4rec(serving_model(N_ITEMS, UNITS, ROWS, 'linear', rng), N_ITEMS, UNITS, 'linear')
     ids = g.itemidmap.index.values
     hists = [ids[rng.randint(0, N_ITEMS, size=n)] for n in rng.randint(2, 7, size=ROWS)]
     rows = []

@@ -12,15 +12,11 @@ included) -- a lower bound of the kernel's rate, whose own time comes from a roc
 back-to-back synchronous calls over a window of at least --seconds after the warm-up."""
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from gru4rec_amd import _native  # noqa: E402
+from bench_common import serving_model
 
 SHAPES = {'10M': (10_000_000, 256, 512, 1000), 'rsc15': (37_483, 100, 128, 100)}
 
@@ -37,21 +33,6 @@ def timed(fn, seconds, warmup):
             return dt / n * 1e6
 
 
-def model(I, D, rows, act, rng):
-    sm = act.startswith('softmax')
-    m = _native.Model(n_items=I, layers=[D], batch_size=rows, n_sample=0, loss=_native.LOSS_IDS['cross-entropy' if sm else 'bpr-max'],
-                      final_act=_native.ACT_IDS[act], hidden_act=_native.ACT_IDS['tanh'], embed_mode=0, embedding=0, learning_rate=0.1,
-                      sample_store=0, seed=1, device=0, rank=0, nranks=1, use_graph=0)
-    blk = 4093
-    m.set_param('Wy', np.tile((rng.randn(blk, D) * 0.1).astype(np.float32), (I // blk + 1, 1))[:I])     # (a random block, repeated)
-    m.set_param('By', (rng.randn(I) * 0.1).astype(np.float32))
-    m.set_param('Wx', (rng.randn(D, 3 * D) * 0.05).astype(np.float32))
-    m.set_param('Wh', (rng.randn(D, D) * 0.05).astype(np.float32))
-    m.set_param('Wrz', (rng.randn(D, 2 * D) * 0.05).astype(np.float32))
-    m.set_param('Bh', (rng.randn(3 * D) * 0.1).astype(np.float32))
-    return m
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', default='10M,rsc15')
@@ -63,7 +44,7 @@ def main():
         I, D, rows, C = SHAPES[name]
         for act in a.acts.split(','):
             rng = np.random.RandomState(0)
-            m = model(I, D, rows, act, rng)
+            m = serving_model(I, D, rows, act, rng)
             in_idx = rng.randint(0, I, size=rows).astype(np.int32)
             cand = rng.randint(0, I, size=rows * C).astype(np.int32)
             offs = (np.arange(rows + 1) * C).astype(np.int64)

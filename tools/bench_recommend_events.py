@@ -6,15 +6,14 @@ existed before it (a predict_step loop with a host argpartition; recommend_sessi
     python tools/bench_recommend_events.py --items 10000000 --units 256 --batch 512 --sessions 1200 --max_len 6
 """
 import argparse
+import functools
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from gru4rec_amd import _native, evaluation      # noqa: E402
+from bench_common import serving_model, tiled_weights      # (first: it puts the repository root on sys.path)
+from gru4rec_amd import _native, evaluation
 
 
 def main():
@@ -30,18 +29,7 @@ def main():
     o = ap.parse_args()
     I, D, B, k = o.items, o.units, o.batch, o.k
     rng = np.random.RandomState(1)
-    m = _native.Model(n_items=I, layers=[D], batch_size=32, n_sample=0, loss=_native.LOSS_IDS['bpr-max'], final_act=_native.ACT_IDS['linear'],
-                      hidden_act=_native.ACT_IDS['tanh'], embed_mode=0, embedding=0, learning_rate=0.1, sample_store=0, seed=3,
-                      device=0, rank=0, nranks=1, use_graph=0)
-    block = (rng.randn(min(I, 65536), D) * 0.1).astype(np.float32)
-    Wy = np.empty((I, D), dtype=np.float32)
-    for a in range(0, I, len(block)):
-        Wy[a:a + len(block)] = block[:min(len(block), I - a)]
-    m.set_param('Wy', Wy)
-    del Wy
-    m.set_param('By', (rng.randn(I) * 0.01).astype(np.float32))
-    for name, shape in (('Wx', (D, 3 * D)), ('Wh', (D, D)), ('Wrz', (D, 2 * D)), ('Bh', (3 * D,))):
-        m.set_param(name, (rng.randn(*shape) * 0.1).astype(np.float32))
+    m = serving_model(I, D, 32, 'linear', rng, weights=functools.partial(tiled_weights, blk=min(I, 65536), by=0.01, w=0.1), seed=3)
     lens = rng.randint(2, o.max_len + 1, size=o.sessions)
     offs = np.r_[0, np.cumsum(lens)].astype(np.int64)
     titems = rng.randint(0, I, size=int(offs[-1])).astype(np.int32)

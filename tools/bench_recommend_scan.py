@@ -12,15 +12,11 @@ this script: run it under `rocprofv3 --kernel-trace --stats -- python tools/benc
 run of its own and read k_scan_bf16 / k_topk_range / k_scan_merge / k_score_cand from the kernel statistics."""
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from gru4rec_amd import _native  # noqa: E402
+from bench_common import dense_weights, serving_model
 
 SHAPES = {'10M': (10_000_000, 256, 512), 'rsc15': (37_483, 100, 128)}
 
@@ -36,23 +32,6 @@ def median_ms(fn, calls, warmup):
     return float(np.median(t) * 1e3)
 
 
-def model(I, D, rows, rng):
-    m = _native.Model(n_items=I, layers=[D], batch_size=rows, n_sample=0, loss=_native.LOSS_IDS['bpr-max'], final_act=_native.ACT_IDS['linear'],
-                      hidden_act=_native.ACT_IDS['tanh'], embed_mode=0, embedding=0, learning_rate=0.1, sample_store=0, seed=1,
-                      device=0, rank=0, nranks=1, use_graph=0)
-    Wy = np.empty((I, D), dtype=np.float32)
-    for b in range(0, I, 1 << 20):      # (in blocks: no float64 copy of the whole table)
-        Wy[b:b + (1 << 20)] = rng.standard_normal((min(1 << 20, I - b), D), dtype=np.float32) * np.float32(0.1)
-    m.set_param('Wy', Wy)
-    del Wy
-    m.set_param('By', (rng.standard_normal(I, dtype=np.float32) * np.float32(0.05)))
-    m.set_param('Wx', (rng.standard_normal((D, 3 * D)) * 0.05).astype(np.float32))
-    m.set_param('Wh', (rng.standard_normal((D, D)) * 0.05).astype(np.float32))
-    m.set_param('Wrz', (rng.standard_normal((D, 2 * D)) * 0.05).astype(np.float32))
-    m.set_param('Bh', (rng.standard_normal(3 * D) * 0.1).astype(np.float32))
-    return m
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', default='10M,rsc15')
@@ -65,7 +44,7 @@ def main():
     for name in a.shapes.split(','):
         I, D, rows = SHAPES[name]
         rng = np.random.default_rng(0)
-        m = model(I, D, rows, rng)
+        m = serving_model(I, D, rows, 'linear', rng, weights=dense_weights)
         in_idx = rng.integers(0, I, size=rows).astype(np.int32)
         m.predict_begin(rows)
         t0 = time.perf_counter()

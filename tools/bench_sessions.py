@@ -11,15 +11,12 @@ call with its T = 1 call at the same shape and activation when --lens holds 1 be
 synchronous calls over a window of at least --seconds after the warm-up."""
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from gru4rec_amd import _native, synth  # noqa: E402
+from bench_common import serving_model      # (first: it puts the repository root on sys.path)
+from gru4rec_amd import synth
 
 SHAPES = {'10M': (10_000_000, 256, 512, 20), 'rsc15': (37_483, 100, 128, 20)}
 
@@ -34,21 +31,6 @@ def timed(fn, seconds, warmup):
         dt = time.perf_counter() - t0
         if dt >= seconds:
             return dt / n * 1e6
-
-
-def model(I, D, rows, act, rng):
-    sm = act.startswith('softmax')
-    m = _native.Model(n_items=I, layers=[D], batch_size=rows, n_sample=0, loss=_native.LOSS_IDS['cross-entropy' if sm else 'bpr-max'],
-                      final_act=_native.ACT_IDS[act], hidden_act=_native.ACT_IDS['tanh'], embed_mode=0, embedding=0, learning_rate=0.1,
-                      sample_store=0, seed=1, device=0, rank=0, nranks=1, use_graph=0)
-    blk = 4093
-    m.set_param('Wy', np.tile((rng.randn(blk, D) * 0.1).astype(np.float32), (I // blk + 1, 1))[:I])     # (a random block, repeated)
-    m.set_param('By', (rng.randn(I) * 0.1).astype(np.float32))
-    m.set_param('Wx', (rng.randn(D, 3 * D) * 0.05).astype(np.float32))
-    m.set_param('Wh', (rng.randn(D, D) * 0.05).astype(np.float32))
-    m.set_param('Wrz', (rng.randn(D, 2 * D) * 0.05).astype(np.float32))
-    m.set_param('Bh', (rng.randn(3 * D) * 0.1).astype(np.float32))
-    return m
 
 
 def lengths(spec, rows):
@@ -70,7 +52,7 @@ def main():
         I, D, rows, k = SHAPES[name]
         for act in a.acts.split(','):
             rng = np.random.RandomState(0)
-            m = model(I, D, rows, act, rng)
+            m = serving_model(I, D, rows, act, rng)
             in_idx = rng.randint(0, I, size=rows).astype(np.int32)
             one = np.zeros(1, dtype=np.int32)
             m.predict_begin(rows)

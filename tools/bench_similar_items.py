@@ -18,14 +18,11 @@ Kernel times do not come from this script: run it under `rocprofv3 --kernel-trac
 import argparse
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from gru4rec_amd import _native  # noqa: E402
+from bench_common import dense_weights, serving_model
 
 PEAK_F32_MFMA = 157.3e12
 PEAK_HBM = 8.0e12
@@ -33,19 +30,9 @@ CHUNK_ROWS = 4096      # G4R_SIM_CHUNK_ROWS
 
 
 def model(I, D, rows, rng, keep_table=False):
-    m = _native.Model(n_items=I, layers=[D], batch_size=rows, n_sample=0, loss=_native.LOSS_IDS['bpr-max'], final_act=_native.ACT_IDS['linear'],
-                      hidden_act=_native.ACT_IDS['tanh'], embed_mode=0, embedding=0, learning_rate=0.1, sample_store=0, seed=1,
-                      device=0, rank=0, nranks=1, use_graph=0)
-    Wy = np.empty((I, D), dtype=np.float32)
-    for b in range(0, I, 1 << 20):      # (in blocks: no float64 copy of the whole table)
-        Wy[b:b + (1 << 20)] = rng.standard_normal((min(1 << 20, I - b), D), dtype=np.float32) * np.float32(0.1)
-    m.set_param('Wy', Wy)
-    m.set_param('By', (rng.standard_normal(I, dtype=np.float32) * np.float32(0.05)))
-    m.set_param('Wx', (rng.standard_normal((D, 3 * D)) * 0.05).astype(np.float32))
-    m.set_param('Wh', (rng.standard_normal((D, D)) * 0.05).astype(np.float32))
-    m.set_param('Wrz', (rng.standard_normal((D, 2 * D)) * 0.05).astype(np.float32))
-    m.set_param('Bh', (rng.standard_normal(3 * D) * 0.1).astype(np.float32))
-    return m, (Wy if keep_table else None)
+    kept = {'Wy': None} if keep_table else None
+    m = serving_model(I, D, rows, 'linear', rng, weights=dense_weights, keep=kept)
+    return m, (kept['Wy'] if keep_table else None)
 
 
 def timed(fn):
