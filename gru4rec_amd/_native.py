@@ -51,7 +51,7 @@ SYMBOLS = [
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
     'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
-    'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
+    'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
 ]
@@ -159,6 +159,7 @@ def lib():
     L.g4r_sync_export.argtypes, L.g4r_sync_export.restype = [vp, i32, i32p, f32p, i64], i64
     L.g4r_sync_import.argtypes = [vp, i32, i32, i64p, C.POINTER(i32p), f32pp]
     L.g4r_get_debug.argtypes = [vp, C.c_char_p, f32p, i64]
+    L.g4r_debug_loss_rows.argtypes = [vp, f32p, i64, i32, f32p]
     L.g4r_selftest_mfma.argtypes = [f32p]
     L.g4r_stress_start.argtypes = [i32, i64, i32, C.POINTER(vp)]
     L.g4r_stress_stop.argtypes = [vp]
@@ -401,6 +402,16 @@ class Model:
         a = np.empty(shape, dtype=np.float32)
         _chk(lib().g4r_get_debug(self.h, name.encode(), _f32(a), a.size))
         return a
+
+    def debug_loss_rows(self, scores, M):
+        """The loss launch of a training step on the score rows `scores` ([batch_size, ldSc], a copy is taken) with M active rows
+        (g4r_debug_loss_rows): (d cost / d s float32[batch_size, ldSc], row losses float32[batch_size], rows < M written)."""
+        ds = np.array(scores, dtype=np.float32, order='C')
+        if ds.ndim != 2:
+            raise ValueError('scores must be a [batch_size, ldSc] matrix')
+        lossrow = np.zeros(ds.shape[0], dtype=np.float32)
+        _chk(lib().g4r_debug_loss_rows(self.h, _f32(ds), ds.size, int(M), _f32(lossrow)))
+        return ds, lossrow
 
     # -- sampling
     def set_popularity(self, cum_p, lq_tgt=None, lq_smp=None):

@@ -49,7 +49,11 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
                "carries on from the wrong state wherever the selection re-parents",
            16: "the owner walk of k_sparse_update_generic drops the first hit of every pass after the first (an item with more than 64 "
                "earlier occurrences in a step loses one of them per later pass)",
-           17: "opt_rule's new second statistic (adadelta's update average, Adam's mean) x 1.01"}
+           17: "opt_rule's new second statistic (adadelta's update average, Adam's mean) x 1.01",
+           18: "k_loss_rows' grp_fast takes a group of V columns whose last column is the first inactive in-batch one (column M) as wholly "
+               "active: the unmasked copy of the element loops runs over it",
+           19: "k_loss_rows' first pass starts its loop past the prefetched groups one STEP late: the columns of the first trip keep "
+               "whatever the LDS held"}
 
 
 def mutant_path(k):

@@ -58,6 +58,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #else
 #define G4R_MUT_STAT2(x) (x)
 #endif
+#if defined(G4R_MUTATE) && G4R_MUTATE == 18      // test build: k_loss_rows' grp_fast takes a group of V columns whose LAST column is the first
+// inactive in-batch one (column M) as wholly active
+#define G4R_MUT_FAST_M(M) ((M) + 1)
+#else
+#define G4R_MUT_FAST_M(M) (M)
+#endif
+#if defined(G4R_MUTATE) && G4R_MUTATE == 19      // test build: k_loss_rows' first pass starts its loop past the prefetched groups one STEP late
+#define G4R_MUT_FIRST_LATE(step) (step)
+#else
+#define G4R_MUT_FIRST_LATE(step) 0
+#endif
 
 // Philox stream ids (counter word 3); twin of oracle/philox.py
 #define G4R_STREAM_SAMPLE 0x53414D50u

@@ -1,5 +1,5 @@
 // g4r_host_debug.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
-// instantiated there).  Holds: g4r_get_debug, the row gather / scatter micro-benchmark, the stress load of the asm-pipeline test, the MFMA self-test.
+// instantiated there).  Holds: g4r_get_debug, g4r_debug_loss_rows, the row gather / scatter micro-benchmark, the stress load of the asm-pipeline test, the MFMA self-test.
 // ------------------------------------------------------------------------------------------------ debug
 int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     if (!m || !name || !host) return fail("null argument");
@@ -128,6 +128,34 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     if (count != n) return fail(std::string("size mismatch for debug buffer ") + name + " expected " + std::to_string(n));
     HIPCHK(hipStreamSynchronize(m->stream));
     HIPCHK(hipMemcpy(host, p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- the product's loss launch on score rows the caller supplies (tests/test_gpu_loss_rows.py): `scores` (B x ldSc) goes to Sc, the device
+// step state says M for this launch only, the k_loss_rows instantiation a training step of this model launches (launch_loss_rows) runs
+// on B workgroups -- the rows alone, no owner pre-scan --, and Sc (d cost / d s) and the row losses come back.  The step state is put back
+// byte for byte; Sc and lossrow are scratch that every step rewrites before it reads them.
+int g4r_debug_loss_rows(g4r_model* m, float* scores, int64_t count, int32_t M, float* lossrow) {
+    if (!m || !scores || !lossrow) return fail("null argument");
+    DevModel& d = m->dm;
+    if (count != (int64_t)d.B * d.ldSc) return fail("size mismatch for the score rows: expected " + std::to_string((int64_t)d.B * d.ldSc));
+    if (M < 1 || M > d.B) return fail("M outside [1, batch_size]");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    StepState saved, mine;
+    HIPCHK(hipMemcpy(&saved, (const void*)d.st, sizeof(saved), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy((void*)d.Sc, scores, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
+    mine = saved;
+    mine.M_b = M;      // what load_ctx hands the kernel (t_b / g_b: not read by it)
+    HIPCHK(hipMemcpy((void*)d.st, &mine, sizeof(mine), hipMemcpyHostToDevice));
+    launch_loss_rows(m, dim3(d.B), false, nullptr, nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    const hipError_t r = hipMemcpy((void*)d.st, &saved, sizeof(saved), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(std::string("k_loss_rows: ") + hipGetErrorString(e));
+    if (r != hipSuccess) return fail(std::string("step state: ") + hipGetErrorString(r));
+    HIPCHK(hipMemcpy(scores, (const void*)d.Sc, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lossrow, (const void*)d.lossrow, (size_t)d.B * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,6 +1,31 @@
 // g4r_host_step.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
 // instantiated there).  Holds: the training step: launch_step (every launch of a step, in order), tail compaction, the captured step graphs, g4r_train_steps (+ virtual ranks), losses, counters, per-kernel profiling.
 // ------------------------------------------------------------------------------------------------ the step
+// The k_loss_rows instantiation of this model (m->kern: loss_long, loss_spec, loss_quads) on `grid` workgroups of the model's stream -- the one
+// place that chooses it, for launch_step and for g4r_debug_loss_rows (g4r_host_debug.hpp).  timed: per-kernel profiling, the start / stop
+// events ev_a / ev_b attached to the dispatch itself.
+static void launch_loss_rows(g4r_model* m, dim3 grid, bool timed, hipEvent_t ev_a, hipEvent_t ev_b) {
+    const StepKernels& k = m->kern;
+    const DevModel* dmp = (const DevModel*)m->d_dm;
+    StepState* stp = (StepState*)m->dm.st;
+#define G4R_LK_LOSS1(kern)                                                                                            \
+    do {                                                                                                              \
+        if (timed) hipExtLaunchKernelGGL(kern, grid, dim3(LOSS_T), m->smem_loss, m->stream, ev_a, ev_b, 0, dmp, stp); \
+        else hipLaunchKernelGGL(kern, grid, dim3(LOSS_T), m->smem_loss, m->stream, dmp, stp);                         \
+    } while (0)
+#define G4R_LK_LOSS(L, V)                                                      \
+    do {                                                                       \
+        if (k.loss_spec == 1) G4R_LK_LOSS1((k_loss_rows<L, 1, V>));            \
+        else if (k.loss_spec == 2) G4R_LK_LOSS1((k_loss_rows<L, 2, V>));       \
+        else if (k.loss_spec == 3) G4R_LK_LOSS1((k_loss_rows<L, 3, V>));       \
+        else G4R_LK_LOSS1((k_loss_rows<L, 0, V>));                             \
+    } while (0)
+    if (k.loss_long) G4R_LK_LOSS(true, 4);      // (rows that long always take four columns per thread)
+    else { if (k.loss_quads) G4R_LK_LOSS(false, 4); else G4R_LK_LOSS(false, 1); }
+#undef G4R_LK_LOSS
+#undef G4R_LK_LOSS1
+}
+
 // Every launch of a training step, in order, as m->kern chose them (choose_kernels).
 // part: 0 = the whole step; 1 = head (everything up to the dense gradients); 2 = tail (all-reduce, dense apply, sparse update)
 static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
@@ -120,16 +145,7 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
         // a step that ends in k_update_l: up to one more workgroup per idle CU, the owner pre-scan of its repeated items (g4r_loss_kernel.cuh)
         const int nown = std::min(cdiv(d.R, LOSS_NW), std::max(2 * m->n_cu - B, 32));
         const dim3 gloss(B + (merged && k.update == UP_LEAN && d.own_pos ? nown : 0));
-#define G4R_LK_LOSS(L, V)                                                                                                      \
-        do {                                                                                                                   \
-            if (k.loss_spec == 1) LK((k_loss_rows<L, 1, V>), gloss, dim3(LOSS_T), m->smem_loss, s, dmp, stp);        \
-            else if (k.loss_spec == 2) LK((k_loss_rows<L, 2, V>), gloss, dim3(LOSS_T), m->smem_loss, s, dmp, stp);   \
-            else if (k.loss_spec == 3) LK((k_loss_rows<L, 3, V>), gloss, dim3(LOSS_T), m->smem_loss, s, dmp, stp);   \
-            else LK((k_loss_rows<L, 0, V>), gloss, dim3(LOSS_T), m->smem_loss, s, dmp, stp);                         \
-        } while (0)
-        if (k.loss_long) G4R_LK_LOSS(true, 4);      // (rows that long always take four columns per thread)
-        else { if (k.loss_quads) G4R_LK_LOSS(false, 4); else G4R_LK_LOSS(false, 1); }
-#undef G4R_LK_LOSS
+        if (!(m->sw.skip_kn && ((m->sw.skip_kn >> KN_LOSS) & 1ull))) launch_loss_rows(m, gloss, recs != nullptr, cur_a, cur_b);
     }
     end();
     begin(KN_SCORE_BWD);

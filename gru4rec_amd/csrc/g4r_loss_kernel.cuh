@@ -160,7 +160,7 @@ __global__ __launch_bounds__(LOSS_T) void k_loss_rows(const DevModel* __restrict
     const float n_out = (float)(M + (N - B));      // active columns (gru4rec.py:227,233,244: M + n_sample)
     // Column j is active iff j < M (in-batch targets) or B <= j < N (sampled negatives)
     auto active = [&](int j) { return j < N && (j < M || j >= B); };
-    auto grp_fast = [&](int j0) { return (j0 >= B && j0 + V <= N) || (j0 + V <= M && (i < j0 || i >= j0 + V)); };
+    auto grp_fast = [&](int j0) { return (j0 >= B && j0 + V <= N) || (j0 + V <= G4R_MUT_FAST_M(M) && (i < j0 || i >= j0 + V)); };
     using Fast = std::true_type;
     using Slow = std::false_type;
 #define G4R_GROUPS(lim, fn) for (int j0 = jt; j0 < (lim); j0 += STEP) { if (grp_fast(j0)) fn(Fast{}, j0); else fn(Slow{}, j0); }
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(LOSS_T) void k_loss_rows(const DevModel* __restrict
             const int j0 = jt + q * STEP;
             if (j0 < N) { if (grp_fast(j0)) first(Fast{}, j0, pre_s[q]); else first(Slow{}, j0, pre_s[q]); }
         }
-        for (int j0 = jt + LOSS_PRE * STEP; j0 < N; j0 += STEP) {
+        for (int j0 = jt + LOSS_PRE * STEP + G4R_MUT_FIRST_LATE(STEP); j0 < N; j0 += STEP) {
             float v[V];
             vld<V>(v, row + j0);
             if (grp_fast(j0)) first(Fast{}, j0, v); else first(Slow{}, j0, v);
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(LOSS_T) void k_loss_rows(const DevModel* __restrict
             const int j0 = jt + q * STEP;
             if (j0 < N) { if (grp_fast(j0)) first(Fast{}, j0, pre_s[q]); else first(Slow{}, j0, pre_s[q]); }
         }
-        for (int j0 = jt + LOSS_PRE * STEP; j0 < N; j0 += STEP) {
+        for (int j0 = jt + LOSS_PRE * STEP + G4R_MUT_FIRST_LATE(STEP); j0 < N; j0 += STEP) {
             float v[V];
             vld<V>(v, row + j0);
             if (grp_fast(j0)) first(Fast{}, j0, v); else first(Slow{}, j0, v);

@@ -458,6 +458,12 @@ int g4r_p2p_active(g4r_model* m);                              /* 1 when the ste
 /* ---- debugging / tests ---------------------------------------------------------------------- */
 /* copy a named intermediate of the most recent step (e.g. "scores", "dS", "dV0", "hd0") */
 int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count);
+/* Test support (tests/test_gpu_loss_rows.py): the loss launch of a training step on score rows the caller supplies.  scores: B x ldSc
+ * floats (g4r_get_debug "ldSc"), in: the scores, out: d cost / d s as the step leaves it in "scores"; M: the active rows of the step
+ * (1 .. batch_size); lossrow: batch_size floats out, rows < M written.  Runs the k_loss_rows instantiation the model's steps run, on
+ * batch_size workgroups, and waits for it.  The step state on the device is the same before and after; the "scores" and "lossrow"
+ * buffers are overwritten (every step rewrites them before it reads them).  count must be batch_size * ldSc. */
+int g4r_debug_loss_rows(g4r_model* m, float* scores, int64_t count, int32_t M, float* lossrow);
 int g4r_selftest_mfma(float* max_abs_err);
 /* Row gather / scatter micro-benchmark on a table of n_items x W floats (fresh allocation, random rows, every launch its own
  * rows): mode 0 gather to a compact buffer, 1 gather consumed in registers (what the step's fused gathers do), 2 Adagrad scatter

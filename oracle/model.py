@@ -113,8 +113,9 @@ def softplus(x):
     return np.maximum(x, 0) + np.log1p(np.exp(-np.abs(x)))
 
 
-def loss_fwd_bwd(loss, yhat, M, diag_cols, colmask, bpreg, smoothing=0.0):
+def loss_fwd_bwd(loss, yhat, M, diag_cols, colmask, bpreg, smoothing=0.0, per_row=False):
     """Return (sum of per-row losses, d/d yhat).  Rows 0..M-1; row i's positive is column diag_cols[i].
+    per_row: the vector of the M row losses in place of their sum (top1: with the factor M, so that it sums to the cost).
 
     softmax_neg restates gru4rec.py:199-203: the positive is masked out *after* being zeroed, the row
     max therefore includes the zeroed entry.  bpr_max :239-241, top1_max :245-248, cross_entropy :225-230.
@@ -138,13 +139,13 @@ def loss_fwd_bwd(loss, yhat, M, diag_cols, colmask, bpreg, smoothing=0.0):
         L = wd * l_all[rows, diag_cols] + wa * (l_all * cm).sum(axis=1)
         d = wa * dl_all * cm
         d[rows, diag_cols] += wd * dl_all[rows, diag_cols]
-        return L.sum(dtype=yhat.dtype), d.astype(yhat.dtype)
+        return (L.astype(yhat.dtype) if per_row else L.sum(dtype=yhat.dtype)), d.astype(yhat.dtype)
     if loss == 'bpr':
         # bpr :237-238: -log sigmoid(yd - y_j) summed over ALL columns (the diagonal contributes log 2, no gradient)
         L = (softplus(yhat - ydiag) * cm).sum(axis=1)
         d = sigmoid(yhat - ydiag) * hm
         d[rows, diag_cols] = -d.sum(axis=1)
-        return L.sum(dtype=yhat.dtype), d.astype(yhat.dtype)
+        return (L.astype(yhat.dtype) if per_row else L.sum(dtype=yhat.dtype)), d.astype(yhat.dtype)
     if loss == 'top1':
         # top1 :242-244: mean_j(sigmoid(y_j - yd) + sigmoid(y_j^2)) - sigmoid(yd^2) / n.  As written in the reference the
         # mean is a vector (M,) and the subtracted term a column (M, 1) (gpu_diag(..., keepdims=True)), so the
@@ -154,7 +155,7 @@ def loss_fwd_bwd(loss, yhat, M, diag_cols, colmask, bpreg, smoothing=0.0):
         L = (((u + q) * hm).sum(axis=1) + dt(0.5)) / n_out
         d = (u * (dt(1) - u) + dt(2) * yhat * q * (dt(1) - q)) * hm / n_out
         d[rows, diag_cols] = -((u * (dt(1) - u)) * hm).sum(axis=1) / n_out
-        return dt(M) * L.sum(dtype=yhat.dtype), (dt(M) * d).astype(yhat.dtype)
+        return ((dt(M) * L).astype(yhat.dtype) if per_row else dt(M) * L.sum(dtype=yhat.dtype)), (dt(M) * d).astype(yhat.dtype)
     if loss in ('bpr-max', 'top1-max'):
         X = yhat * hm
         Xm = np.where(colmask[None, :], X, -np.inf)
@@ -170,7 +171,7 @@ def loss_fwd_bwd(loss, yhat, M, diag_cols, colmask, bpreg, smoothing=0.0):
             d = -p * (sg - sgp - A) / (A + dt(EPS_LOSS)) + dt(bpreg) * p * (dt(2) * yhat + yhat * yhat - Q)
             d = d * hm
             d[rows, diag_cols] = -((sgp * p).sum(axis=1)) / (A[:, 0] + dt(EPS_LOSS))
-            return L.sum(dtype=yhat.dtype), d.astype(yhat.dtype)
+            return (L.astype(yhat.dtype) if per_row else L.sum(dtype=yhat.dtype)), d.astype(yhat.dtype)
         else:
             u = sigmoid(yhat - ydiag)
             q = sigmoid(yhat * yhat)
@@ -180,7 +181,7 @@ def loss_fwd_bwd(loss, yhat, M, diag_cols, colmask, bpreg, smoothing=0.0):
             d = p * (t - T) + p * (u * (dt(1) - u) + dt(2) * yhat * q * (dt(1) - q))
             d = d * hm
             d[rows, diag_cols] = -((p * u * (dt(1) - u)).sum(axis=1))
-            return L.sum(dtype=yhat.dtype), d.astype(yhat.dtype)
+            return (L.astype(yhat.dtype) if per_row else L.sum(dtype=yhat.dtype)), d.astype(yhat.dtype)
     raise NotImplementedError(loss)
 
 

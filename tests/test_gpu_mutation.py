@@ -13,6 +13,10 @@ mutant; every one of those runs has to come back red, and the tensor it names ha
   mutant 16 k_sparse_update_generic's owner walk drops the first hit of every pass after the first -> dWy of the hot rows of
             test_gpu_generic_edges.py::test_hot_items (an item with > 64 earlier occurrences loses one per later pass)
   mutant 17 opt_rule's new second statistic x 1.01 -> acc2_* of an adadelta and of an adam case; rmsprop (no such statistic) passes
+  mutant 18 k_loss_rows' grp_fast takes the quad whose last column is the first inactive one as wholly active -> ds of the M = 35 run
+            of a four-column case of test_gpu_loss_rows.py; the M = 36 run of the same case passes
+  mutant 19 k_loss_rows' first pass starts its loop past the prefetched groups one STEP late -> ds at N = 12301; N = 4099 (no such
+            trip) passes
 
 (Round 2's `atol = 1e-4` on every tensor let an accumulator that is wrong by 100 x pass.)  The same selection runs green on the
 product library in the ordinary suite."""
@@ -123,6 +127,25 @@ def test_mutant_17_turns_the_second_statistic_red(mutants, tmp_path):
         assert state[tag + ' acc2_Wy'] and state[tag + ' acc2_By'] and state[tag + ' acc2_Wh0'], state
     r, state = _child(mutants[17], 'tests/test_gpu_generic_edges.py::test_row_width[260-rmsprop]', str(tmp_path / 'rms.txt'))
     assert r.returncode == 0, 'mutant 17 on rmsprop: rc %d\n%s' % (r.returncode, (r.stdout + r.stderr)[-3000:])
+
+
+def test_mutant_18_turns_the_quad_that_ends_on_column_M_red(mutants, tmp_path):
+    """k_loss_rows takes a quad whose last column is the first inactive in-batch column as wholly active: at B = 37 the run with
+    M = 35 (quad [32, 36)) must fail on ds; the runs with M = 36 and M = 34 of the same case, where no quad ends on column M, pass."""
+    r, state = _child(mutants[18], 'tests/test_gpu_loss_rows.py::test_loss_rows[elubm-q4099]', str(tmp_path / 'm18.txt'))
+    assert r.returncode == 1, 'mutant 18 passed the four-column case:\n%s' % (r.stdout + r.stderr)[-3000:]
+    assert state['elubm q4099 M=35 ds'], state
+    assert not state['elubm q4099 M=36 ds'] and not state['elubm q4099 M=34 ds'] and not state['elubm q4099 M=36 loss'], state
+
+
+def test_mutant_19_turns_the_first_trip_past_the_prefetch_red(mutants, tmp_path):
+    """k_loss_rows' first pass skips the first loop trip past the prefetched groups: N = 12301 (columns 8192 .. 12287 of every row)
+    must fail on ds; N = 4099, where the prefetched groups hold the whole row, passes."""
+    r, state = _child(mutants[19], 'tests/test_gpu_loss_rows.py::test_loss_rows[elubm-q12301]', str(tmp_path / 'm19a.txt'))
+    assert r.returncode == 1, 'mutant 19 passed N = 12301:\n%s' % (r.stdout + r.stderr)[-3000:]
+    assert state['elubm q12301 M=37 ds'], state
+    r, state = _child(mutants[19], 'tests/test_gpu_loss_rows.py::test_loss_rows[elubm-q4099]', str(tmp_path / 'm19b.txt'))
+    assert r.returncode == 0, 'mutant 19 on N = 4099: rc %d\n%s' % (r.returncode, (r.stdout + r.stderr)[-3000:])
 
 
 def test_product_library_is_not_a_mutant():

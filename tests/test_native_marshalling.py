@@ -48,6 +48,7 @@ SPECS = {
                                      'ns', 'sess*T*B', 'pos*T*B', 'out_items>n_slots*k', 'out_scores>n_slots*k', 'rank>n_slots',
                                      'target_score>n_slots'),
     'g4r_p2p_attach': ('h', 'blob', 'nranks', 'rank'),
+    'g4r_debug_loss_rows': ('h', 'scores>count', 'count', 'M', 'lossrow>B'),
 }
 
 
@@ -628,6 +629,22 @@ def test_p2p_attach(m, fake):
     assert not fake.calls
 
 
+def test_debug_loss_rows(m, fake):
+    fake.env = dict(B=3)
+    scores = np.arange(12, dtype=np.float64).reshape(3, 4) + 0.5
+    ds, lossrow = m.debug_loss_rows(scores, 2)
+    name, c = fake.only()
+    assert name == 'g4r_debug_loss_rows' and c['h'] == HANDLE and (c['count'], c['M']) == (12, 2)
+    same(c['scores'], scores.ravel(), np.float32)                           # in: the caller's values, converted
+    same(c['lossrow'], [0, 0, 0], np.float32)
+    filled(ds, (3, 4), np.float32)                                          # out: the same buffer, a copy of the caller's array
+    filled(lossrow, (3,), np.float32)
+    assert scores[0, 0] == 0.5
+    with raises('scores must be a [batch_size, ldSc] matrix'):
+        m.debug_loss_rows(np.zeros(12), 2)
+    assert not fake.calls
+
+
 def test_a_failed_call_raises_the_library_error(m, fake):
     fake.rc, fake.error = 3, 'k is too large (the fake said so)'.encode()
     fake.env = dict(nh=6, nx=0, ncand=3, B=B_)
@@ -637,7 +654,8 @@ def test_a_failed_call_raises_the_library_error(m, fake):
              lambda: m.similar_items([3]), lambda: m.score_candidates([3], [0, 3], [1, 2, 3]),
              lambda: m.score_candidates_sessions(cand_offs=[0, 1, 2, 3], cand_items=[1, 2, 3], **HIST), lambda: m.set_plan(plan(0)),
              lambda: m.evaluate(plan(0), B_, None, [20], 'standard'),
-             lambda: m.recommend_events(plan(0), B_, None, 'standard', np.zeros((T_, B_)), 5, 2), lambda: m.p2p_attach([b'a' * 64], 1, 0)]
+             lambda: m.recommend_events(plan(0), B_, None, 'standard', np.zeros((T_, B_)), 5, 2), lambda: m.p2p_attach([b'a' * 64], 1, 0),
+             lambda: m.debug_loss_rows(np.zeros((B_, 4)), 1)]
     for f in calls:
         with pytest.raises(NativeError, match=re.escape('k is too large (the fake said so)')):
             f()
