@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get('G4R_LIB') or os.path.join(_HERE, 'libgru4rec_hip.so')
 G4R_MAX_LAYERS = 8
 G4R_TOPK_MAX = 256      # largest k of g4r_recommend_step
 G4R_BEAM_MAX = 32       # widest beam of g4r_beam_sessions
+G4R_SAMPLE_MAX = 64     # most draws per session of g4r_sample_sessions
+G4R_STREAM_GUMBEL = 0x47554D42      # Philox stream id (counter word 3) of its noise
 BEAM_COMBINE = {'sum': 0, 'product': 1}      # G4R_BEAM_*
 G4R_EXCLUDE_MAX = 1024  # most distinct items one row of g4r_recommend_step_filtered may exclude
 G4R_CAND_MAX = 2 ** 31 - 256  # most candidate positions of one g4r_score_candidates* call
@@ -50,8 +52,8 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
-    'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
+    'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_debug_gumbel', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
 ]
@@ -132,6 +134,8 @@ def lib():
     L.g4r_continue_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i32, i64p, i32p, u32p, i32p, f32p, f32pp]
     L.g4r_beam_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i32, i32, i64p, i32p, u32p, i32p, i32p,
                                     f32p, f32p, i32p]
+    L.g4r_sample_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i64p, i32p, u32p, i32, i32, C.c_float, C.c_uint64, i32,
+                                      i32p, f32p, f32pp]
     L.g4r_scan_table_release.argtypes = [vp]
     L.g4r_similar_items.argtypes = [vp, i32, i32, i32p, i64, i32p, i64, i32, i32, u32p, i32p, f32p]
     L.g4r_score_candidates.argtypes = [vp, i32p, i32, i64p, i32p, i32, f32p, i32p]
@@ -160,6 +164,7 @@ def lib():
     L.g4r_sync_import.argtypes = [vp, i32, i32, i64p, C.POINTER(i32p), f32pp]
     L.g4r_get_debug.argtypes = [vp, C.c_char_p, f32p, i64]
     L.g4r_debug_loss_rows.argtypes = [vp, f32p, i64, i32, f32p]
+    L.g4r_debug_gumbel.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, i32p, i64, f32p]
     L.g4r_selftest_mfma.argtypes = [f32p]
     L.g4r_stress_start.argtypes = [i32, i64, i32, C.POINTER(vp)]
     L.g4r_stress_stop.argtypes = [vp]
@@ -580,6 +585,37 @@ class Model:
                                      steps, 1 if no_repeat else 0, BEAM_COMBINE[combine], _i64(xo), _i32(xi), _u32(mask), _i32(parent),
                                      _i32(cols), _f32(step_scores), _f32(path_scores), _i32(scale_exp)))
         return parent, cols, step_scores, path_scores, scale_exp
+
+    def sample_sessions(self, hist_offs, hist_items, item_idx=None, steps=1, samples=1, top_k=None, temperature=1.0, seed=0, first_step=0,
+                        no_repeat=True, excl_offs=None, excl_items=None, excl_mask=None, hidden=None, return_hidden=False):
+        """`samples` independent draws per session of `steps` items each from softmax(logit / temperature) over the eligible
+        candidates (top_k: cut to the top_k best first), every drawn item fed back on the device (g4r_sample_sessions).  Arguments as
+        in continue_sessions; draw (i, j) uses the noise of row id i * samples + j at steps first_step, first_step + 1, ...  Returns
+        (cols int32[n, samples, steps], scores float32[n, samples, steps] -- the chosen positions' logits), + the hidden states that
+        produced the last step's scores (float32[n * samples, layers[l]] each) with return_hidden=True."""
+        offs, hi, n = _hist(hist_offs, hist_items)
+        steps, samples = int(steps), int(samples)
+        if steps < 1:
+            raise ValueError('steps must be at least 1')
+        if not 1 <= samples <= G4R_SAMPLE_MAX:
+            raise ValueError('samples must be in [1, %d]' % G4R_SAMPLE_MAX)
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        xo, xi, mask = _excl(n, excl_offs, excl_items, excl_mask, self.cfg.n_items, 'n')
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        hout, houtp = _hidden_out(n * samples, self.layers, return_hidden)
+        cols, scores = _topk_out((n, samples, steps))
+        _chk(lib().g4r_sample_sessions(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, steps, 1 if no_repeat else 0, _i64(xo), _i32(xi),
+                                       _u32(mask), samples, 0 if top_k is None else int(top_k), float(temperature), int(seed), int(first_step),
+                                       _i32(cols), _f32(scores), houtp))
+        return (cols, scores, hout) if return_hidden else (cols, scores)
+
+    def debug_gumbel(self, seed, row_id, step, items):
+        """The noise of sample_sessions for (seed, row id, step) and every item index of `items`, from the device function the
+        selection calls (g4r_debug_gumbel): float32[len(items)]."""
+        it = np.ascontiguousarray(items, dtype=np.int32)
+        out = np.empty(len(it), dtype=np.float32)
+        _chk(lib().g4r_debug_gumbel(self.h, int(seed), int(row_id), int(step), _i32(it), len(it), _f32(out)))
+        return out
 
     def similar_items(self, q_idx, item_idx=None, k=20, metric='cosine', space='output', exclude_self=True, excl_mask=None):
         """The k candidates most similar to every query item in the model's own embedding space (g4r_similar_items; stateless):

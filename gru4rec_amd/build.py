@@ -53,7 +53,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            18: "k_loss_rows' grp_fast takes a group of V columns whose last column is the first inactive in-batch one (column M) as wholly "
                "active: the unmasked copy of the element loops runs over it",
            19: "k_loss_rows' first pass starts its loop past the prefetched groups one STEP late: the columns of the first trip keep "
-               "whatever the LDS held"}
+               "whatever the LDS held",
+           20: "gumbel_noise (g4r_sample_sessions) ignores the decoding step (Philox counter word 2 = 0): every step of a draw gets the "
+               "noise of step 0"}
 
 
 def mutant_path(k):

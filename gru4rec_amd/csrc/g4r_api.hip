@@ -18,6 +18,7 @@
 #include "g4r_rollout_kernels.cuh"
 #include "g4r_beam_kernels.cuh"
 #include "g4r_cand_kernels.cuh"
+#include "g4r_sample_kernels.cuh"
 #include "g4r_scan_kernels.cuh"
 #include "g4r_sim_kernels.cuh"
 #include "g4r_sync_kernels.cuh"
@@ -37,6 +38,7 @@ extern "C" {
 #include "g4r_host_predict.hpp"
 #include "g4r_host_sessions.hpp"
 #include "g4r_host_beam.hpp"
+#include "g4r_host_sample.hpp"
 #include "g4r_host_events.hpp"
 #include "g4r_host_similar.hpp"
 #include "g4r_host_comm.hpp"

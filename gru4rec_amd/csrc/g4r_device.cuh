@@ -75,6 +75,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define G4R_STREAM_DROP_EMBED 0x44454D42u
 #define G4R_STREAM_DROP_HIDDEN 0x44484944u
 #define G4R_STREAM_TIEBREAK 0x54494542u
+// (G4R_STREAM_GUMBEL, the stream of g4r_sample_sessions' noise, is part of the ABI: include/gru4rec_hip.h)
 
 // ---------------------------------------------------------------------------------------------
 // Pointers that the kernels read out of device-resident descriptors (DevModel, DenseTile) would be generic
@@ -354,6 +355,20 @@ __device__ __forceinline__ float tie_noise(unsigned long long seed, unsigned ctr
     const int e = (int)(col & 3);
     const unsigned x = e == 0 ? p.x : (e == 1 ? p.y : (e == 2 ? p.z : p.w));
     return u32_to_unit(x) * 1e-10f;
+}
+// Gumbel noise of g4r_sample_sessions for (row id q, decoding step, item index): lane item & 3 of the Philox call (item >> 2, q, step,
+// G4R_STREAM_GUMBEL) keyed by the caller's seed; u = (x >> 9) 2^-23 + 2^-24 (exact in fp32, in [2^-24, 1 - 2^-24]); g = -log(-log u) with
+// the precise logf, finite, in about [-2.82, 16.64].  The one definition behind the selection (k_topk_range<.., TkSample>, k_sample_pick)
+// and k_debug_gumbel; tests/sampling_ref.py holds its float64 twin
+__device__ __forceinline__ float gumbel_noise(unsigned long long seed, unsigned q, unsigned step, int item) {
+#if defined(G4R_MUTATE) && G4R_MUTATE == 20      // test build: the noise ignores the step
+    step = 0u;
+#endif
+    const Philox4 p = philox4x32_10((unsigned)item >> 2, q, step, G4R_STREAM_GUMBEL, (unsigned)seed, (unsigned)(seed >> 32));
+    const int e = item & 3;
+    const unsigned x = e == 0 ? p.x : (e == 1 ? p.y : (e == 2 ? p.z : p.w));
+    const float u = __fadd_rn(__fmul_rn((float)(x >> 9), 0x1p-23f), 0x1p-24f);
+    return -logf(-logf(u));
 }
 __device__ __forceinline__ float4 drop_mult4(unsigned long long seed, unsigned g, unsigned stream, int row, int col4,
                                              float retain) {

@@ -1,5 +1,5 @@
 // g4r_host_debug.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
-// instantiated there).  Holds: g4r_get_debug, g4r_debug_loss_rows, the row gather / scatter micro-benchmark, the stress load of the asm-pipeline test, the MFMA self-test.
+// instantiated there).  Holds: g4r_get_debug, g4r_debug_loss_rows, g4r_debug_gumbel, the row gather / scatter micro-benchmark, the stress load of the asm-pipeline test, the MFMA self-test.
 // ------------------------------------------------------------------------------------------------ debug
 int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     if (!m || !name || !host) return fail("null argument");
@@ -156,6 +156,27 @@ int g4r_debug_loss_rows(g4r_model* m, float* scores, int64_t count, int32_t M, f
     if (r != hipSuccess) return fail(std::string("step state: ") + hipGetErrorString(r));
     HIPCHK(hipMemcpy(scores, (const void*)d.Sc, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(lossrow, (const void*)d.lossrow, (size_t)d.B * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- the noise of g4r_sample_sessions (tests/test_gpu_sample_sessions.py): out[p] = gumbel_noise(seed, row_id, step, items[p]) through the
+// __device__ function the selection calls.  items: n non-negative item indices (the model's catalogue does not bound them)
+int g4r_debug_gumbel(g4r_model* m, uint64_t seed, uint32_t row_id, uint32_t step, const int32_t* items, int64_t n, float* out) {
+    if (!m || !items || !out) return fail("null argument");
+    if (n < 1) return fail("n must be positive");
+    for (int64_t p = 0; p < n; ++p)
+        if (items[p] < 0) return fail("item index out of range");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    CallTemps tmp(m);
+    int* d_it = nullptr;
+    float* d_out = nullptr;
+    if (tmp.get(&d_it, (size_t)n, false) || tmp.get(&d_out, (size_t)n, false)) return -1;
+    HIPCHK(hipMemcpyAsync(d_it, items, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(k_debug_gumbel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, (unsigned long long)seed, (unsigned)row_id,
+                       (unsigned)step, (const int*)d_it, (long long)n, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
     return 0;
 }
 

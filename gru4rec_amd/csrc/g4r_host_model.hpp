@@ -176,6 +176,11 @@ struct g4r_model {
     // downloads, as 4-byte words: [steps][rows] parent | column | step score, [rows] path score, [sessions] scale_exp
     DevBuf<int> bm_in, bm_sel, bm_xlen, bm_xitems, bm_out;
     DevBuf<long long> bm_beg;
+    // sampling (g4r_sample_sessions; rows = a chunk's draw rows): the rows' ids, their chosen (column | item) of the step and its score;
+    // outputs, feedback and lists live in the continuation's arrays (ro_*, p_xoffs / p_xitems / p_xmask)
+    DevBuf<unsigned> sm_rowid;
+    DevBuf<int> sm_pick;
+    DevBuf<float> sm_z;
     // per-row candidate scoring (g4r_score_candidates*): one call's (or chunk's) CSR -- row offsets, candidate item indices, scores
     // in CSR order -- the work items of k_score_cand, the top-k lists of k_cand_pack and the selected (position, score) pairs
     DevBuf<long long> c_offs;
@@ -296,6 +301,7 @@ static constexpr auto k_topk_fused_x = k_topk_range<false, true, TkExcl>;       
 static constexpr auto k_topk_stored_x = k_topk_range<true, true, TkExcl>;
 static constexpr auto k_topk_fused_g = k_topk_range<false, true, TkGrow>;        // the same two with lists that grow on the device (g4r_continue_sessions)
 static constexpr auto k_topk_stored_g = k_topk_range<true, true, TkGrow>;
+static constexpr auto k_topk_sample = k_topk_range<false, true, TkSample>;      // selection on the Gumbel-perturbed key (g4r_sample_sessions)
 static constexpr auto k_topk_rank = k_topk_range<false, false, TkEvents>;        // g4r_recommend_events: k_topk_fused + the rank counters of k_score_count
 static constexpr auto k_topk_rank_x = k_topk_range<false, true, TkEvents>;       // + the session-list / mask exclusions
 static constexpr auto k_topk_stored_ev = k_topk_range<true, true, TkEvents>;     // softmax / softmax_logit with those exclusions (no counters)

@@ -1,0 +1,80 @@
+// Sampling kernels (gfx950), behind g4r_sample_sessions (not in the reference): stochastic decoding of session continuations from the
+// model's own next-item distribution by the Gumbel-max trick -- the argmax of key = fl32(fl32(z * invT) + g) over the eligible
+// candidate positions is a draw from softmax(z / T) over them, so a draw is a SELECTION and nothing materialises a score row, a softmax
+// or a prefix sum.  Session row r of a chunk owns the draw rows r S + j, j < S = samples.
+//   k_topk_sample    k_topk_range<false, true, TkSample> (g4r_topk_kernels.cuh): the fused score-and-select kernel selecting on the key
+//   k_sample_expand  after the replay: session row r's state (every layer) and top-layer output become those of its S draw rows
+//   k_sample_pick    one wave per draw row, behind k_topk_merge.  top_k = t: the argmax of the key over the row's t best (column, z);
+//                    untruncated: the merge's one (column, key) entry.  Leaves the row's chosen column and item
+//   k_debug_gumbel   gumbel_noise for a list of items (tests compare it with a float64 twin)
+// The per-step tail is k_rollout_feed with k = 1 (g4r_rollout_kernels.cuh) on (chosen column, its z): z is the merge's own in the top_k
+// path and is recomputed for the one chosen column per row by k_score_cand in the untruncated one (g4r_predict_step's bit pattern).
+#pragma once
+#include "g4r_beam_kernels.cuh"
+#include "g4r_cand_kernels.cuh"
+
+// LDS of the sampling form of the range kernel: the EXCL fused kernel's (the row ids live in registers, 8 per lane)
+#define TK_SMEM_SAMPLE TK_SMEM_FUSED_X
+static_assert(TK_SMEM_SAMPLE <= TK_SMEM_FUSED_X + SC_BM * 4 && TK_SMEM_SAMPLE <= 156 * 1024,
+              "the sampling form of the range kernel may add at most a row-id column to the EXCL fused kernel's LDS");
+
+template __global__ void k_topk_range<false, true, TkSample>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkSample);
+
+// One wave per draw row q = r S + j (grid = rows S, 64 threads): every layer's state of session row r -- in st.src (even history length)
+// or st.src1 (odd) -- is copied to row q of st.dst, the row's top-layer output hsrc[r] to hdst[q] (Dtop floats each)
+__global__ __launch_bounds__(64) void k_sample_expand(BeamState st, const int* len, int S, const float* hsrc, float* hdst, int Dtop) {
+    const int q = blockIdx.x, lane = threadIdx.x, r = q / S;
+    const int odd = len[r] & 1;
+    for (int l = 0; l < st.n_layers; ++l) {
+        const int D = st.W[l];
+        const float* s = (odd ? st.src1[l] : st.src[l]) + (size_t)r * D;
+        float* d = st.dst[l] + (size_t)q * D;
+        for (int j = lane; j < D; j += 64) d[j] = s[j];
+    }
+    for (int j = lane; j < Dtop; j += 64) hdst[(size_t)q * Dtop + j] = hsrc[(size_t)r * Dtop + j];
+}
+
+// One wave per draw row (grid = rows, 64 threads).  tcols / tvals: the merge's [rows][t] result.  keyed != 0 (top_k = t): tvals are
+// the scores z of the row's t best eligible columns; the row's choice is the entry with the largest topk_key(key, column) -- equal
+// keys to the lower column, NaN last --, key = fl32(fl32(z * invT) + gumbel_noise(seed, row_id[row], step, item)); pick_z[row] <- its z.
+// keyed == 0 (t = 1): the entry is the choice already (the range kernel selected on the key); pick_z is left to k_score_cand.
+// pick_col / pick_item[row] <- the chosen column and its item index (item_idx[column], or the column)
+__global__ __launch_bounds__(64) void k_sample_pick(const int* tcols, const float* tvals, int t, int keyed, const int* item_idx,
+                                                    const unsigned* row_id, unsigned long long seed, unsigned step, float invT,
+                                                    int* pick_col, int* pick_item, float* pick_z) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const size_t o = (size_t)row * t;
+    int bj = 0;
+    if (keyed) {
+        const unsigned q = row_id[row];
+        unsigned long long best = 0ull;
+        for (int j = lane; j < t; j += 64) {
+            const int col = tcols[o + j];
+            if (col < 0) continue;      // (a pad: never there, every row keeps t eligible positions)
+            const int item = item_idx ? item_idx[col] : col;
+            const float key = __fadd_rn(__fmul_rn(tvals[o + j], invT), gumbel_noise(seed, q, step, item));
+            const unsigned long long kk = topk_key(key, (unsigned)col);
+            if (kk > best) { best = kk; bj = j; }
+        }
+#pragma unroll
+        for (int w = 32; w > 0; w >>= 1) {
+            const unsigned lo = __shfl_xor((unsigned)best, w), hi = __shfl_xor((unsigned)(best >> 32), w);
+            const int oj = __shfl_xor(bj, w);
+            const unsigned long long ob = ((unsigned long long)hi << 32) | lo;
+            if (ob > best) { best = ob; bj = oj; }      // (keys of distinct columns are distinct: every lane ends with the same pair)
+        }
+    }
+    if (lane == 0) {
+        const int col = tcols[o + bj];
+        pick_col[row] = col;
+        pick_item[row] = item_idx ? item_idx[col] : col;
+        if (keyed) pick_z[row] = tvals[o + bj];
+    }
+}
+
+// out[p] = gumbel_noise(seed, q, step, items[p]): the function the selection calls
+__global__ __launch_bounds__(256) void k_debug_gumbel(unsigned long long seed, unsigned q, unsigned step, const int* items, long long n,
+                                                      float* out) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p < n) out[p] = gumbel_noise(seed, q, step, items[p]);
+}

@@ -96,6 +96,29 @@ __device__ __forceinline__ TkGrow tk_grow(TkExcl) { return TkGrow{}; }
 __device__ __forceinline__ TkGrow tk_grow(TkEvents) { return TkGrow{}; }
 __device__ __forceinline__ TkGrow tk_grow(TkGrow g) { return g; }
 
+// The trailing argument of the g4r_sample_sessions instantiation (k_topk_range<false, true, TkSample>): TkGrow's fields, plus what turns
+// the selection into a draw.  Row r of the launch is the draw with row id row_id[r]; the value pushed to a row's queue, compared with
+// its threshold and kept in the lists is key = fl32(fl32(z * invT) + gumbel_noise(seed, row id, step, item)) in place of the score z:
+// the argmax of the keys over the eligible columns is a draw from softmax(z / T) over them (Gumbel-max), and the threshold, queue
+// and merge logic are the selection's own.  Again a type of its own: the other instantiations keep their arguments and their code.
+struct TkSample {
+    const long long* beg; const int* len; const int* items; const unsigned* mask;
+    const unsigned* row_id; unsigned long long seed; unsigned step; float invT;
+};
+__device__ __forceinline__ TkExcl tk_excl(TkSample s) { return TkExcl{nullptr, s.items, s.mask}; }
+__device__ __forceinline__ TkEvents tk_events(TkSample) { return TkEvents{}; }
+__device__ __forceinline__ TkGrow tk_grow(TkSample s) { return TkGrow{s.beg, s.len, s.items, s.mask}; }
+template <> struct tk_is_grow<TkSample> { static constexpr bool value = true; };
+template <typename... X> struct tk_is_sample { static constexpr bool value = false; };
+template <> struct tk_is_sample<TkSample> { static constexpr bool value = true; };
+__device__ __forceinline__ TkSample tk_sample() { return TkSample{}; }
+__device__ __forceinline__ TkSample tk_sample(TkExcl) { return TkSample{}; }
+__device__ __forceinline__ TkSample tk_sample(TkEvents) { return TkSample{}; }
+__device__ __forceinline__ TkSample tk_sample(TkGrow) { return TkSample{}; }
+__device__ __forceinline__ TkSample tk_sample(TkSample s) { return s; }
+// (Every score gets its noise.  Skipping the Philox call and the logarithms of a score whose key cannot beat its row's threshold
+// whatever the noise -- g < 17 -- gives the same results and was measured: it does not pay, profiles/sample_sessions.md.)
+
 // One wave merges the survivor queue of local row r into the row's sorted list L (global, length n <= k): the queue is sorted in
 // registers (bitonic over the 64 lanes), then every element's place in the union is its own index plus the number of elements of
 // the other sequence above it (binary search), and the first k places are written.  The row's threshold becomes its k-th key.
@@ -185,7 +208,7 @@ __device__ __forceinline__ void topk_merge_row(int r, uint2* L, int k, uint2* sq
 // activation), so every score is bit-identical to g4r_predict_step's.  STORED = true: the tile is read from `sc` (ldo floats per row).
 // EXCL: the exclusions (one trailing TkExcl argument) apply at every merge (topk_merge_row), the per-wave scratch grows by the
 // row's list (TK_SCRATCH_WAVE_X).  EXCL = false takes no trailing argument, so its kernel arguments -- and with them its code --
-// are those of the unfiltered kernel.
+// are those of the unfiltered kernel.  TkSample (fused, EXCL): the value selected on is the draw's key, see the struct.
 template <bool STORED, bool EXCL, typename... X>
 __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__ mp, const float* h, int mrows, const int* item_idx,
                                                     long long n_sel, const float* sc, long long ldo, int k, int tpr, uint2* ws,
@@ -194,6 +217,9 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
     static_assert(sizeof...(X) == ((EXCL || EV) ? 1 : 0), "EXCL takes one TkExcl, the events form one TkEvents");
     const TkExcl ex = tk_excl(xs...);
     const TkEvents ev = tk_events(xs...);
+    constexpr bool SMP = tk_is_sample<X...>::value;      // g4r_sample_sessions: keys in place of scores
+    static_assert(!SMP || (EXCL && !STORED), "the sampling form is fused and takes its (possibly empty) lists");
+    const TkSample smp = tk_sample(xs...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, lg = lane >> 4;
     uint2* s_q = reinterpret_cast<uint2*>(smem);
@@ -262,6 +288,13 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
                 if (ev.tie_col) t += tie_noise(mp->seed, ev.tie_ctr, row, ev.tie_col[rc]);
                 tt[ri][rg] = t; cg[ri][rg] = 0; ce[ri][rg] = 0;
             }
+    }
+    unsigned rq[2][4];      // (sampling form) the row ids of the lane's 8 rows
+    if constexpr (SMP) {
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) rq[ri][rg] = smp.row_id[min(rbase + 32 * wid + 16 * ri + 4 * lg + rg, mrows - 1)];
     }
     for (long long n0 = c0; n0 < c1; n0 += TK_TN) {
         float v[2][2][4];      // [ri][cj][rg]: row 32 wid + 16 ri + 4 lg + rg, column n0 + 16 cj + li (the MFMA accumulator layout)
@@ -343,10 +376,13 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
                         cg[ri][rg] += (n < c1 && x > tt[ri][rg]) ? 1 : 0;
                         ce[ri][rg] += (n < c1 && x == tt[ri][rg]) ? 1 : 0;
                     }
-                    const unsigned long long key = topk_key(v[ri][cj][rg], (unsigned)n);
+                    float val = v[ri][cj][rg];
+                    if constexpr (SMP)      // the draw's key (never contracted into an FMA); the tile's items are still in sItem
+                        val = __fadd_rn(__fmul_rn(val, smp.invT), gumbel_noise(smp.seed, rq[ri][rg], smp.step, max(sItem[16 * cj + li], 0)));
+                    const unsigned long long key = topk_key(val, (unsigned)n);
                     if (rbase + r < mrows && n < c1 && key > t) {
                         const int p = atomicAdd(s_qn + r, 1);
-                        s_q[r * TK_Q + p] = make_uint2(__float_as_uint(v[ri][cj][rg]), (unsigned)n);
+                        s_q[r * TK_Q + p] = make_uint2(__float_as_uint(val), (unsigned)n);
                     }
                 }
             }

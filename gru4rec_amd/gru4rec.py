@@ -1164,6 +1164,96 @@ class GRU4Rec:
         paths, step_scores = _native.beam_backtrack(parent, cols, sscores)
         return cand[paths], path_scores, step_scores, scale_exp
 
+    def sample_sessions(self, histories, steps, samples=1, temperature=1.0, top_k=None, seed=0, first_step=0, no_repeat=True,
+                        predict_for_item_ids=None, exclude=None, exclude_per_row=None, hidden=None, return_hidden=False):
+        """Stochastic continuations of N whole sessions in one stateless call: `samples` independent draws per session of `steps`
+        items each, drawn from the model's own next-item distribution.  Returns (item_ids[N, samples, steps], scores[N, samples,
+        steps] float32), plus the hidden state with return_hidden=True.  Not in the reference.  continue_sessions and beam_sessions are
+        deterministic; this call gives varied continuations of one history, several independent roll-outs per session, or simulated
+        sessions for offline policy evaluation, without a score row ever leaving the device.
+
+        Draw (i, j) -- session i, sample j -- starts from the state after histories[i] (replayed from zero, or from hidden[i]).  At
+        step s it draws ONE item from softmax(z / temperature) over its eligible candidates, where z is a candidate's logit; the item
+        is fed back on the device as the draw's next input and, with no_repeat, joins the draw's own exclusions: continue_sessions'
+        feedback on N * samples rows.  The draw is an argmax (the Gumbel-max trick):
+          z       the predict_next_batch score, bit for bit; for final_act softmax / softmax_logit the PRE-activation value
+                  h . Wy_i + By_i, of which those scores are the softmax;
+          g       -log(-log(u)), u uniform in (0, 1) from the counter-based generator: Philox4x32-10 keyed by `seed`, counter (item
+                  index >> 2, row id i * samples + j, first_step + s, a stream id of its own), lane item index & 3;
+          chosen  the eligible candidate with the largest fl32(fl32(z / temperature) + g), equal values to the lower position.
+        So a draw depends on (seed, i, j, first_step + s, the items' logits) and on nothing else: not on N, the batch, the order of
+        the rows or how the call is chunked.  `scores` holds the chosen items' z, not the perturbed values: for softmax models that
+        is the LOGIT, not the probability predict_next_batch returns.
+
+          samples          an integer in [1, G4R_SAMPLE_MAX = 64]: draws per session.
+          temperature      a finite float > 0.  Below 1 sharpens, above 1 flattens.  The greedy limit (temperature -> 0) is
+                           continue_sessions(k=1).
+          top_k            None, or an integer in [1, min(number of candidates, G4R_TOPK_MAX = 256)]: the eligible candidates are
+                           first cut to the top_k best by z (recommend_sessions' exact order, the same exclusions) and the draw is
+                           made among those.  top_k=1 is continue_sessions(k=1)'s path for every seed.
+          seed             an integer in [0, 2^64): the key of the noise.
+          first_step       the step number of the call's first draw, >= 0 with first_step + steps <= 2^31 - 1.  It lets a roll-out be
+                           carried on: sample_sessions(h, a + b)[..., a:] equals sample_sessions(<the N * samples one-item histories
+                           of the a-th drawn items>, b, samples=1, first_step=a, hidden=<the returned state reshaped to [N * samples,
+                           layers[l]]>, exclude_per_row=<history + the first a drawn items, when no_repeat>).
+          no_repeat        draw (i, j) never receives an item of histories[i] nor one it has drawn itself.  False: only exclude /
+                           exclude_per_row apply.
+          return_hidden    also return a list of float32 [N, samples, layers[l]] arrays: the state that produced the LAST step's
+                           scores, the same moment as in continue_sessions.
+          predict_for_item_ids, exclude, exclude_per_row, hidden: as in continue_sessions with k = top_k (1 without it), with its
+                           refusals, each naming its row: duplicate-free candidates under no_repeat, excluded items + steps - 1 <=
+                           G4R_EXCLUDE_MAX, at least k eligible positions at the last step.
+
+        Everything is checked before any device work and the prediction state is neither read nor changed.  N * samples must not
+        exceed 2^31 - 1.  The two-stage scan='bf16' selection is not offered here.  Out of scope as well: the log-probabilities of
+        the drawn items and nucleus (top-p) sampling -- both need a normaliser over the row's whole eligible set, which the
+        selection kernel never forms."""
+        if self.error_during_train:
+            raise Exception
+        steps = _check_steps(steps)
+        try:
+            ok = not isinstance(samples, bool) and int(samples) == samples and 1 <= samples <= _native.G4R_SAMPLE_MAX
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('samples = %r: it must be an integer in [1, G4R_SAMPLE_MAX = %d]' % (samples, _native.G4R_SAMPLE_MAX))
+        samples = int(samples)
+        try:
+            with np.errstate(all='ignore'):
+                t32 = np.float32(temperature) if not isinstance(temperature, (bool, str)) else np.float32('nan')
+                ok = bool(np.isfinite(t32) and t32 > 0 and np.isfinite(np.float32(1) / t32))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('temperature = %r: it must be a finite float > 0 (as a float32, with a finite reciprocal); the greedy limit '
+                             'temperature -> 0 is continue_sessions(k=1)' % (temperature,))
+        if top_k is not None:
+            top_k = _check_k(top_k, self._n_candidates(predict_for_item_ids), name='top_k', own_errors=True)
+        try:
+            ok = not isinstance(seed, bool) and int(seed) == seed and 0 <= seed < 2 ** 64
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('seed = %r: it must be an integer in [0, 2^64)' % (seed,))
+        try:
+            ok = not isinstance(first_step, bool) and int(first_step) == first_step and first_step >= 0 and first_step + steps <= 2 ** 31 - 1
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('first_step = %r: it must be an integer >= 0 with first_step + steps <= 2^31 - 1' % (first_step,))
+        k = top_k or 1
+        N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
+        if N * samples > 2 ** 31 - 1:
+            raise ValueError('N * samples = %d * %d exceeds 2^31 - 1' % (N, samples))
+        iidx, cand = self._candidates(predict_for_item_ids)
+        excl = self._session_exclusions(N, lens, hidx, k, iidx, no_repeat, exclude, exclude_per_row, steps=steps)
+        m = self._ensure_model()
+        out = m.sample_sessions(offs, hidx, iidx, steps, samples, top_k, float(t32), int(seed), int(first_step), bool(no_repeat), *excl,
+                                hidden=h0, return_hidden=return_hidden)
+        if not return_hidden:
+            return cand[out[0]], out[1]
+        return cand[out[0]], out[1], [h.reshape(N, samples, -1) for h in self._unpad_hidden(out[2])]
+
     # ------------------------------------------------------------------ per-row candidate lists (not in the reference)
     def _candidate_csr(self, candidates, rows, k):
         """Checks and packs the `candidates` argument of score_candidates*: (offsets int64[rows + 1], item indices int32, the

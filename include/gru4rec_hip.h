@@ -275,6 +275,33 @@ int g4r_beam_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* his
                       int32_t combine, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
                       int32_t* out_parent, int32_t* out_cols, float* out_step_scores, float* out_path_scores, int32_t* out_scale_exp);
 
+/* not in the reference: stochastic decoding of the continuations of n whole sessions, stateless -- `samples` independent draws per
+ * session from the model's own next-item distribution, with a temperature and an optional top-k truncation.  The arguments of
+ * g4r_continue_sessions without k and oversample, plus samples (1 .. G4R_SAMPLE_MAX), top_k (0: none, else 1 .. min(candidates,
+ * G4R_TOPK_MAX)), temperature (finite, > 0, finite reciprocal), seed and first_step (>= 0, first_step + steps <= 2^31 - 1).  Draw
+ * (i, j) -- session i, sample j -- has the row id q = i * samples + j (n * samples <= 2^31 - 1).  Every draw starts from the state
+ * after the history (from zero, or from h0 row i); at step s it draws one item, which is fed to the GRU as its next input and, with
+ * no_repeat, joins its own exclusion list: g4r_continue_sessions' feedback on n * samples rows.
+ *   logit z   of a candidate position: g4r_predict_step's score, bit for bit, for the element-wise final activations; for softmax /
+ *             softmax_logit the pre-activation value h . Wy_i + By_i (no stored softmax matrix is read);
+ *   noise g   lane (item & 3) of the Philox4x32-10 call (item >> 2, q, first_step + s, G4R_STREAM_GUMBEL) keyed by seed (low, high
+ *             word), item the absolute item index: x -> u = (float)(x >> 9) * 2^-23 + 2^-24 -> g = -logf(-logf(u)) (precise logf);
+ *   key       fl32(fl32(z * invT) + g), invT = 1.0f / temperature, never contracted into an FMA;
+ *   choice    the eligible position with the largest key (equal keys: the lower position; NaN last): a draw from softmax(z / T) over
+ *             the eligible positions.  top_k = t: the eligible positions are first cut to the t best by z (g4r_recommend_sessions'
+ *             exact order with k = t, the same exclusions) and the argmax runs over those; top_k = 1 is g4r_continue_sessions' path (k = 1).
+ * out_cols / out_scores[n * samples * steps], [session][sample][step]: the chosen position (item index when item_idx is NULL) and its
+ * z, not its key.  out_hidden (NULL: not wanted): per layer n * samples rows, the state that produced the LAST step's scores.  The
+ * refusals of g4r_continue_sessions apply with k = top_k, or 1 without it; everything is checked before any launch; the prediction
+ * state is neither read nor changed.  One stream synchronisation and one download per chunk of sessions (a chunk holds at most
+ * 512 draw rows).  Log-probabilities of the draws and nucleus (top-p) sampling are not offered: both need a row-wide normaliser. */
+#define G4R_SAMPLE_MAX 64
+#define G4R_STREAM_GUMBEL 0x47554D42u
+int g4r_sample_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                        const int32_t* item_idx, int64_t n_sel, int32_t steps, int32_t no_repeat, const int64_t* excl_offs,
+                        const int32_t* excl_items, const uint32_t* excl_mask, int32_t samples, int32_t top_k, float temperature,
+                        uint64_t seed, int32_t first_step, int32_t* out_cols, float* out_scores, float* const* out_hidden);
+
 /* not in the reference: item-to-item neighbours in the model's own embedding space -- the k candidates most similar to each of n
  * query items.  Stateless: the prediction state and the training state are neither read nor changed.
  *   table T     space = G4R_SPACE_OUTPUT: Wy, rows of layers[n_layers - 1] floats.  G4R_SPACE_INPUT: E when embed_mode is
@@ -464,6 +491,9 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count);
  * batch_size workgroups, and waits for it.  The step state on the device is the same before and after; the "scores" and "lossrow"
  * buffers are overwritten (every step rewrites them before it reads them).  count must be batch_size * ldSc. */
 int g4r_debug_loss_rows(g4r_model* m, float* scores, int64_t count, int32_t M, float* lossrow);
+/* Test support (tests/test_gpu_sample_sessions.py), not in the reference: out[p] = the noise g of g4r_sample_sessions for row id
+ * row_id, step `step` and item index items[p] >= 0, p < n, computed by the device function its selection calls. */
+int g4r_debug_gumbel(g4r_model* m, uint64_t seed, uint32_t row_id, uint32_t step, const int32_t* items, int64_t n, float* out);
 int g4r_selftest_mfma(float* max_abs_err);
 /* Row gather / scatter micro-benchmark on a table of n_items x W floats (fresh allocation, random rows, every launch its own
  * rows): mode 0 gather to a compact buffer, 1 gather consumed in registers (what the step's fused gathers do), 2 Adagrad scatter
