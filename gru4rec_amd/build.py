@@ -55,7 +55,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            19: "k_loss_rows' first pass starts its loop past the prefetched groups one STEP late: the columns of the first trip keep "
                "whatever the LDS held",
            20: "gumbel_noise (g4r_sample_sessions) ignores the decoding step (Philox counter word 2 = 0): every step of a draw gets the "
-               "noise of step 0"}
+               "noise of step 0",
+           21: "k_owner_window takes the sample-store row of every step of its window from the window's FIRST global step: the owner "
+               "tables of the later steps are those of another list"}
 
 
 def mutant_path(k):

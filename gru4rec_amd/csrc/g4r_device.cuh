@@ -11,6 +11,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define G4R_EPS_LOSS 1e-24f    /* gru4rec.py:230,241 */
 #define G4R_EPS_ADAGRAD 1e-6f  /* gru4rec.py:330 */
 #define G4R_OWN_INLINE 15      /* earlier occurrences an owner-table row holds (DevModel::own_pos) */
+#define G4R_OWN_SLOTS 16       /* owner tables in the ring: the steps of a window (= G4R_GRAPH_STEPS, k_owner_window) */
+#define G4R_OWN_WINDOW_MAXR 12288      /* longest occurrence list k_owner_window stages in its LDS (48 KB of ids) */
+#define G4R_OWN_WINDOW_MINWG 4         /* pre-scan workgroups of k_loss_rows (16 occurrences each) up to which the pre-scan stays: a window launch would cost more */
 
 // Mutation builds for the parity suite's self-test (tests/test_gpu_mutation.py builds them as variant libraries next to the product
 // one and expects the parity tests to turn red): G4R_MUTATE=1 inflates every per-occurrence sparse accumulator increment by
@@ -68,6 +71,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define G4R_MUT_FIRST_LATE(step) (step)
 #else
 #define G4R_MUT_FIRST_LATE(step) 0
+#endif
+
+#if defined(G4R_MUTATE) && G4R_MUTATE == 21      // test build: k_owner_window takes the sample-store row of EVERY step of its window from the
+// window's first global step
+#define G4R_MUT_WIN_G(g0, s) (g0)
+#else
+#define G4R_MUT_WIN_G(g0, s) ((g0) + (s))
 #endif
 
 // Philox stream ids (counter word 3); twin of oracle/philox.py
@@ -217,10 +227,12 @@ struct DevModel {
     GP(unsigned) dstat;  // [1024][2] rows / bias entries applied by flush launches, per workgroup id mod 1024 (statistics)
     // narrow layers (g4r_lean_kernels.cuh): dr' = da Wh^T leaves k_gru_da as ceil(D / 16) K-slice partial planes drp[slice][B][D]; k_gru_dy adds them
     GP(float) drp;
-    // owner table of the lean update (k_update_l; the pre-scan in k_loss_rows writes it, g4r_loss_kernel.cuh): [R][16] ints, row k of
-    // the owner of a repeated item = (number of earlier occurrences, their positions in ascending order), -1 when there are more than
-    // G4R_OWN_INLINE of them (k_update_l scans for those).  It sits behind k_update_l's dense-tile table.  Null: no pre-scan
-    // (G4R_OWNER_SCAN=1, or no k_update_l): every owner scans occ_idx itself.
+    // owner table of the lean update (k_update_l): a ring of G4R_OWN_SLOTS tables of [R][16] ints, row k of the owner of a repeated
+    // item = (number of earlier occurrences, their positions in ascending order), -1 when there are more than G4R_OWN_INLINE of them
+    // (k_update_l scans for those).  k_owner_window (g4r_update_kernels.cuh) writes the tables of a whole window of steps, slot = the
+    // step's index in its window; G4R_OWNER_WINDOW=0 and lists longer than its LDS: the pre-scan in k_loss_rows writes slot 0 every
+    // step (g4r_loss_kernel.cuh).  The ring sits behind k_update_l's dense-tile table.  Null: no owner table (G4R_OWNER_SCAN=1, or no
+    // k_update_l): every owner scans occ_idx itself.
     GP(int) own_pos;
 };
 // step plane of global step g

@@ -86,12 +86,19 @@ static int build_lean_args(g4r_model* m) {
         m->h_leanU = u;
         const std::vector<DenseTile> tiles = dense_tiles(d, 16, 64);
         m->ntiles16 = (int)tiles.size();
-        // behind the tiles, in the same allocation: the owner table ([R][16] ints), so that k_update_l finds it from its arguments at
-        // the first load; k_loss_rows' pre-scan fills it unless G4R_OWNER_SCAN=1
-        const size_t nslot = cdiv((long long)d.R * 16 * sizeof(int), (long long)sizeof(DenseTile));
+        // behind the tiles, in the same allocation: the ring of owner tables (G4R_OWN_SLOTS x [R][16] ints), so that k_update_l finds
+        // its step's table from its arguments at the first load.  k_owner_window fills a window's tables ahead of its steps; with
+        // G4R_OWNER_WINDOW=0, or a list too long for that kernel's LDS or too short to pay for a launch of its own, k_loss_rows' pre-scan fills slot 0 inside every step; G4R_OWNER_SCAN=1: no table
+        const size_t nslot = cdiv((long long)G4R_OWN_SLOTS * d.R * 16 * sizeof(int), (long long)sizeof(DenseTile));
         if (dalloc(m, &m->d_tiles16, tiles.size() + nslot) || dalloc(m, &m->d_leanU, (size_t)1)) return -1;
         d.own_pos = m->sw.owner_scan_in_update ? nullptr : (int*)(m->d_tiles16 + tiles.size());
         m->h_leanU.own_on = d.own_pos ? 1 : 0;
+        // the window launch costs a step what one launch per 16 steps costs (measured as the step with and without it: 0.19 us at R = 64, bench
+        // cfg #1; 0.82 us at cfg #2's R = 2304); the pre-scan costs the loss launch in proportion to the workgroups it adds -- nothing measurable
+        // at 4 (cfg #1: the window form LOST those 0.19 us per step), 1.5 us at 144 (cfg #2; profiles/owner_window.md, with the lengths between).  So: the window form where the pre-scan would add more than G4R_OWN_WINDOW_MINWG
+        // workgroups; G4R_OWNER_WINDOW=1 asks for it at any length the LDS holds
+        const bool pays = cdiv(d.R, LOSS_NW) > G4R_OWN_WINDOW_MINWG;
+        m->own_window = d.own_pos && d.R <= G4R_OWN_WINDOW_MAXR && (m->sw.owner_window > 0 || (m->sw.owner_window < 0 && pays));
         HIPCHK(hipMemcpyAsync(m->d_tiles16, tiles.data(), tiles.size() * sizeof(DenseTile), hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipStreamSynchronize(m->stream));      // (before `tiles` goes out of scope)
     }
@@ -104,6 +111,7 @@ static KernelSwitches read_switches(const g4r_config& cfg) {
     KernelSwitches w;
     w.no_lean = getenv("G4R_NO_LEAN") != nullptr; w.no_mt = getenv("G4R_NO_MT") != nullptr; w.no_bmt = getenv("G4R_NO_BMT") != nullptr;
     w.no_merge = getenv("G4R_NO_MERGE") != nullptr; w.owner_scan_in_update = env_int("G4R_OWNER_SCAN", 0) != 0;
+    w.owner_window = env_int("G4R_OWNER_WINDOW", -1);
     w.score_b_split = env_int("G4R_SCORE_B_SPLIT", 1) != 0;
     w.allow_lean_update = env_int("G4R_LEAN_UPDATE", 1) != 0; w.defer = env_int("G4R_DEFER", cfg.defer_updates) != 0;
     w.p2_geo = env_int("G4R_P2_GEO", -1); w.ba_geo = env_int("G4R_BA_GEO", -1);
@@ -407,6 +415,7 @@ void g4r_destroy(g4r_model* m) {
     if (m->p2p_region) (void)hipFree(m->p2p_region);
     for (auto e : m->evs) (void)hipEventDestroy(e);
     for (auto e : m->ev_df) if (e) (void)hipEventDestroy(e);
+    for (auto e : m->ev_ow) if (e) (void)hipEventDestroy(e);
     for (g4r_model::Scratch* sc : {&m->sc_ids, &m->sc_blk, &m->sc_cnt, &m->sc_all, &m->sc_send, &m->sc_pack, &m->sc_recv, &m->sc_hall}) {
         if (sc->p) { if (sc->host) (void)hipHostFree(sc->p); else (void)hipFree(sc->p); }
         sc->p = nullptr; sc->cap = 0;

@@ -62,7 +62,13 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     else if (s == "Hprev") { p = d.H[l][(m->gstep + 1) & 1]; n = bd; }
     else if (s == "occ_idx") { p = (const float*)d.occ_idx; n = d.R; }
     // the owner table of the last step (ints, [R][16]): row k valid for the owners of repeated items outside the negatives-only shortcut
-    else if (s == "own_pos") { if (!d.own_pos) return fail("no owner table (k_update_l not chosen, or G4R_OWNER_SCAN=1)"); p = (const float*)d.own_pos; n = 16 * (int64_t)d.R; }
+    else if (s == "own_pos") {
+        if (!d.own_pos) return fail("no owner table (k_update_l not chosen, or G4R_OWNER_SCAN=1)");
+        p = (const float*)(d.own_pos + (m->own_window ? (size_t)m->own_last * d.R * 16 : (size_t)0)); n = 16 * (int64_t)d.R;
+    }
+    // every table of the owner ring ([G4R_OWN_SLOTS][R][16]): slot i = step i of the last window (k_owner_window); without it only slot 0 is written
+    else if (s == "own_pos_ring") { if (!d.own_pos) return fail("no owner table (k_update_l not chosen, or G4R_OWNER_SCAN=1)"); p = (const float*)d.own_pos; n = (int64_t)G4R_OWN_SLOTS * 16 * d.R; }
+    else if (s == "owner_window") { if (count < 1) return fail("count"); host[0] = (m->own_window && k.update == UP_LEAN) ? 1.f : 0.f; return 0; }      // 1: k_owner_window writes the owner tables of a window of steps ahead of them; 0: the pre-scan in k_loss_rows (G4R_OWNER_WINDOW=0, R > G4R_OWN_WINDOW_MAXR, R <= 16 G4R_OWN_WINDOW_MINWG), or no table
 #if !defined(G4R_CLK_TRACE)
     else if (s == "dbgclk" || s == "dbgtile") return fail("in-kernel traces need a library built with G4R_BUILD_CLK=1 (python -m gru4rec_amd.build --force) and G4R_CLK=1 at run time");
 #endif

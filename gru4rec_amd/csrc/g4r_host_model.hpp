@@ -25,10 +25,10 @@ void g4r_set_error(const char* fmt, ...) {
     } while (0)
 
 enum { KN_GRU_P1 = 0, KN_GRU_P2, KN_SCORE_FWD, KN_LOSS, KN_SCORE_BWD, KN_BWD_PRE, KN_BWD_A, KN_BWD_B, KN_DENSE, KN_ALLREDUCE,
-       KN_DENSE_APPLY, KN_SPARSE, KN_UPDATE, KN_BWD_FUSED, KN_FWD_FUSED, KN_GATE, KN_FLUSH, KN_SCAN, KN_FINISH, KN_GRU_V, KN_GRU_H, KN_GRU_DA, KN_GRU_DY, KN_COUNT };
+       KN_DENSE_APPLY, KN_SPARSE, KN_UPDATE, KN_BWD_FUSED, KN_FWD_FUSED, KN_GATE, KN_FLUSH, KN_SCAN, KN_FINISH, KN_GRU_V, KN_GRU_H, KN_GRU_DA, KN_GRU_DY, KN_OWNER_WINDOW, KN_COUNT };
 static const char* KN_NAMES[KN_COUNT] = {"k_gru_p1", "k_gru_p2", "k_score_fwd", "k_loss_rows", "k_score_bwd", "k_gru_bwd_pre",
                                          "k_gru_bwd_a", "k_gru_bwd_b", "k_dense_grad", "rccl_allreduce", "k_dense_apply",
-                                         "k_sparse_update", "k_update", "k_gru_bwd", "k_gru_fwd", "k_gru_gate", "k_sparse_flush", "k_defer_scan", "k_finish_rows", "k_gru_v", "k_gru_h", "k_gru_da", "k_gru_dy"};
+                                         "k_sparse_update", "k_update", "k_gru_bwd", "k_gru_fwd", "k_gru_gate", "k_sparse_flush", "k_defer_scan", "k_finish_rows", "k_gru_v", "k_gru_h", "k_gru_da", "k_gru_dy", "k_owner_window"};
 
 struct EvRec { int kn; hipEvent_t a, b; };
 
@@ -41,6 +41,7 @@ struct KernelSwitches {
     bool allow_lean_update = true;        // G4R_LEAN_UPDATE=0: the merged k_update where k_update_l would run, as the deferred mode runs it
     bool score_b_split = true;            // G4R_SCORE_B_SPLIT=0: k_score_b keeps its role A (the item-gradient tiles), no hosting in k_gru_dy
     bool owner_scan_in_update = false;    // G4R_OWNER_SCAN=1: k_update_l's owners of repeated items scan occ_idx themselves (no pre-scan in k_loss_rows)
+    int owner_window = -1;                // G4R_OWNER_WINDOW=0: the owner tables come from the pre-scan in k_loss_rows, every step, not from k_owner_window once per window; 1: from k_owner_window wherever its LDS holds the list; unset: where that pays (g4r_host_create.hpp)
     bool defer = false;                   // G4R_DEFER (default: g4r_config::defer_updates)
     int p2_geo = -1, ba_geo = -1;         // G4R_P2_GEO / G4R_BA_GEO = 0 / 1: the 4-wave / 8-wave geometry of k_gru_p2 / k_gru_bwd_a (-1: the policy)
     int wide2 = -1, p1_ks = 128, bb_ks = 0;      // G4R_WIDE2 (wide-layer kernel mask, -1: the policy), G4R_P1_KS / G4R_BB_KS (their K slices)
@@ -123,6 +124,9 @@ struct g4r_model {
     LeanB* d_leanB = nullptr; LeanB h_leanB;      // argument block of k_score_b
     LeanU* d_leanU = nullptr; LeanU h_leanU;      // argument block of k_update_l, its 16 x 64 dense tiles
     DenseTile* d_tiles16 = nullptr; int ntiles16 = 0;
+    bool own_window = false;     // k_owner_window writes the owner tables of a window of steps ahead of them (debug key `owner_window`)
+    int own_last = 0;            // ring slot of the last step run (debug key `own_pos`)
+    hipEvent_t ev_ow[2] = {nullptr, nullptr};      // profiling: the window launch
     LeanV* d_leanV = nullptr; LeanH* d_leanH = nullptr; LeanDa* d_leanDa = nullptr; LeanDy* d_leanDy = nullptr;      // [layers] argument blocks (g4r_lean_kernels.cuh)
     hipGraphExec_t gexec = nullptr;
     hipGraphExec_t gexec_small = nullptr;        // single GPU: G4R_GRAPH_STEPS_SMALL steps, for what a run leaves after the big replays
@@ -350,6 +354,7 @@ static constexpr auto k_score_bwd_w = k_score_bwd<64, 64>;
 static const size_t SMEM_SBW = std::max(tile_smem<64, 64, 64, true, false>(), tile_smem<64, 64, 64, false, false>());
 #define ZROW_FLOATS 8192      // DevModel::zrow: an LDS-DMA tile walks K floats along it
 #define G4R_DEFER_SLOTS 16    // ring slots of the step planes = steps of a deferral window (= G4R_GRAPH_STEPS; a power of two)
+static_assert(G4R_OWN_SLOTS == G4R_DEFER_SLOTS, "the windows of g4r_train_steps serve the deferral ring and the owner ring alike");
 static const size_t SMEM_SF = tile_smem<SF_BM, GT_BN, GT_BK, false, true>() + GT_BN * sizeof(int);
 static constexpr auto k_score_mt_4s = k_score_mt<4, true>;       // W = 272: B = 512, N = 8704 on 256 CUs
 static const size_t SMEM_MT_4S = (size_t)MtCfg<4, true>::SMEM_FLOATS * sizeof(float);

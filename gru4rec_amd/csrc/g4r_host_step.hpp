@@ -28,7 +28,9 @@ static void launch_loss_rows(g4r_model* m, dim3 grid, bool timed, hipEvent_t ev_
 
 // Every launch of a training step, in order, as m->kern chose them (choose_kernels).
 // part: 0 = the whole step; 1 = head (everything up to the dense gradients); 2 = tail (all-reduce, dense apply, sparse update)
-static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
+// slot: the step's index in its window (a graph's steps: their index in the graph; eager steps: g4r_train_steps' windows) -- the table
+// of the owner ring k_owner_window wrote for it (g4r_update_kernels.cuh); 0 where the pre-scan in k_loss_rows writes the table
+static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0, int slot = 0) {
     DevModel& d = m->dm;
     const StepKernels& k = m->kern;
     const int L = d.n_layers, B = d.B;
@@ -142,9 +144,10 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
     end();
     begin(KN_LOSS);
     {
-        // a step that ends in k_update_l: up to one more workgroup per idle CU, the owner pre-scan of its repeated items (g4r_loss_kernel.cuh)
+        // a step that ends in k_update_l and whose owner table no window launch has written: up to one more workgroup per idle CU, the
+        // owner pre-scan of its repeated items (g4r_loss_kernel.cuh)
         const int nown = std::min(cdiv(d.R, LOSS_NW), std::max(2 * m->n_cu - B, 32));
-        const dim3 gloss(B + (merged && k.update == UP_LEAN && d.own_pos ? nown : 0));
+        const dim3 gloss(B + (merged && k.update == UP_LEAN && d.own_pos && !m->own_window ? nown : 0));
         if (!(m->sw.skip_kn && ((m->sw.skip_kn >> KN_LOSS) & 1ull))) launch_loss_rows(m, gloss, recs != nullptr, cur_a, cur_b);
     }
     end();
@@ -248,10 +251,12 @@ static int launch_step(g4r_model* m, std::vector<EvRec>* recs, int part = 0) {
             const unsigned packA = (unsigned)m->ntiles16 | ((unsigned)nb8 << 16), packB = (unsigned)d.R | ((unsigned)B << 16);
             const unsigned nbk = 1u + (unsigned)cdiv(d.ldSc, 512);
             const dim3 gl(nbk + m->ntiles16 + nb8);
+            // this step's table of the owner ring (behind the dense tiles; slot 0 without a window launch, the ring's base when there is no table)
+            const int* opos = (const int*)(m->d_tiles16 + m->ntiles16) + (m->own_window ? (size_t)slot * d.R * 16 : (size_t)0);
             if (mo) LK(k_update_l<true>, gl, dim3(512), 0, s, (const LeanU*)m->d_leanU, (const DenseTile*)m->d_tiles16, (const int*)d.occ_idx, (int*)d.occ_fl,
-                       (const float*)d.dSx, (const float*)d.dSy, (const float*)d.dSBy, packA, packB, nbk);
+                       (const float*)d.dSx, (const float*)d.dSy, (const float*)d.dSBy, opos, packA, packB, nbk);
             else LK(k_update_l<false>, gl, dim3(512), 0, s, (const LeanU*)m->d_leanU, (const DenseTile*)m->d_tiles16, (const int*)d.occ_idx, (int*)d.occ_fl,
-                    (const float*)d.dSx, (const float*)d.dSy, (const float*)d.dSBy, packA, packB, nbk);
+                    (const float*)d.dSx, (const float*)d.dSy, (const float*)d.dSBy, opos, packA, packB, nbk);
             end();
             HIPCHK(hipGetLastError());
             return 0;
@@ -395,7 +400,7 @@ static int ensure_graph(g4r_model* m) {
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(m->stream, rccl_in_graph ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
     int rc = 0;
-    for (int i = 0; i < G4R_GRAPH_STEPS && !rc; ++i) rc = launch_step(m, nullptr);
+    for (int i = 0; i < G4R_GRAPH_STEPS && !rc; ++i) rc = launch_step(m, nullptr, 0, i);
     hipError_t e = hipStreamEndCapture(m->stream, &graph);
     if (rc || e != hipSuccess || !graph) {
         if (graph) (void)hipGraphDestroy(graph);
@@ -413,7 +418,7 @@ static int ensure_graph(g4r_model* m) {
         hipGraph_t g2 = nullptr;
         if (hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
             int rc2 = 0;
-            for (int i = 0; i < G4R_GRAPH_STEPS_SMALL && !rc2; ++i) rc2 = launch_step(m, nullptr);
+            for (int i = 0; i < G4R_GRAPH_STEPS_SMALL && !rc2; ++i) rc2 = launch_step(m, nullptr, 0, i);
             hipError_t e2 = hipStreamEndCapture(m->stream, &g2);
             if (!rc2 && e2 == hipSuccess && g2 && hipGraphInstantiate(&m->gexec_small, g2, nullptr, nullptr, 0) != hipSuccess) m->gexec_small = nullptr;
             if (g2) (void)hipGraphDestroy(g2);
@@ -493,16 +498,38 @@ int g4r_train_steps(g4r_model* m, int64_t t0, int64_t n_steps) {
         if (run <= 0) return fail("internal: empty run");
         int64_t done = 0;
         // a deferral window around `nw` steps starting `done` steps into this run: which rows may wait (scan), ... steps ..., their flush
-        auto window_open = [&](int64_t nw) {
-            if (!m->defer_on) return;
+        // ... and, where the steps end in k_update_l with the owner tables on, the tables of the window's steps (k_owner_window: slot i of
+        // the ring = step i of the window)
+        const bool own_win = m->own_window && m->kern.update == UP_LEAN && !(m->profiling && m->profile_split);
+        auto window_open = [&](int64_t nw) -> int {
+            if (own_win && !((m->sw.skip_kn >> KN_OWNER_WINDOW) & 1ull)) {      // (G4R_SKIP_KN, tools/kn_cost.py: what the window launch costs a step)
+                const DevModel& d = m->dm;
+                const bool timed = m->profiling;
+                if (timed) for (auto& e : m->ev_ow) if (!e) (void)hipEventCreate(&e);
+                const dim3 gw((unsigned)(nw * cdiv(2 * d.B, OW_NW)));
+                const size_t lds = (size_t)(((d.R + 3) & ~3) + 16 * OW_NW) * sizeof(int);
+                if (timed) hipExtLaunchKernelGGL(k_owner_window, gw, dim3(OW_T), lds, m->stream, m->ev_ow[0], m->ev_ow[1], 0, (const DevModel*)m->d_dm, (long long)(t + done), (long long)(m->gstep + done), (int)nw);
+                else hipLaunchKernelGGL(k_owner_window, gw, dim3(OW_T), lds, m->stream, (const DevModel*)m->d_dm, (long long)(t + done), (long long)(m->gstep + done), (int)nw);
+                HIPCHK(hipGetLastError());      // (a refused launch would leave the steps the tables of an older window)
+            }
+            if (!m->defer_on) return 0;
             wguard.open = true;
             const dim3 gs(cdiv(nw * m->dm.R, 256));
             if (m->profiling) (void)hipEventRecord(m->ev_df[0], m->stream);
             hipLaunchKernelGGL(k_defer_scan, gs, dim3(256), 0, m->stream, (const DevModel*)m->d_dm, (long long)(t + done), (long long)(m->gstep + done), (int)nw, 0);
             hipLaunchKernelGGL(k_defer_scan, gs, dim3(256), 0, m->stream, (const DevModel*)m->d_dm, (long long)(t + done), (long long)(m->gstep + done), (int)nw, 1);
             if (m->profiling) (void)hipEventRecord(m->ev_df[1], m->stream);
+            return 0;
         };
         auto window_close = [&](int64_t nw, int64_t first) -> int {
+            if (own_win) {
+                m->own_last = (int)nw - 1;
+                if (m->profiling) {
+                    HIPCHK(hipStreamSynchronize(m->stream));
+                    float ms = 0.f;
+                    if (hipEventElapsedTime(&ms, m->ev_ow[0], m->ev_ow[1]) == hipSuccess) { m->kn_ms[KN_OWNER_WINDOW] += ms; m->kn_n[KN_OWNER_WINDOW]++; }
+                }
+            }
             if (!m->defer_on) return 0;
             if (m->profiling) (void)hipEventRecord(m->ev_df[2], m->stream);
             hipLaunchKernelGGL(k_sparse_flush, dim3(cdiv(nw * m->dm.dRcap, SP_WAVES * FL_NR)), dim3(SP_WAVES * 64), 0, m->stream, (const DevModel*)m->d_dm, (long long)(m->gstep + first), (int)nw);
@@ -519,28 +546,29 @@ int g4r_train_steps(g4r_model* m, int64_t t0, int64_t n_steps) {
         if (use_graph && run >= G4R_GRAPH_STEPS_SMALL) {
             if (ensure_graph(m)) return -1;
             for (; done + m->graph_steps <= run; done += m->graph_steps) {
-                window_open(m->graph_steps);
+                if (window_open(m->graph_steps)) return -1;
                 HIPCHK(hipGraphLaunch(m->gexec, m->stream));
                 if (window_close(m->graph_steps, done)) return -1;
             }
             if (m->gexec_small)
                 for (; done + G4R_GRAPH_STEPS_SMALL <= run; done += G4R_GRAPH_STEPS_SMALL) {
-                    window_open(G4R_GRAPH_STEPS_SMALL);
+                    if (window_open(G4R_GRAPH_STEPS_SMALL)) return -1;
                     HIPCHK(hipGraphLaunch(m->gexec_small, m->stream));
                     if (window_close(G4R_GRAPH_STEPS_SMALL, done)) return -1;
                 }
         }
-        int64_t win_first = -1, win_n = 0;      // eager steps (no graph; per-kernel profiling): windows of up to G4R_DEFER_SLOTS steps
+        int64_t win_first = -1, win_n = 0;      // eager steps (no graph; per-kernel profiling): windows of up to G4R_DEFER_SLOTS steps (deferral, owner tables)
         for (; done < run; ++done) {
-            if (m->defer_on && win_n == 0) {
+            if ((m->defer_on || own_win) && win_n == 0) {
                 win_n = std::min<int64_t>(G4R_DEFER_SLOTS, run - done); win_first = done;
-                window_open(win_n);
+                if (window_open(win_n)) return -1;
             }
+            const int slot = win_n > 0 ? (int)(done - win_first) : 0;
             if (m->profiling) {
                 // per-kernel durations: start/stop events attached to every dispatch (hipExtLaunchKernelGGL), i.e. the
                 // kernel's own begin/end timestamps -- the quantity rocprofv3 --kernel-trace reports; eager launches
                 recs.clear();
-                if (launch_step(m, &recs)) return -1;
+                if (launch_step(m, &recs, 0, slot)) return -1;
                 HIPCHK(hipStreamSynchronize(m->stream));
                 for (auto& r : recs) {
                     float ms = 0.f;
@@ -552,7 +580,7 @@ int g4r_train_steps(g4r_model* m, int64_t t0, int64_t n_steps) {
                 if (ensure_head_graph(m)) return -1;
                 HIPCHK(hipGraphLaunch(m->gexec_head, m->stream));
                 if (launch_step(m, nullptr, 2)) return -1;
-            } else if (launch_step(m, nullptr)) return -1;
+            } else if (launch_step(m, nullptr, 0, slot)) return -1;
             if (win_n > 0 && done + 1 == win_first + win_n) {
                 if (window_close(win_n, win_first)) return -1;
                 win_n = 0;

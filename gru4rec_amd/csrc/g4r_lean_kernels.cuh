@@ -927,7 +927,8 @@ __global__ __launch_bounds__(1024) void k_gru_dy_a(const LeanDy* __restrict__ ap
 //   sparse role (one wave per occurrence k of X | Y | samples, eight per workgroup, NO LDS, no barrier): item id and step row with the
 //     first loads; behind the id the item's (last, first, count) entry, parameter row and bias -- one round trip; the wave of the LAST
 //     occurrence owns the row.  Single occurrences (~90 %) finish right there.  An owner of a repeated item takes the positions of the
-//     earlier occurrences from its row of the owner table k_loss_rows' pre-scan wrote (owner_prescan, g4r_loss_kernel.cuh: requested
+//     earlier occurrences from its row of the step's owner table (written ahead of the step's window by k_owner_window, g4r_update_kernels.cuh,
+//     or -- G4R_OWNER_WINDOW=0 -- by k_loss_rows' pre-scan, owner_prescan, g4r_loss_kernel.cuh; requested
 //     with the item id), or -- more than G4R_OWN_INLINE of them, or G4R_OWNER_SCAN=1 -- finds them itself: the id list is 9 KB and L2 resident,
 //     so it reads the slice [first, k) with 16-byte loads (up to 1024 ids per round trip) and ballots the matches.  Either way it adds
 //     their step rows in occurrence order, eight rows per round trip -- the arithmetic and the
@@ -989,7 +990,7 @@ __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* 
             for (int cdup = 1; cdup < n; ++cdup) { S.x += sk.x; S.y += sk.y; S.z += sk.z; S.w += sk.w; Sb += bsk; }
             nb_e = n - 1;
         } else if (a.own_on && __builtin_amdgcn_readfirstlane(opos) >= 0) {
-            // earlier occurrences from the owner table (ascending positions, k_loss_rows' pre-scan), eight step rows per round trip
+            // earlier occurrences from the owner table (ascending positions: k_owner_window / k_loss_rows' pre-scan), eight step rows per round trip
             const int ln = __builtin_amdgcn_readfirstlane(opos);
             for (int q0 = 0; q0 < ln; q0 += 8) {
                 const int nj = min(8, ln - q0);
@@ -1227,7 +1228,8 @@ __device__ __forceinline__ void lean_bookkeep(const LeanU& a, unsigned part, uns
 // packA = ntiles | nblk << 16, packB = R | B << 16, nbk = 1 + ceil(ldSc / 512).
 template <bool MOM>
 __global__ __launch_bounds__(512) void k_update_l(const LeanU* __restrict__ ap, const DenseTile* __restrict__ tiles_, const int* occ_idx_, int* occ_fl_,
-                                                  const float* dSx_, const float* dSy_, const float* dSBy_, unsigned packA, unsigned packB, unsigned nbk) {
+                                                  const float* dSx_, const float* dSy_, const float* dSBy_, const int* opos_, unsigned packA, unsigned packB,
+                                                  unsigned nbk) {
     const unsigned ntiles = packA & 0xFFFFu, nblk = packA >> 16, R = packB & 0xFFFFu, B = packB >> 16;
     const LeanU a = *ap;
     LSPAN_BEGIN(a.dbgtile, 2700);
@@ -1236,11 +1238,11 @@ __global__ __launch_bounds__(512) void k_update_l(const LeanU* __restrict__ ap, 
     if (b < ntiles) { lean_dense_tile<MOM>(a, tiles_, b, B); LSPAN_END(); return; }
     // occurrences strided over the workgroups (wave w of workgroup q takes k = w nblk + q: the owners of the popular items -- the LAST
     // occurrences, with their duplicate sums -- sit together at the end of the list; contiguous, they would share a few workgroups)
-    // (the owner table sits behind the dense-tile table, in its allocation: its address is in the arguments)
+    // (opos_: this step's table of the owner ring, an argument: its rows are requested with the first loads)
     const unsigned q = b - ntiles, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     lean_rows_update<MOM>(a, (const GAS int*)occ_idx_, (GAS int*)occ_fl_, (const GAS float*)dSx_, (const GAS float*)dSy_, (const GAS float*)dSBy_,
-                          (const GAS int*)(tiles_ + ntiles), wid * nblk + q, R, B);
+                          (const GAS int*)opos_, wid * nblk + q, R, B);
     LSPAN_END();
 }
-template __global__ void k_update_l<false>(const LeanU*, const DenseTile*, const int*, int*, const float*, const float*, const float*, unsigned, unsigned, unsigned);
-template __global__ void k_update_l<true>(const LeanU*, const DenseTile*, const int*, int*, const float*, const float*, const float*, unsigned, unsigned, unsigned);
+template __global__ void k_update_l<false>(const LeanU*, const DenseTile*, const int*, int*, const float*, const float*, const float*, const int*, unsigned, unsigned, unsigned);
+template __global__ void k_update_l<true>(const LeanU*, const DenseTile*, const int*, int*, const float*, const float*, const float*, const int*, unsigned, unsigned, unsigned);

@@ -52,7 +52,10 @@ __device__ __forceinline__ void vst(Ptr p, const float (&o)[V]) {
     else p[0] = o[0];
 }
 
-// Owner pre-scan of the lean update (k_update_l, g4r_lean_kernels.cuh), run by the workgroups of k_loss_rows past the batch rows: launch_step
+// Owner pre-scan of the lean update (k_update_l, g4r_lean_kernels.cuh), run by the workgroups of k_loss_rows past the batch rows.  The default
+// form writes the owner tables of a whole window of steps in one launch in front of it (k_owner_window, g4r_update_kernels.cuh: the pre-scan
+// workgroups made this launch's boundary 0.8-2.2 us longer in every step); this one stays for G4R_OWNER_WINDOW=0 and for occurrence lists past
+// G4R_OWN_WINDOW_MAXR ids, and writes the same rows into slot 0 of the ring: launch_step
 // adds min(ceil(R / 16), max(2 CUs - B, 32)) of them when the step ends in k_update_l (one occurrence per wave at the bench shapes; they
 // carry the launch's dynamic LDS, which they do not use, so their count stays bounded at large R).  Nothing here depends on that launch -- occ_idx / occ_fl are complete once
 // k_score_s has ended -- and k_loss_rows leaves most CUs idle (B = 128 workgroups on 256 CUs), so the owners of repeated items find
@@ -141,8 +144,8 @@ __global__ __launch_bounds__(LOSS_T) void k_loss_rows(const DevModel* __restrict
     // (measured, round 3: requesting the WHOLE row up front -- 10 scores per thread at B = 512 with 8192 negatives -- does not move
     // the kernel, 17.0 vs 17.1 us; neither do 512- or 256-thread workgroups, 18.7 / 29.5 us: the row is not waiting for its loads)
     constexpr int LOSS_PRE = (V == 4) ? 2 : 4;
-#if defined(G4R_CLK_TRACE)      // (first, last) stamp of workgroups < 1024 -> dbgtile[7168 + workgroup], the top of the span table (tools/clk_lean.py), written at thread 0's exit
-    struct Span { GAS long long* p; __device__ ~Span() { if (p) p[1] = wall_clock64(); } } span_{(m.dbgtile && tid == 0 && i < 1024) ? m.dbgtile + 8 * (size_t)(7168 + i) : nullptr};
+#if defined(G4R_CLK_TRACE)      // (first, last) stamp of workgroups < 532 -> dbgtile[7168 + workgroup] (tools/clk_lean.py), written at thread 0's exit; [7700, 8100) is k_owner_window's
+    struct Span { GAS long long* p; __device__ ~Span() { if (p) p[1] = wall_clock64(); } } span_{(m.dbgtile && tid == 0 && i < 532) ? m.dbgtile + 8 * (size_t)(7168 + i) : nullptr};
     if (span_.p) span_.p[0] = wall_clock64();
 #endif
     const StepCtx c = load_ctx(st);

@@ -661,6 +661,99 @@ __global__ __launch_bounds__(256) void k_defer_scan(const DevModel* __restrict__
     if (pass == 0) atomicMax((int*)lu, (int)(g0 + s));
     else m.dcand[slot] = (*lu == (int)(g0 + s)) ? 1 : 0;
 }
+// ---------------------------------------------------------------------------------------------
+// Owner tables of the lean update (k_update_l, g4r_lean_kernels.cuh) for a whole window of steps, in ONE launch in front of the window
+// (the host loop: window launch, graph replay): by the rule above the occurrence list X | Y | samples of every step of the window is
+// known before the first of them runs, and so is, for every repeated item, which occurrence comes last in its table (the owner) and
+// where the earlier ones sit.  Slot s of the ring DevModel::own_pos takes the table of step s: row k of an owner = (number of earlier
+// occurrences, their positions in ascending order), or -1 when there are more than G4R_OWN_INLINE of them (that owner scans in
+// k_update_l) -- entry for entry what owner_prescan (g4r_loss_kernel.cuh) writes from the step's own occ_idx / occ_fl inside the step.
+// No row is needed where all occurrences of an item are sampled negatives (k_update_l's (count - 1) x own row shortcut), so only the
+// items of X | Y have to be looked at: ceil(2 B / 16) workgroups per step stage the step's R ids in the LDS, and wave p < 2 B takes the
+// item at position p: it reads its table's part of the list ([0, B) of X for a separate embedding, [B, R) for Wy next to one, the whole
+// list for the constrained embedding) in slices of 1024 ids, four 16-byte LDS reads per lane, and ballots only where a lane saw a
+// match.  Is the first match not p itself, the wave of that earlier position does the item and this one ends.  The first 16 positions
+// go to the wave's LDS row in ascending order, the last match is the owner.  No atomics, no counters, no item-indexed table.
+#define OW_T 1024
+#define OW_NW (OW_T / 64)
+static_assert(G4R_OWN_INLINE + 1 == 16, "an owner-table row is 16 ints: the count and G4R_OWN_INLINE positions");
+static_assert(((size_t)G4R_OWN_WINDOW_MAXR + 16 * OW_NW) * sizeof(int) <= 65536, "k_owner_window: the longest list and the waves' position rows share one workgroup's 64 KB of LDS");
+__global__ __launch_bounds__(OW_T) void k_owner_window(const DevModel* __restrict__ mp, long long t0, long long g0, int nw) {
+    const DevModel& m = *mp;
+    extern __shared__ __attribute__((aligned(16))) int sid[];      // [Rp] the step's ids, [OW_NW][16] the waves' first positions
+    const int R = m.R, B = m.B, Rp = (R + 3) & ~3;
+    const int gps = (2 * B + OW_NW - 1) / OW_NW;      // workgroups per step
+    const int s = (int)blockIdx.x / gps, q = (int)blockIdx.x - s * gps;
+#if defined(G4R_CLK_TRACE)      // (first, last) stamp of workgroups < 400 -> dbgtile[7700 + workgroup] (tools/clk_lean.py), written at thread 0's exit; k_loss_rows keeps to [7168, 7700)
+    struct Span { GAS long long* p; __device__ ~Span() { if (p) p[1] = wall_clock64(); } } span_{(m.dbgtile && threadIdx.x == 0 && blockIdx.x < 400) ? m.dbgtile + 8 * (size_t)(7700 + blockIdx.x) : nullptr};
+    if (span_.p) span_.p[0] = wall_clock64();
+#endif
+    if (s >= nw) return;
+    for (int k = threadIdx.x; k < Rp; k += OW_T) {
+        int table;
+        sid[k] = k < R ? defer_item(m, t0 + s, G4R_MUT_WIN_G(g0, s), k, table) : -1;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int p = q * OW_NW + wid;
+    if (p >= 2 * B) return;
+    const int item = sid[p];
+    if (item < 0) return;      // wave-uniform
+    const bool constrained = m.embed_mode == G4R_EMBED_CONSTRAINED;
+    const int ta = (constrained || p < B) ? 0 : B, tb = (!constrained && p < B) ? B : R;      // the positions of p's table
+    int* spos = sid + Rp + 16 * wid;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int cnt = 0, last = p;      // matches so far, the newest of them (wave-uniform)
+    for (int base0 = ta & ~3; base0 < tb; base0 += 1024) {
+        int4 vv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) vv[u] = *(const int4*)(sid + min(base0 + 256 * u + 4 * lane, Rp - 4));
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j0 = base0 + 256 * u + 4 * lane;
+            const int ids[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+            bool hit[4], anyl = false;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { hit[e] = ids[e] == item && j0 + e >= ta && j0 + e < tb; anyl = anyl || hit[e]; }
+            if (__ballot(anyl) == 0ull) continue;      // wave-uniform
+            unsigned long long mk[4];
+            int at = cnt;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                mk[e] = __ballot(hit[e]);
+                at += __popcll(mk[e] & below);      // matches of the lanes below (positions j0' < j0)
+            }
+            const unsigned long long any = mk[0] | mk[1] | mk[2] | mk[3];
+            if (cnt == 0) {      // the item's first occurrence in its table
+                const int l0 = __builtin_ctzll(any);
+                int e0 = 3;
+#pragma unroll
+                for (int e = 2; e >= 0; --e) if ((mk[e] >> l0) & 1ull) e0 = e;
+                if (base0 + 256 * u + 4 * l0 + e0 != p) return;      // an earlier position: its wave writes the row
+            }
+            const int lh = 63 - __builtin_clzll(any);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if ((mk[e] >> lh) & 1ull) last = base0 + 256 * u + 4 * lh + e;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (hit[e]) {
+                    if (at <= G4R_OWN_INLINE) spos[at] = j0 + e;
+                    ++at;
+                }
+                cnt += __popcll(mk[e]);
+            }
+        }
+    }
+    if (cnt < 2) return;      // a single occurrence
+    GAS int* pos = m.own_pos + ((size_t)s * (size_t)R + (size_t)last) * 16;
+    if (cnt - 1 > G4R_OWN_INLINE) {      // a hot item: its owner in k_update_l scans the ids itself
+        if (lane == 0) pos[0] = -1;
+        return;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (the positions other lanes of this wave put into spos)
+    if (lane < cnt - 1) pos[1 + lane] = spos[lane];
+    if (lane == 0) pos[0] = cnt - 1;
+}
 #define FL_NR 4      // pending entries per wave: their row requests are in flight together (rows of <= 256 floats)
 __global__ __launch_bounds__(SP_WAVES * 64) void k_sparse_flush(const DevModel* __restrict__ mp, long long g0, int n) {
     const DevModel& m = *mp;

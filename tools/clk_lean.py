@@ -20,6 +20,8 @@ for rep in range(5):
         m.train_steps(200 + rep, 1)
     R = 2 * cfg['batch_size'] + cfg['n_sample']
     NOWN = min((R + 15) // 16, max(2 * int(m.get_debug('n_cu', (1,))[0]) - cfg['batch_size'], 32))      # owner pre-scan workgroups (launch_step)
+    if int(m.get_debug('owner_window', (1,))[0]):
+        NOWN = 0      # the owner tables come from k_owner_window, one launch in front of the window
     raw = m.get_debug('dbgclk', (2 * (64 + 8 * R),)).view(np.int64)
     def show(name, v, idx):
         v = np.asarray(v, dtype=np.int64)
@@ -59,6 +61,10 @@ for rep in range(5):
     okb = tb[nA:][tb[nA:, 1] > 0]
     if len(okb):
         t0b = okb[:, 0].min()      # role B's first start: the launch k_score_b in both forms
+        ts = tl_all[4096:4096 + ((ld + 31) // 32) * ((B_ + 31) // 32)]
+        ts = ts[ts[:, 1] > 0]
+        if len(ts):      # the loss launch and its two boundaries
+            print('      k_score_s last end -> k_score_b role B first start: %.2f us' % ((t0b - ts[:, 1].max()) / 100.))
         ends = {}
         for nm, tt in (('k_score_b role A (%s)' % ('hosted in k_gru_dy' if moved else 'in k_score_b'), tb[:nA]), ('k_score_b role B', tb[nA:]),
                        ('k_gru_da', tl_all[1400:1400 + ((D_ + 15) // 16) * ((B_ + 15) // 16)]),
@@ -83,6 +89,12 @@ for rep in range(5):
                 print('      k_loss_rows %-23s %4d: start %+5.2f .. %+5.2f, end %+5.2f .. %+5.2f us; own duration median %.2f max %.2f' % (
                     nm, len(tt), (tt[:, 0].min() - t0l) / 100., (tt[:, 0].max() - t0l) / 100., (tt[:, 1].min() - t0l) / 100., (tt[:, 1].max() - t0l) / 100.,
                     np.median((tt[:, 1] - tt[:, 0]) / 100.), ((tt[:, 1] - tt[:, 0]) / 100.).max()))
+    # k_owner_window (dbgtile[7700 ..]): the launch in front of the window this step belongs to
+    tw = tl_all[7700:8100]
+    tw = tw[tw[:, 1] > 0]
+    if len(tw) and NOWN == 0:
+        print('      k_owner_window %4d workgroups: span %.2f us (first start .. last end), own duration median %.2f max %.2f; last end %.2f us before the last step\'s k_gru_v began' % (
+            len(tw), (tw[:, 1].max() - tw[:, 0].min()) / 100., np.median((tw[:, 1] - tw[:, 0]) / 100.), ((tw[:, 1] - tw[:, 0]) / 100.).max(), (t0 - tw[:, 1].max()) / 100.))
     if True:
         nt = 82
         nbk = 1 + (ld + 511) // 512

@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 cfg = sys.argv[1] if len(sys.argv) > 1 else 'cfg2'
 KN = ["k_gru_p1", "k_gru_p2", "k_score_fwd", "k_loss_rows", "k_score_bwd", "k_gru_bwd_pre", "k_gru_bwd_a", "k_gru_bwd_b", "k_dense_grad", "rccl_allreduce",
       "k_dense_apply", "k_sparse_update", "k_update", "k_gru_bwd", "k_gru_fwd", "k_gru_gate", "k_sparse_flush", "k_defer_scan", "k_finish_rows",
-      "k_gru_v", "k_gru_h", "k_gru_da", "k_gru_dy"]
+      "k_gru_v", "k_gru_h", "k_gru_da", "k_gru_dy", "k_owner_window"]
 def run(mask):
     env = dict(os.environ)
     if mask: env['G4R_SKIP_KN'] = hex(mask)
