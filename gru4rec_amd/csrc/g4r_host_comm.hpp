@@ -126,9 +126,8 @@ int g4r_p2p_attach(g4r_model* m, const char* handles, int32_t nranks, int32_t ra
     a.round = m->p2p_round;
     a.nranks = nranks; a.rank = rank; a.count = m->dm.dense_count; a.cap = m->p2p_cap; a.nblk = m->p2p_nblk;
     a.spin_ticks = (long long)p2p_timeout_ms() * 100000;      // wall_clock64: 100 MHz
-    // a step graph captured with the RCCL node is stale now
-    if (m->gexec) { (void)hipGraphExecDestroy(m->gexec); m->gexec = nullptr; }
-    if (m->gexec_small) { (void)hipGraphExecDestroy(m->gexec_small); m->gexec_small = nullptr; }
+    // a step graph captured with the RCCL node is stale now (the head graph holds no collective: it stays)
+    drop_step_graphs(m, false);
     m->p2p_ready = true;
     return 0;
 }

@@ -154,7 +154,8 @@ int g4r_debug_loss_rows(g4r_model* m, float* scores, int64_t count, int32_t M, f
     mine = saved;
     mine.M_b = M;      // what load_ctx hands the kernel (t_b / g_b: not read by it)
     HIPCHK(hipMemcpy((void*)d.st, &mine, sizeof(mine), hipMemcpyHostToDevice));
-    launch_loss_rows(m, dim3(d.B), false, nullptr, nullptr);
+    StepLauncher lk(m, nullptr);      // (no slot open: untimed, outside G4R_SKIP_KN)
+    launch_loss_rows(lk, dim3(d.B));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
     const hipError_t r = hipMemcpy((void*)d.st, &saved, sizeof(saved), hipMemcpyHostToDevice);

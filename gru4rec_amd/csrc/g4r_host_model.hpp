@@ -32,7 +32,7 @@ static const char* KN_NAMES[KN_COUNT] = {"k_gru_p1", "k_gru_p2", "k_score_fwd", 
 
 struct EvRec { int kn; hipEvent_t a, b; };
 
-// ---- the kernels of a training step: chosen once per model (choose_kernels, at g4r_create), dispatched on by launch_step
+// ---- the kernels of a training step: chosen once per model (choose_kernels, at g4r_create), dispatched on by step_head / step_tail
 // The environment switches that steer the choice, read at g4r_create (tests and A/B runs toggle them between models)
 struct KernelSwitches {
     bool no_lean = false;                 // G4R_NO_LEAN: the fused / LDS-staged kernels the lean launches replaced (tests/test_gpu_lean.py)
@@ -46,6 +46,7 @@ struct KernelSwitches {
     int p2_geo = -1, ba_geo = -1;         // G4R_P2_GEO / G4R_BA_GEO = 0 / 1: the 4-wave / 8-wave geometry of k_gru_p2 / k_gru_bwd_a (-1: the policy)
     int wide2 = -1, p1_ks = 128, bb_ks = 0;      // G4R_WIDE2 (wide-layer kernel mask, -1: the policy), G4R_P1_KS / G4R_BB_KS (their K slices)
     unsigned long long skip_kn = 0;       // G4R_SKIP_KN: measurement aid, bit k = leave the launches of slot k (KN_*) out of the step
+    bool trace = false;                   // G4R_TRACE: every launch of an (eager) step named on stderr and waited for; no step graphs
 };
 // What choose_kernels decided; the debug key `kernels` reports these values.  Tile forms: k_gru_p1* then k_gru_p2; k_gru_bwd_pre,
 // k_gru_bwd_a, then k_onehot_step (layer 0 of a one-hot input) / k_gru_bwd_bw (dy as K-slice partial sums) / k_gru_bwd_b.
@@ -248,6 +249,40 @@ struct g4r_model {
 // every entry that may rewrite Wy / E calls this: the bf16 shadow table of the two-stage top-k and the inverse norms of
 // g4r_similar_items are rebuilt on their next use
 static inline void weights_changed(g4r_model* m) { m->s_tab_valid = false; m->sim_valid[0] = m->sim_valid[1] = false; }
+// the captured step graphs, stale with what they captured (the kernel choice, the collective); the next step that wants one captures
+// it again.  also_head: the head graph (one step's kernels up to the dense gradients) too
+static inline void drop_step_graphs(g4r_model* m, bool also_head) {
+    for (hipGraphExec_t* g : {&m->gexec, &m->gexec_small, also_head ? &m->gexec_head : nullptr})
+        if (g && *g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+}
+
+// ---- how the steps of a model run (g4r_host_step.hpp).  STEP_GRAPH: whole steps replayed from a captured graph, G4R_GRAPH_STEPS at a
+// time.  STEP_HEAD_GRAPH: one step's kernels up to the dense gradients replayed, the tail (all-reduce, dense apply, sparse update)
+// launched eagerly behind them.  STEP_EAGER: every launch from the host (use_graph = 0, per-kernel profiling, G4R_TRACE).
+enum StepMode { STEP_GRAPH, STEP_HEAD_GRAPH, STEP_EAGER };
+// one GPU, staged dense path without a communicator (the generic optimizers: rmsprop / adadelta / adam / plain SGD / grad_cap): no
+// collective in the step, so the whole step is captured like the fused single-GPU step (it used to replay a head graph and launch
+// its tail eagerly)
+static inline bool local_staged(const g4r_model* m) {
+    return !m->dm.apply_dense_inplace && m->cfg.nranks <= 1 && !m->comm_ready && !m->p2p_ready && !m->virtual_ranks;
+}
+// N > 1 (or the one-rank staged mode): the all-reduce is captured with the step, so that a replay covers 16 whole steps
+// (kernels, RCCL all-reduce, dense apply) with no host work in between -- unless an earlier capture with the collective failed
+static inline bool dist_graph_wanted(const g4r_model* m) {
+    return !m->dm.apply_dense_inplace && !m->dist_graph_failed && (m->p2p_ready || m->comm_ready || local_staged(m));
+}
+// The one place that says which: g4r_train_steps asks it for a call's steps (again after a capture that failed: dist_graph_failed),
+// g4r_set_plan for the graphs to capture ahead of the first step.
+static inline StepMode step_mode(const g4r_model* m) {
+    if (!m->cfg.use_graph || m->profiling || m->sw.trace) return STEP_EAGER;
+    return (m->dm.apply_dense_inplace || dist_graph_wanted(m)) ? STEP_GRAPH : STEP_HEAD_GRAPH;
+}
+// the steps a run leaves behind its replays (fewer than the shortest graph holds): on the staged dense path the head graph + eager
+// tail, else eager launches
+static inline StepMode single_step_mode(const g4r_model* m, StepMode mode) {
+    if (mode != STEP_GRAPH) return mode;
+    return m->dm.apply_dense_inplace ? STEP_EAGER : STEP_HEAD_GRAPH;
+}
 
 template <class T>
 static int dalloc(g4r_model* m, T** p, size_t n, bool zero = true) {
@@ -361,6 +396,21 @@ static const size_t SMEM_MT_4S = (size_t)MtCfg<4, true>::SMEM_FLOATS * sizeof(fl
 static const size_t SMEM_T2K = (size_t)(4 * 64 * 16) * sizeof(float);                               // gemm_tile2k: two 16-deep buffers per operand
 static const size_t SMEM_T3 = (size_t)Tile3Cfg<3, 32>::SMEM_FLOATS * sizeof(float);                 // gemm_tile3: ring of three 32-deep stages
 
+// ---- the instantiations of the step's templated kernels, as tables: the launch picks its entry from m->kern, g4r_create walks them for
+// the LDS opt-in.  (hipcc emits device code only for the explicit instantiations of the .cuh files: an entry needs one there.)
+// k_loss_rows<long row, spec, columns per thread>: [0] short rows, one column per thread; [1] short rows, four; [2] long rows (always four)
+static constexpr decltype(&k_loss_rows<false, 0, 1>) K_LOSS_ROWS[3][4] = {
+    {k_loss_rows<false, 0, 1>, k_loss_rows<false, 1, 1>, k_loss_rows<false, 2, 1>, k_loss_rows<false, 3, 1>},
+    {k_loss_rows<false, 0, 4>, k_loss_rows<false, 1, 4>, k_loss_rows<false, 2, 4>, k_loss_rows<false, 3, 4>},
+    {k_loss_rows<true, 0, 4>, k_loss_rows<true, 1, 4>, k_loss_rows<true, 2, 4>, k_loss_rows<true, 3, 4>}};
+static inline auto loss_rows_kernel(const StepKernels& k) { return K_LOSS_ROWS[k.loss_long ? 2 : (k.loss_quads ? 1 : 0)][k.loss_spec]; }
+// [chunks 1 / 2 / 4][momentum]; k_update holds at most two chunks per lane
+static inline int chunk_index(int chunks) { return chunks == 1 ? 0 : (chunks == 2 ? 1 : 2); }
+static constexpr decltype(&k_sparse_update<1, false>) K_SPARSE_UPDATE[3][2] = {
+    {k_sparse_update<1, false>, k_sparse_update<1, true>}, {k_sparse_update<2, false>, k_sparse_update<2, true>}, {k_sparse_update<4, false>, k_sparse_update<4, true>}};
+static constexpr decltype(&k_sparse_update_generic<1>) K_SPARSE_UPDATE_GENERIC[3] = {k_sparse_update_generic<1>, k_sparse_update_generic<2>, k_sparse_update_generic<4>};
+static constexpr decltype(&k_update<1, 32, false>) K_UPDATE[2][2] = {{k_update<1, 32, false>, k_update<1, 32, true>}, {k_update<2, 32, false>, k_update<2, 32, true>}};
+
 // the dense-gradient tiles of the model's GRU weights, TR x TC each (k_dense_grad: 32 x 32, k_dense_grad2: 64 x 64, k_update_l: 16 x 64)
 static std::vector<DenseTile> dense_tiles(const DevModel& d, int TR, int TC) {
     std::vector<DenseTile> tiles;
@@ -385,7 +435,7 @@ static std::vector<DenseTile> dense_tiles(const DevModel& d, int TR, int TC) {
 }
 
 // Which kernel runs each stage of the training step, from the shapes in `d` (d.touched included), the CU count and the switches: every
-// precedence rule written once, for launch_step, the memory plan of g4r_create, the prediction GRU and the debug keys.
+// precedence rule written once, for step_head / step_tail, the memory plan of g4r_create, the prediction GRU and the debug keys.
 static StepKernels choose_kernels(const DevModel& d, int n_cu, const KernelSwitches& sw, bool defer_on) {
     StepKernels k = {};
     const int L = d.n_layers, B = d.B, top = L - 1;

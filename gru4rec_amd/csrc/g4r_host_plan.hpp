@@ -170,7 +170,7 @@ int64_t g4r_build_plan(const int32_t* off, int64_t n_sessions, const int64_t* or
 static int ensure_graph(g4r_model* m);
 static int ensure_head_graph(g4r_model* m);
 static int sync_dense_enqueue(g4r_model* m);
-static int ensure_step_graph(g4r_model* m, bool* whole);
+static int ensure_step_graph(g4r_model* m);
 
 int g4r_set_plan(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, const uint8_t* reset, const int32_t* M,
                  int64_t T, const int64_t* compact_steps, const int32_t* compact_maps, int64_t n_compact) {
@@ -218,10 +218,12 @@ int g4r_set_plan(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, co
     // the captured graph stays valid: kernels read the plan pointers from the device descriptor
     if (sync_dm(m)) return -1;
     // capture + instantiate the step graph now (capturing executes nothing): the first timed steps of a short run must not
-    // pay the ~10 ms of graph construction
-    if (m->cfg.use_graph && !m->profiling && !getenv("G4R_TRACE") && (m->dm.apply_dense_inplace || m->comm_ready || m->p2p_ready)) {
-        bool whole = false;
-        if (ensure_step_graph(m, &whole)) return -1;
+    // pay the ~10 ms of graph construction.  The one exception: a staged dense path with no communicator attached (the one-GPU staged
+    // mode, a rank of several before g4r_comm_init, virtual ranks) captures at its first g4r_train_steps -- not widened here
+    const bool staged_no_comm = !m->dm.apply_dense_inplace && !m->comm_ready && !m->p2p_ready;
+    if (step_mode(m) != STEP_EAGER && !staged_no_comm) {
+        if (ensure_step_graph(m)) return -1;
+        const bool whole = step_mode(m) == STEP_GRAPH;      // (asked again: a capture the collective refused falls back to the head graph)
         hipGraphExec_t ge = whole ? m->gexec : m->gexec_head;
         if (ge) (void)hipGraphUpload(ge, m->stream);
         if (whole && m->gexec_small) (void)hipGraphUpload(m->gexec_small, m->stream);

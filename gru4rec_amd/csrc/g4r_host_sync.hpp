@@ -49,8 +49,7 @@ int g4r_sync_enable(g4r_model* m) {
     // and drop the step graphs captured with k_update_l
     const int was = m->kern.update;
     m->kern = choose_kernels(d, m->n_cu, m->sw, m->defer_on);
-    if (m->kern.update != was)
-        for (hipGraphExec_t* g : {&m->gexec, &m->gexec_small, &m->gexec_head}) if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+    if (m->kern.update != was) drop_step_graphs(m, true);
     return sync_dm(m);
 }
 

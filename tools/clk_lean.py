@@ -19,7 +19,7 @@ for rep in range(5):
     else:
         m.train_steps(200 + rep, 1)
     R = 2 * cfg['batch_size'] + cfg['n_sample']
-    NOWN = min((R + 15) // 16, max(2 * int(m.get_debug('n_cu', (1,))[0]) - cfg['batch_size'], 32))      # owner pre-scan workgroups (launch_step)
+    NOWN = min((R + 15) // 16, max(2 * int(m.get_debug('n_cu', (1,))[0]) - cfg['batch_size'], 32))      # owner pre-scan workgroups (score_forward_and_loss, g4r_host_step.hpp)
     if int(m.get_debug('owner_window', (1,))[0]):
         NOWN = 0      # the owner tables come from k_owner_window, one launch in front of the window
     raw = m.get_debug('dbgclk', (2 * (64 + 8 * R),)).view(np.int64)
