@@ -57,7 +57,10 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            20: "gumbel_noise (g4r_sample_sessions) ignores the decoding step (Philox counter word 2 = 0): every step of a draw gets the "
                "noise of step 0",
            21: "k_owner_window takes the sample-store row of every step of its window from the window's FIRST global step: the owner "
-               "tables of the later steps are those of another list"}
+               "tables of the later steps are those of another list",
+           22: "hidden_act_bwd decides the branch of leaky / elu / selu on the VALUE of the stored candidate (c >= 0), not on its sign bit: "
+               "a pre-activation whose result rounds to -0.0 gets the positive branch's slope",
+           23: "hidden_act_bwd: the negative-branch slope of leaky / elu / selu x 1.01"}
 
 
 def mutant_path(k):

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void k_gru_bwd_pre(const DevModel* __restrict_
     }
     if (m.drop_h > 0.f) dh *= drop_mult(m.seed, (unsigned)c.g, G4R_STREAM_DROP_HIDDEN + l, row, d, 1.0f - m.drop_h);
     const float dz = dh * (cc - hv), dc = dh * zz;
-    m.dV[l][(size_t)row * D3 + d] = dc * act_bwd_from_out(m.hidden_act, m.ha_p0, m.ha_p1, cc);
+    m.dV[l][(size_t)row * D3 + d] = dc * hidden_act_bwd(m.hidden_act, m.ha_p0, m.ha_p1, cc);
     m.dV[l][(size_t)row * D3 + 2 * D + d] = dz * zz * (1.f - zz);
 }
 
@@ -536,7 +536,7 @@ __global__ __launch_bounds__(512) void k_gru_bwd_fused(const DevModel* __restric
                 for (int j = 0; j < 4; ++j) ad[j] = 1.0f - cc[j] * cc[j];
             } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) ad[j] = act_bwd_from_out(hact, hp0, hp1, cc[j]);
+                for (int j = 0; j < 4; ++j) ad[j] = hidden_act_bwd(hact, hp0, hp1, cc[j]);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {

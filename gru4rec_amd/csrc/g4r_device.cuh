@@ -447,3 +447,21 @@ __device__ __forceinline__ float act_bwd_from_out(int kind, float p0, float p1, 
         default: return 1.0f;
     }
 }
+// The hidden layers' derivative da / dc, from the candidate c[l] the forward stored: the one place k_gru_da, k_gru_bwd_fused and
+// k_gru_bwd_pre take it from (their tanh fast paths stay in the kernels).  The product build is act_bwd_from_out under another name.
+// Test builds (tests/test_gpu_mutation.py, tests/test_gpu_hidden_act.py): G4R_MUTATE=22 decides the branch of leaky / elu / selu on the
+// VALUE of c (c >= 0) instead of its sign bit -- wrong exactly where the forward returned -0.0; =23 puts a factor 1.01 on their
+// negative-branch slope.
+__device__ __forceinline__ float hidden_act_bwd(int kind, float p0, float p1, float c) {
+#if defined(G4R_MUTATE) && G4R_MUTATE == 22
+    if (kind == G4R_ACT_LEAKY || kind == G4R_ACT_ELU || kind == G4R_ACT_SELU) {
+        const bool pos = c >= 0.0f;
+        return kind == G4R_ACT_LEAKY ? (pos ? 1.0f : p0) : kind == G4R_ACT_ELU ? (pos ? 1.0f : c + p0) : (pos ? p0 : c + p0 * p1);
+    }
+#endif
+#if defined(G4R_MUTATE) && G4R_MUTATE == 23
+    if ((kind == G4R_ACT_LEAKY || kind == G4R_ACT_ELU || kind == G4R_ACT_SELU) && (__builtin_bit_cast(unsigned, c) >> 31))
+        return act_bwd_from_out(kind, p0, p1, c) * 1.01f;
+#endif
+    return act_bwd_from_out(kind, p0, p1, c);
+}

@@ -421,7 +421,7 @@ __global__ __launch_bounds__(128) void k_gru_da(const LeanDa* __restrict__ ap, c
         for (int u = 0; u < 4; ++u) ad[u] = 1.0f - cc[u] * cc[u];
     } else {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) ad[u] = act_bwd_from_out(a.hidden_act, a.ha_p0, a.ha_p1, cc[u]);
+        for (int u = 0; u < 4; ++u) ad[u] = hidden_act_bwd(a.hidden_act, a.ha_p0, a.ha_p1, cc[u]);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {

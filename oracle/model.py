@@ -467,6 +467,7 @@ class OracleGRU4Rec:
             dzp = dz * z * (1 - z)
             dWrz = H.T @ np.hstack([drp, dzp])
             dV = np.hstack([da, drp, dzp]).astype(self.dtype)
+            cch['dV'] = dV                    # debug dump: [da | dr' | dz'], what the backward kernels leave in dV<l>
             dBh = dV.sum(axis=0)
             if self.onehot and i == 0:
                 dWx, dy = None, dV            # the gathered rows of Wx[0] receive dV itself (sparse update below)

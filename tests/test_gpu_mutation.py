@@ -17,6 +17,11 @@ mutant; every one of those runs has to come back red, and the tensor it names ha
             of a four-column case of test_gpu_loss_rows.py; the M = 36 run of the same case passes
   mutant 19 k_loss_rows' first pass starts its loop past the prefetched groups one STEP late -> ds at N = 12301; N = 4099 (no such
             trip) passes
+  mutant 22 hidden_act_bwd decides the branch of leaky / elu / selu on the VALUE of the stored candidate c, not on its sign bit -> dV (da)
+            of the sign-bit cases of test_gpu_hidden_act.py for elu and selu, lean (k_gru_da) and wide (k_gru_bwd_pre); leaky (p0 * a is
+            not zero) and the one-step cases of every activation pass
+  mutant 23 hidden_act_bwd's negative-branch slope of leaky / elu / selu x 1.01 -> dV0 (da) and dWx0 of their one-step cases, lean and
+            wide; the tanh and relu rows pass
 
 (Round 2's `atol = 1e-4` on every tensor let an accumulator that is wrong by 100 x pass.)  The same selection runs green on the
 product library in the ordinary suite."""
@@ -146,6 +151,62 @@ def test_mutant_19_turns_the_first_trip_past_the_prefetch_red(mutants, tmp_path)
     assert state['elubm q12301 M=37 ds'], state
     r, state = _child(mutants[19], 'tests/test_gpu_loss_rows.py::test_loss_rows[elubm-q4099]', str(tmp_path / 'm19b.txt'))
     assert r.returncode == 0, 'mutant 19 on N = 4099: rc %d\n%s' % (r.returncode, (r.stdout + r.stderr)[-3000:])
+
+
+HIDDEN = 'tests/test_gpu_hidden_act.py::'
+HIDDEN_FAMILIES = ('lean', 'wide_w4')      # a k_gru_da site and a k_gru_bwd_pre site
+HIDDEN_ACTS = ('tanh', 'relu', 'linear', 'leaky-0.2', 'elu-0.5', 'selu-1.0507-1.6733')
+
+
+def _hidden_children(lib, ids, rep):
+    """The test ids of tests/test_gpu_hidden_act.py in one child process on library `lib`: (return code, output, per test -- in the
+    order of its `--- hidden_act ...` header in the report -- {report line name: failed})."""
+    env = dict(os.environ, G4R_LIB=lib, G4R_PARITY_REPORT=rep)
+    r = subprocess.run([sys.executable, '-m', 'pytest'] + [HIDDEN + i for i in ids] + ['-q', '-p', 'no:cacheprovider'], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=900)
+    sections = {}
+    for ln in (open(rep).read().splitlines() if os.path.exists(rep) else []):
+        if ln.startswith('--- hidden_act'):
+            cur = sections.setdefault(ln.split(':')[0], {})
+        elif 'worst/tol' in ln:
+            cur[ln[:28].strip()] = ln.rstrip().endswith('FAIL')
+    return r.returncode, (r.stdout + r.stderr)[-3000:], sections
+
+
+def _one_step_ids():
+    return ['test_one_step_against_the_float64_oracle[%s-%s-bprmax-dh0.00]' % (f, a) for f in HIDDEN_FAMILIES for a in HIDDEN_ACTS]
+
+
+def test_mutant_22_turns_the_sign_bit_cases_red(mutants, tmp_path):
+    """The branch decided on c >= 0: where the forward returned -0.0 (elu / selu of a = -1e-9) the backward takes the positive slope.  The
+    sign-bit cases of elu and selu must fail on da, at a k_gru_da site (lean) and at a k_gru_bwd_pre site (wide); leaky, whose p0 * a
+    is not zero, and the one-step cases of every activation (no candidate rounds to zero there) must pass."""
+    ids = ['test_branch_travels_in_the_sign_bit_of_the_stored_candidate[%s-%s]' % (f, a) for f in HIDDEN_FAMILIES
+           for a in ('elu-0.5', 'selu-1.0507-1.6733', 'leaky-0.2')]
+    rc, out, sec = _hidden_children(mutants[22], ids, str(tmp_path / 'm22c.txt'))
+    assert rc == 1, 'mutant 22 on the sign-bit cases: rc %d\n%s' % (rc, out)
+    for f in HIDDEN_FAMILIES:
+        for a in ('elu-0.5', 'selu-1.0507-1.6733'):
+            assert sec['--- hidden_act sign bit %s %s' % (f, a)]['sb dV0 da'], (f, a, sec)
+        assert not any(sec['--- hidden_act sign bit %s leaky-0.2' % f].values()), (f, sec)
+    rc, out, sec = _hidden_children(mutants[22], _one_step_ids(), str(tmp_path / 'm22a.txt'))
+    assert rc == 0, 'mutant 22 on the one-step cases: rc %d\n%s' % (rc, out)
+    assert len(sec) == len(HIDDEN_FAMILIES) * len(HIDDEN_ACTS), sorted(sec)
+
+
+def test_mutant_23_turns_the_negative_slope_red(mutants, tmp_path):
+    """The negative-branch slope of leaky / elu / selu x 1.01: their one-step cases must fail on dV0 (da) and on dWx0, lean and wide; the
+    tanh and relu rows (and linear) must pass."""
+    rc, out, sec = _hidden_children(mutants[23], _one_step_ids(), str(tmp_path / 'm23.txt'))
+    assert rc == 1, 'mutant 23 on the one-step cases: rc %d\n%s' % (rc, out)
+    for f in HIDDEN_FAMILIES:
+        for a in HIDDEN_ACTS:
+            state = sec['--- hidden_act one step %s-%s-bprmax-dh0.00' % (f, a)]
+            if a in ('tanh', 'relu', 'linear'):
+                assert not any(state.values()), (f, a, state)
+            else:
+                assert state['ha dV0 da'] and state['ha dWx0'], (f, a, state)
+                assert not state['ha r0'] and not state['ha z0'] and not state['ha c0'] and not state['ha dV0 dzp'], (f, a, state)
 
 
 def test_product_library_is_not_a_mutant():
