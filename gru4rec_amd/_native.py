@@ -19,6 +19,7 @@ G4R_STREAM_GUMBEL = 0x47554D42      # Philox stream id (counter word 3) of its n
 BEAM_COMBINE = {'sum': 0, 'product': 1}      # G4R_BEAM_*
 G4R_EXCLUDE_MAX = 1024  # most distinct items one row of g4r_recommend_step_filtered may exclude
 G4R_CAND_MAX = 2 ** 31 - 256  # most candidate positions of one g4r_score_candidates* call
+G4R_DIVERSIFY_POOL_MAX = 128  # largest pool of g4r_diversify_lists / g4r_diversify_sessions
 G4R_SCAN_CAND_MAX = 1024  # most candidates per row (k * oversample) of g4r_recommend_step_scan / g4r_recommend_sessions_scan
 LOSS_IDS = {'cross-entropy': 0, 'bpr-max': 1, 'top1-max': 2, 'bpr': 3, 'top1': 4, 'xe_logit': 5}
 ACT_IDS = {'linear': 0, 'relu': 1, 'tanh': 2, 'leaky': 3, 'elu': 4, 'selu': 5, 'softmax': 6, 'softmax_logit': 7}
@@ -52,7 +53,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_debug_gumbel', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -138,6 +139,9 @@ def lib():
                                       i32p, f32p, f32pp]
     L.g4r_scan_table_release.argtypes = [vp]
     L.g4r_similar_items.argtypes = [vp, i32, i32, i32p, i64, i32p, i64, i32, i32, u32p, i32p, f32p]
+    L.g4r_diversify_lists.argtypes = [vp, i32, i32, i32p, f32p, i64, i32, i32, C.c_float, i32, i32p, f32p]
+    L.g4r_diversify_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i64p, i32p, u32p, i32, i32, C.c_float, i32,
+                                         i32p, f32p, i32p, f32p, f32pp]
     L.g4r_score_candidates.argtypes = [vp, i32p, i32, i64p, i32p, i32, f32p, i32p]
     L.g4r_score_candidates_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i64p, i32p, i32, f32p, i32p, f32pp]
     L.g4r_rank_targets.argtypes = [vp, i32p, i32, i64, i32, f32p]
@@ -628,6 +632,37 @@ class Model:
         _chk(lib().g4r_similar_items(self.h, SIM_SPACES[space], SIM_METRICS[metric], _i32(qi), len(qi), _i32(it), n_sel, k,
                                      1 if exclude_self else 0, _u32(mask), _i32(cols), _f32(scores)))
         return cols, scores
+
+    def diversify_lists(self, items, rel, k, lam=0.7, metric='cosine', space='output', normalize=True):
+        """k of every row's P candidates picked by maximal marginal relevance (g4r_diversify_lists; stateless): items int32[n, P]
+        (item indices), rel float32[n, P] -> (pos int32[n, k] positions in the row's list, values float32[n, k]), pick by pick."""
+        it = np.ascontiguousarray(items, dtype=np.int32)
+        rl = np.ascontiguousarray(rel, dtype=np.float32)
+        if it.ndim != 2 or it.shape != rl.shape:
+            raise ValueError('items and rel must be two arrays of one shape [n, P]')
+        n, P = it.shape
+        pos, values = _topk_out((n, k))
+        _chk(lib().g4r_diversify_lists(self.h, SIM_SPACES[space], SIM_METRICS[metric], _i32(it), _f32(rl), n, P, k, float(lam),
+                                       1 if normalize else 0, _i32(pos), _f32(values)))
+        return pos, values
+
+    def diversify_sessions(self, hist_offs, hist_items, item_idx=None, k=20, pool=100, lam=0.7, metric='cosine', space='output',
+                           normalize=True, excl_offs=None, excl_items=None, excl_mask=None, hidden=None, return_hidden=False,
+                           oversample=None):
+        """recommend_sessions with k = pool followed on the device by diversify_lists over every session's pool
+        (g4r_diversify_sessions): (cols int32[n, k], scores float32[n, k], pos int32[n, k], values float32[n, k]) in pick order, + the
+        hidden states with return_hidden=True.  The other arguments as in recommend_sessions."""
+        offs, hi, n = _hist(hist_offs, hist_items)
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        xo, xi, mask = _excl(n, excl_offs, excl_items, excl_mask, self.cfg.n_items, 'n')
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        hout, houtp = _hidden_out(n, self.layers, return_hidden)
+        cols, scores = _topk_out((n, k))
+        pos, values = _topk_out((n, k))
+        _chk(lib().g4r_diversify_sessions(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, k, pool, 0 if oversample is None else int(oversample),
+                                          _i64(xo), _i32(xi), _u32(mask), SIM_SPACES[space], SIM_METRICS[metric], float(lam),
+                                          1 if normalize else 0, _i32(cols), _f32(scores), _i32(pos), _f32(values), houtp))
+        return (cols, scores, pos, values, hout) if return_hidden else (cols, scores, pos, values)
 
     def sim_norms(self):
         """State of the inverse-norm cache of similar_items: (bytes held, valid, builds so far)."""

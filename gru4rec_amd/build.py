@@ -60,7 +60,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
                "tables of the later steps are those of another list",
            22: "hidden_act_bwd decides the branch of leaky / elu / selu on the VALUE of the stored candidate (c >= 0), not on its sign bit: "
                "a pre-activation whose result rounds to -0.0 gets the positive branch's slope",
-           23: "hidden_act_bwd: the negative-branch slope of leaky / elu / selu x 1.01"}
+           23: "hidden_act_bwd: the negative-branch slope of leaky / elu / selu x 1.01",
+           24: "k_mmr_rerank (g4r_diversify_*): from the second update on, a position's largest similarity to the picks is OVERWRITTEN by "
+               "its similarity to the last pick instead of max-ed with it"}
 
 
 def mutant_path(k):

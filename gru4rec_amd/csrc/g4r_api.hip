@@ -21,6 +21,7 @@
 #include "g4r_sample_kernels.cuh"
 #include "g4r_scan_kernels.cuh"
 #include "g4r_sim_kernels.cuh"
+#include "g4r_mmr_kernels.cuh"
 #include "g4r_sync_kernels.cuh"
 #include "g4r_micro_kernels.cuh"
 #include "g4r_wide_kernels.cuh"
@@ -41,6 +42,7 @@ extern "C" {
 #include "g4r_host_sample.hpp"
 #include "g4r_host_events.hpp"
 #include "g4r_host_similar.hpp"
+#include "g4r_host_diversify.hpp"
 #include "g4r_host_comm.hpp"
 #include "g4r_host_sync.hpp"
 #include "g4r_host_debug.hpp"

@@ -326,6 +326,7 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
         (const void*)k_score_store, (const void*)k_score_count, (const void*)k_topk_fused, (const void*)k_topk_stored, (const void*)k_topk_fused_x,
         (const void*)k_topk_stored_x, (const void*)k_topk_fused_g, (const void*)k_topk_stored_g, (const void*)k_topk_sample, (const void*)k_topk_rank,
         (const void*)k_topk_rank_x, (const void*)k_topk_stored_ev, (const void*)k_sim_range<false>, (const void*)k_sim_range<true>,
+        (const void*)k_mmr_rerank<false>, (const void*)k_mmr_rerank<true>,
         (const void*)k_scan_bf16<2>, (const void*)k_scan_bf16<4>, (const void*)k_scan_bf16<8>, (const void*)k_scan_bf16<2, TkGrow>,
         (const void*)k_scan_bf16<4, TkGrow>, (const void*)k_scan_bf16<8, TkGrow>};
     auto opt_in = [&](const void* kern) { return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, big); };

@@ -211,6 +211,10 @@ struct g4r_model {
     int64_t sim_builds = 0;
     DevBuf<int> sim_q;
     DevBuf<float> sim_rows;                      // [chunk rows][W] the chunk's query rows (k_sim_gather)
+    // diversified top-k (g4r_diversify_lists / _sessions; k_mmr_rerank): a chunk's supplied lists [rows][P] and its picks [rows][k] --
+    // position, value and, after a session selection, the picked candidates' columns and model scores
+    DevBuf<int> dv_items, dv_pos, dv_cols;
+    DevBuf<float> dv_rel, dv_val, dv_scores;
     unsigned tie_ctr = 0;                       // evaluation step counter of the 'tiebreaking' noise stream
     // the last g4r_recommend_events call (g4r_get_debug "events_launches"): its steps, the launches whose grid spans the candidate
     // columns, all its launches, the pieces its lists came back in
@@ -244,6 +248,16 @@ struct g4r_model {
     Scratch sc_ids, sc_blk, sc_cnt, sc_all, sc_send, sc_pack, sc_recv, sc_hall;      // sc_hall: pinned host copy of the gathered id lists
     float* d_dense[2] = {nullptr, nullptr};      // dense reconciliation buffers [n_items][sum of plane widths + 1] per table group (small catalogues)
     bool sync_on = false;
+};
+
+// The optional stage behind sessions_run's selection (g4r_diversify_sessions; g4r_host_diversify.hpp): k_mmr_rerank picks k of the
+// `pool` the selection left in p_tcols / p_tscores, and the chunk downloads the picks instead of the pool
+struct MmrStage {
+    int tab; const float* T; int W;      // the item table (sim_table)
+    bool cosine;
+    float lam; int normalize;
+    int k;                               // picks per row
+    int32_t* out_pos; float* out_value;  // host, [n][k] next to sessions_run's out_cols / out_scores
 };
 
 // every entry that may rewrite Wy / E calls this: the bf16 shadow table of the two-stage top-k and the inverse norms of

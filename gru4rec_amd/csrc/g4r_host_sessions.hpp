@@ -159,10 +159,14 @@ static int no_repeat_check(g4r_model* m, const int32_t* item_idx, int64_t n_sel)
 // steps >= 1 (g4r_continue_sessions): that selection followed, per chunk and on the device, by steps - 1 rounds of (winner -> GRU
 // input -> GRU step -> selection); k_rollout_feed files every step's lists in ro_cols / ro_scores and, with no_repeat, adds the winner
 // to the row's exclusion list.  One synchronisation and one download per chunk whatever `steps` is.
+// mmr (g4r_diversify_sessions; steps = 0, k = the pool): k_mmr_rerank picks mmr->k of every row's k selected candidates on the device
+// and the chunk downloads those picks (columns, scores, pool positions, values) instead of the lists.  NULL: nothing is added.
+static int mmr_prepare(g4r_model* m, const MmrStage& st, int rows);
+static int mmr_enqueue(g4r_model* m, const MmrStage& st, int rows, int pool, const int* d_items, int64_t n_sel);
 static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
                         const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample, int32_t steps, int32_t no_repeat,
                         const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask, int32_t* out_cols,
-                        float* out_scores, float* const* out_hidden) {
+                        float* out_scores, float* const* out_hidden, const MmrStage* mmr = nullptr) {
     // ---- every check before any kernel is launched.  cand_upload, among them, stages the candidate items (it may drain the stream, grow
     // p_items and enqueue the copy), and the no_repeat and excl_pack refusals come after it: nothing here has state to advance
     int32_t scan_c = 0;
@@ -188,12 +192,15 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
     const bool sm = is_softmax(d);
     const int64_t ldo = (n_sel + 3) & ~3LL;
     if (sm && m->r_scores.reserve(m, (int64_t)C * ldo)) return -1;
-    const int64_t per_row = (int64_t)n_step * k;
+    const int64_t per_row = mmr ? mmr->k : (int64_t)n_step * k;      // entries a row downloads
+    if (mmr && mmr_prepare(m, *mmr, C)) return -1;
     if (rollout && (m->ro_cols.reserve(m, (int64_t)C * per_row) || m->ro_scores.reserve(m, (int64_t)C * per_row) || m->ro_in.reserve(m, (int64_t)C) ||
                     (grow && m->ro_xlen.reserve(m, (int64_t)C))))
         return -1;
     std::vector<int32_t> tcols((size_t)C * per_row);
     std::vector<float> tscores((size_t)C * per_row);
+    std::vector<int32_t> tpos(mmr ? (size_t)C * per_row : 0);
+    std::vector<float> tval(mmr ? (size_t)C * per_row : 0);
     std::vector<long long> coffs;
     std::vector<int32_t> citems, clen;
     const GruBufs rb = replay_bufs(m);
@@ -234,8 +241,13 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
             }
         }
         final_half = steps > 1 ? ((T + steps - 1) & 1) : -1;
-        HIPCHK(hipMemcpyAsync(tcols.data(), rollout ? m->ro_cols.p : m->p_tcols.p, (size_t)Cc * per_row * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipMemcpyAsync(tscores.data(), rollout ? m->ro_scores.p : m->p_tscores.p, (size_t)Cc * per_row * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        if (mmr) {
+            if (mmr_enqueue(m, *mmr, Cc, k, d_items, n_sel)) return -1;
+            HIPCHK(hipMemcpyAsync(tpos.data(), m->dv_pos.p, (size_t)Cc * per_row * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+            HIPCHK(hipMemcpyAsync(tval.data(), m->dv_val.p, (size_t)Cc * per_row * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        }
+        HIPCHK(hipMemcpyAsync(tcols.data(), mmr ? m->dv_cols.p : rollout ? m->ro_cols.p : m->p_tcols.p, (size_t)Cc * per_row * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(tscores.data(), mmr ? m->dv_scores.p : rollout ? m->ro_scores.p : m->p_tscores.p, (size_t)Cc * per_row * sizeof(float), hipMemcpyDeviceToHost, m->stream));
         return 0;
     };
     // sorted row r is session c0 + perm[r]
@@ -243,6 +255,10 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
         for (int r = 0; r < Cc; ++r) {
             memcpy(out_cols + (size_t)(c0 + perm[r]) * per_row, tcols.data() + (size_t)r * per_row, (size_t)per_row * sizeof(int32_t));
             memcpy(out_scores + (size_t)(c0 + perm[r]) * per_row, tscores.data() + (size_t)r * per_row, (size_t)per_row * sizeof(float));
+            if (mmr) {
+                memcpy(mmr->out_pos + (size_t)(c0 + perm[r]) * per_row, tpos.data() + (size_t)r * per_row, (size_t)per_row * sizeof(int32_t));
+                memcpy(mmr->out_value + (size_t)(c0 + perm[r]) * per_row, tval.data() + (size_t)r * per_row, (size_t)per_row * sizeof(float));
+            }
         }
     };
     return replay_chunks(m, hist_offs, hist_items, n, C, h0, out_hidden, score, done, &final_half);

@@ -1410,6 +1410,108 @@ class GRU4Rec:
         bit: the whole n_items x n_items product is scored and selected on the device in chunks of rows, and only the lists return."""
         return self.similar_items(self.itemidmap.index.values, k=k, metric=metric, space=space, exclude=exclude)
 
+    # ------------------------------------------------------------------ diversified top-k (not in the reference)
+    def _mmr_args(self, trade_off, metric, space):
+        """The checks diversify_sessions and diversify_lists share; the trade-off as the float32 the device uses."""
+        try:
+            ok = not isinstance(trade_off, bool) and 0.0 <= float(trade_off) <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('trade_off = %r: it must be a number in [0, 1]' % (trade_off,))
+        if metric not in _native.SIM_METRICS:
+            raise ValueError("metric = %r: it must be 'cosine' or 'dot'" % (metric,))
+        if space not in _native.SIM_SPACES:
+            raise ValueError("space = %r: it must be 'output' or 'input'" % (space,))
+        if space == 'input' and not self.constrained_embedding and not self.embedding:
+            raise NotImplementedError("space='input': a one-hot input model has no input embedding (layer 0 reads a row of Wx per item, "
+                                      "three gates wide); use space='output'")
+        return float(np.float32(trade_off))
+
+    def diversify_sessions(self, histories, k=20, pool=100, trade_off=0.7, metric='cosine', space='output', normalize=True,
+                           predict_for_item_ids=None, exclude_history=False, exclude=None, exclude_per_row=None, hidden=None,
+                           return_hidden=False, scan='fp32', oversample=8, return_details=False):
+        """Diversified top-k next items of N whole sessions in one stateless call: (item_ids[N, k], scores[N, k] float32).  Not in
+        the reference.  Maximal marginal relevance: the pool of a session is what recommend_sessions(k=pool) returns for it with the
+        same histories, candidates, exclusions, hidden and scan arguments; k of the pool are picked greedily on the device, each pick
+        the position with the largest
+
+            trade_off * r_j - (1 - trade_off) * max over the picks so far of sim(pick -> j)
+
+          r_j         the pool score, with normalize rescaled to [0, 1] over the pool: (s_j - lo) / (hi - lo), 0 when all are equal;
+          sim         similar_items' score of the pair (metric, space as there), bit for bit;
+          trade_off   1: relevance alone -- recommend_sessions(k) exactly; 0: the best item, then the items least similar to the picks.
+        Equal values go to the lower pool position; all arithmetic is fp32 in a fixed order (include/gru4rec_hip.h), so the result
+        equals the host loop over recommend_sessions and similar_items it replaces.  The returned scores are the model's scores of
+        the chosen items -- recommend_sessions' bit patterns -- in pick order, so they need not descend.  return_hidden appends the
+        hidden state as in recommend_sessions; return_details appends (pool_pos[N, k] int32, values[N, k] float32): every pick's
+        position in the pool and the value it won with.  Only N x k entries leave the device; the prediction state is neither read
+        nor changed.  Everything is checked before any device work: ValueError for a k outside [1, pool], a pool outside
+        [1, min(number of candidates, G4R_DIVERSIFY_POOL_MAX = 128)], a trade_off outside [0, 1], a bad metric or space, and
+        recommend_sessions' own refusals with k = pool (every session needs `pool` eligible candidate positions); KeyError for an
+        unknown item id; NotImplementedError for space='input' on a one-hot input model."""
+        if self.error_during_train:
+            raise Exception
+        pool = _check_k(pool, self._n_candidates(predict_for_item_ids), name='pool', cap=_native.G4R_DIVERSIFY_POOL_MAX)
+        k = self._mmr_k(k, pool)
+        lam = self._mmr_args(trade_off, metric, space)
+        over = self._scan_oversample(scan, oversample, pool)
+        N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
+        iidx, cand = self._candidates(predict_for_item_ids)
+        excl = self._session_exclusions(N, lens, hidx, pool, iidx, exclude_history, exclude, exclude_per_row)
+        m = self._ensure_model()
+        out = m.diversify_sessions(offs, hidx, iidx, k, pool, lam, metric, space, bool(normalize), *excl, hidden=h0,
+                                   return_hidden=return_hidden, **_scan_kw(over))
+        res = (cand[out[0]], out[1])
+        if return_hidden:
+            res += (self._unpad_hidden(out[4]),)
+        if return_details:
+            res += (out[2], out[3])
+        return res
+
+    @staticmethod
+    def _mmr_k(k, pool):
+        try:
+            ok = not isinstance(k, bool) and int(k) == k and 1 <= k <= pool
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('k = %r: it must be an integer in [1, pool = %d]' % (k, pool))
+        return int(k)
+
+    def diversify_lists(self, item_lists, relevance, k, trade_off=0.7, metric='cosine', space='output', normalize=True):
+        """The re-ranker of diversify_sessions for lists from any source (score_candidates, another model, a retrieval stage):
+        (pos[N, k] int32, values[N, k] float32).  Not in the reference.
+
+          item_lists  [N, P] item ids, 1 <= P <= G4R_DIVERSIFY_POOL_MAX = 128; duplicates allowed, every position is a candidate.
+          relevance   [N, P] finite numbers (taken as float32), the relevance of every position.
+        Row i picks k of its P positions as diversify_sessions picks from a pool (same arithmetic, same tie rule: the lower
+        position); pos holds the picked positions in pick order, values what each pick won with.  Stateless.  Everything is checked
+        before any device work: ragged lists, shapes that differ, a P or k out of range, a relevance that is not finite, a bad
+        trade_off, metric or space raise ValueError, an unknown item id KeyError, space='input' on a one-hot input model
+        NotImplementedError."""
+        if self.error_during_train:
+            raise Exception
+        try:
+            ids = np.asarray(item_lists)
+            rel = np.asarray(relevance, dtype=np.float64)
+        except (TypeError, ValueError):
+            ids = rel = None
+        if ids is None or ids.dtype == object or ids.ndim != 2 or rel.shape != ids.shape or ids.shape[0] < 1:
+            raise ValueError('item_lists and relevance must be two [N, P] arrays of one shape, N >= 1 (ragged lists are not supported)')
+        P = ids.shape[1]
+        if not 1 <= P <= _native.G4R_DIVERSIFY_POOL_MAX:
+            raise ValueError('the lists hold P = %d items: between 1 and G4R_DIVERSIFY_POOL_MAX = %d are needed' % (P, _native.G4R_DIVERSIFY_POOL_MAX))
+        k = self._mmr_k(k, P)
+        lam = self._mmr_args(trade_off, metric, space)
+        with np.errstate(over='ignore'):      # (a double beyond float32's range becomes inf, which is refused below)
+            rel32 = rel.astype(np.float32)
+        if not np.isfinite(rel32).all():
+            raise ValueError('relevance holds a value that is not finite (as float32)')
+        idx = self.itemidmap[ids.ravel()].values.astype(np.int32).reshape(ids.shape)
+        m = self._ensure_model()
+        return m.diversify_lists(idx, rel32, k, lam, metric, space, bool(normalize))
+
     def symbolic_predict(self, X, Y, M, items, batch_size):
         raise NotImplementedError('symbolic_predict builds a Theano graph (gru4rec.py:729-741); the MI355X path '
                                   'exposes the same computation through gru4rec_amd.evaluation.evaluate_gpu')

@@ -334,6 +334,43 @@ int g4r_sample_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* h
 int g4r_similar_items(g4r_model* m, int32_t space, int32_t metric, const int32_t* q_idx, int64_t n, const int32_t* item_idx,
                       int64_t n_sel, int32_t k, int32_t exclude_self, const uint32_t* excl_mask, int32_t* out_cols, float* out_scores);
 
+/* not in the reference: diversified top-k by maximal marginal relevance (MMR) -- k of a row's pool of P candidates picked greedily,
+ * each pick trading the candidate's relevance against its largest similarity to the picks before it.  A row's pool is the positions
+ * 0 .. P - 1 with item indices c_j and relevance s_j; position order is the tie order.  Every operation below is IEEE fp32, in this
+ * order, never contracted into an FMA; lam is a float in [0, 1] and mu = 1.0f - lam.
+ *   relevance   normalize == 0: r_j = s_j.  Otherwise, with lo / hi the minimum / maximum of the row's s (NaN entries skipped):
+ *               r_j = (s_j - lo) / (hi - lo) when hi > lo, else every r_j = 0.0f.
+ *   similarity  sim(i -> j) is g4r_similar_items' score of the pair (query item c_i, candidate item c_j) in the same space and
+ *               metric, bit for bit: one ascending chain of dot products from zero, for G4R_SIM_COSINE (dot * inv[c_i]) * inv[c_j]
+ *               with the cached inverse norms; a zero row gives 0.
+ *   pick 0      v_j = lam * r_j over all positions.
+ *   pick t >= 1 with i the position picked last, for every position j not picked yet: m_j = sim(i -> j) when t == 1, otherwise
+ *               m_j = sim(i -> j) > m_j ? sim(i -> j) : m_j; v_j = (lam * r_j) - (mu * m_j): two rounded products, one rounded
+ *               subtraction.
+ *   selection   the largest v_j in g4r_recommend_step's order: value descending, the lower position first, NaN last.
+ * out_pos / out_value[n * k] receive, pick by pick, the position in the pool and v.  1 <= k <= P <= G4R_DIVERSIFY_POOL_MAX.
+ *
+ * g4r_diversify_lists re-ranks n supplied lists: items[n * P] (item indices, duplicates allowed) and rel[n * P] (finite).  Stateless.
+ * Everything is checked before any launch: k and P, the item indices, lam in [0, 1] (NaN refused), finite rel, space and metric as
+ * in g4r_similar_items (a one-hot input model has no G4R_SPACE_INPUT).  Rows are processed in chunks, one synchronisation each.
+ *
+ * g4r_diversify_sessions takes the arguments of g4r_recommend_sessions_scan with k = pool (oversample = 0: the exact selection of
+ * g4r_recommend_sessions; otherwise the bf16 scan with pool * oversample <= G4R_SCAN_CAND_MAX): the pool of session i is what that
+ * call returns for it, positions in its order, s = its scores, the columns mapped to items through item_idx.  The selection stays
+ * on the device; out_cols / out_scores[n * k] receive the picked candidates' columns (positions in item_idx, item indices when it
+ * is NULL) and their model scores -- g4r_recommend_sessions' bit patterns -- in pick order, out_pos / out_value as above, out_hidden
+ * as there.  Only n * k entries of each come back, once per chunk of rows.  The checks are those of g4r_recommend_sessions(_scan)
+ * with k = pool (so every session needs `pool` eligible candidate positions) plus the ones above; a pool score that is not finite
+ * follows the arithmetic and the order above, with no special case.  The prediction state is neither read nor changed. */
+#define G4R_DIVERSIFY_POOL_MAX 128
+int g4r_diversify_lists(g4r_model* m, int32_t space, int32_t metric, const int32_t* items, const float* rel, int64_t n, int32_t P,
+                        int32_t k, float lam, int32_t normalize, int32_t* out_pos, float* out_value);
+int g4r_diversify_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                           const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t pool, int32_t oversample,
+                           const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask, int32_t space,
+                           int32_t metric, float lam, int32_t normalize, int32_t* out_cols, float* out_scores, int32_t* out_pos,
+                           float* out_value, float* const* out_hidden);
+
 /* not in the reference: scores of per-row candidate lists (the re-ranking stage behind a retrieval stage).  Row r's list is the
  * item indices cand_items[cand_offs[r] .. cand_offs[r + 1]) (at least one; cand_offs rises strictly; duplicates allowed, every
  * position is scored), at most G4R_CAND_MAX positions in all.  g4r_score_candidates advances the prediction state exactly as
