@@ -53,8 +53,8 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
-    'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_debug_gumbel', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
+    'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_debug_gumbel', 'g4r_debug_lse_terms', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
 ]
@@ -62,6 +62,7 @@ SYMBOLS = [
 # the pointer types of the ABI
 f32p, f64p, i32p, i64p, u8p, u32p = (C.POINTER(t) for t in (C.c_float, C.c_double, C.c_int32, C.c_int64, C.c_uint8, C.c_uint32))
 f32pp = C.POINTER(f32p)      # one float array per layer
+u64p = C.POINTER(C.c_uint64)
 
 _lib = None
 
@@ -137,6 +138,8 @@ def lib():
                                     f32p, f32p, i32p]
     L.g4r_sample_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i64p, i32p, u32p, i32, i32, C.c_float, C.c_uint64, i32,
                                       i32p, f32p, f32pp]
+    L.g4r_sample_sessions_lp.argtypes = L.g4r_sample_sessions.argtypes + [C.c_float, f32p]
+    L.g4r_session_log_partition.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i64p, i32p, u32p, C.c_float, f32p, u64p]
     L.g4r_scan_table_release.argtypes = [vp]
     L.g4r_similar_items.argtypes = [vp, i32, i32, i32p, i64, i32p, i64, i32, i32, u32p, i32p, f32p]
     L.g4r_diversify_lists.argtypes = [vp, i32, i32, i32p, f32p, i64, i32, i32, C.c_float, i32, i32p, f32p]
@@ -169,6 +172,7 @@ def lib():
     L.g4r_get_debug.argtypes = [vp, C.c_char_p, f32p, i64]
     L.g4r_debug_loss_rows.argtypes = [vp, f32p, i64, i32, f32p]
     L.g4r_debug_gumbel.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, i32p, i64, f32p]
+    L.g4r_debug_lse_terms.argtypes = [vp, f32p, f32p, i64, C.c_float, u64p]
     L.g4r_selftest_mfma.argtypes = [f32p]
     L.g4r_stress_start.argtypes = [i32, i64, i32, C.POINTER(vp)]
     L.g4r_stress_stop.argtypes = [vp]
@@ -199,7 +203,7 @@ def _ptr(ptr):
     return lambda a: None if a is None else a.ctypes.data_as(ptr)
 
 
-_f32, _f64, _i32, _i64, _u8, _u32 = (_ptr(t) for t in (f32p, f64p, i32p, i64p, u8p, u32p))
+_f32, _f64, _i32, _i64, _u8, _u32, _u64 = (_ptr(t) for t in (f32p, f64p, i32p, i64p, u8p, u32p, u64p))
 
 
 # -- the argument families of the inference entries.  Every array a packer returns has to stay referenced until the C call returns.
@@ -591,12 +595,15 @@ class Model:
         return parent, cols, step_scores, path_scores, scale_exp
 
     def sample_sessions(self, hist_offs, hist_items, item_idx=None, steps=1, samples=1, top_k=None, temperature=1.0, seed=0, first_step=0,
-                        no_repeat=True, excl_offs=None, excl_items=None, excl_mask=None, hidden=None, return_hidden=False):
+                        no_repeat=True, excl_offs=None, excl_items=None, excl_mask=None, hidden=None, return_hidden=False, top_p=None,
+                        return_logprobs=False):
         """`samples` independent draws per session of `steps` items each from softmax(logit / temperature) over the eligible
         candidates (top_k: cut to the top_k best first), every drawn item fed back on the device (g4r_sample_sessions).  Arguments as
         in continue_sessions; draw (i, j) uses the noise of row id i * samples + j at steps first_step, first_step + 1, ...  Returns
         (cols int32[n, samples, steps], scores float32[n, samples, steps] -- the chosen positions' logits), + the hidden states that
-        produced the last step's scores (float32[n * samples, layers[l]] each) with return_hidden=True."""
+        produced the last step's scores (float32[n * samples, layers[l]] each) with return_hidden=True.  top_p (a float in (0, 1],
+        with top_k) and return_logprobs (+ logprobs float32[n, samples, steps], the last element) go through g4r_sample_sessions_lp;
+        without either the call is g4r_sample_sessions'."""
         offs, hi, n = _hist(hist_offs, hist_items)
         steps, samples = int(steps), int(samples)
         if steps < 1:
@@ -608,10 +615,39 @@ class Model:
         h0, h0p = _hidden_in(hidden, n, self.layers)
         hout, houtp = _hidden_out(n * samples, self.layers, return_hidden)
         cols, scores = _topk_out((n, samples, steps))
-        _chk(lib().g4r_sample_sessions(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, steps, 1 if no_repeat else 0, _i64(xo), _i32(xi),
-                                       _u32(mask), samples, 0 if top_k is None else int(top_k), float(temperature), int(seed), int(first_step),
-                                       _i32(cols), _f32(scores), houtp))
-        return (cols, scores, hout) if return_hidden else (cols, scores)
+        args = (self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, steps, 1 if no_repeat else 0, _i64(xo), _i32(xi), _u32(mask), samples,
+                0 if top_k is None else int(top_k), float(temperature), int(seed), int(first_step), _i32(cols), _f32(scores), houtp)
+        logprobs = np.empty((n, samples, steps), dtype=np.float32) if return_logprobs else None
+        if top_p is None and not return_logprobs:
+            _chk(lib().g4r_sample_sessions(*args))
+        else:
+            _chk(lib().g4r_sample_sessions_lp(*args, 0.0 if top_p is None else float(top_p), _f32(logprobs)))
+        out = (cols, scores) + ((hout,) if return_hidden else ()) + ((logprobs,) if return_logprobs else ())
+        return out
+
+    def session_log_partition(self, hist_offs, hist_items, item_idx=None, temperature=1.0, excl_offs=None, excl_items=None, excl_mask=None,
+                              hidden=None):
+        """The row normaliser after replaying whole session histories (g4r_session_log_partition; arguments as in recommend_sessions):
+        (zeta float32[n], Q uint64[n]) -- every session's largest eligible logit and the exact integer sum of
+        rn(2^39 * expf(fl32(fl32(z - zeta) / temperature))) over its eligible candidate positions."""
+        offs, hi, n = _hist(hist_offs, hist_items)
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        xo, xi, mask = _excl(n, excl_offs, excl_items, excl_mask, self.cfg.n_items, 'n')
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        zeta = np.empty(n, dtype=np.float32)
+        Q = np.empty(n, dtype=np.uint64)
+        _chk(lib().g4r_session_log_partition(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, _i64(xo), _i32(xi), _u32(mask),
+                                             float(temperature), _f32(zeta), _u64(Q)))
+        return zeta, Q
+
+    def debug_lse_terms(self, z, zeta, inv_t):
+        """The terms of the row normaliser for the logits z relative to zeta (an array like z, or one value) at the float32 reciprocal
+        temperature inv_t, from the device function the scan calls (g4r_debug_lse_terms): uint64[len(z)]."""
+        z = np.ascontiguousarray(z, dtype=np.float32).ravel()
+        zeta = np.ascontiguousarray(np.broadcast_to(np.asarray(zeta, dtype=np.float32), z.shape))
+        out = np.empty(len(z), dtype=np.uint64)
+        _chk(lib().g4r_debug_lse_terms(self.h, _f32(z), _f32(zeta), len(z), float(np.float32(inv_t)), _u64(out)))
+        return out
 
     def debug_gumbel(self, seed, row_id, step, items):
         """The noise of sample_sessions for (seed, row id, step) and every item index of `items`, from the device function the

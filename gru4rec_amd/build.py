@@ -62,7 +62,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
                "a pre-activation whose result rounds to -0.0 gets the positive branch's slope",
            23: "hidden_act_bwd: the negative-branch slope of leaky / elu / selu x 1.01",
            24: "k_mmr_rerank (g4r_diversify_*): from the second update on, a position's largest similarity to the picks is OVERWRITTEN by "
-               "its similarity to the last pick instead of max-ed with it"}
+               "its similarity to the last pick instead of max-ed with it",
+           25: "the per-score eligibility of the row normaliser (g4r_sample_sessions_lp, g4r_session_log_partition) never marks the LAST "
+               "item of a row's sorted list, so that item's term is counted in Q"}
 
 
 def mutant_path(k):

@@ -187,6 +187,26 @@ int g4r_debug_gumbel(g4r_model* m, uint64_t seed, uint32_t row_id, uint32_t step
     return 0;
 }
 
+// ---- the terms of the row normaliser of g4r_sample_sessions_lp (tests/test_gpu_sample_logprobs.py): out[p] = lse_term(z[p], zeta[p], invT)
+// through the __device__ function the scan calls
+int g4r_debug_lse_terms(g4r_model* m, const float* z, const float* zeta, int64_t n, float inv_t, uint64_t* out) {
+    if (!m || !z || !zeta || !out) return fail("null argument");
+    if (n < 1) return fail("n must be positive");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    CallTemps tmp(m);
+    float *d_z = nullptr, *d_zeta = nullptr;
+    unsigned long long* d_out = nullptr;
+    if (tmp.get(&d_z, (size_t)n, false) || tmp.get(&d_zeta, (size_t)n, false) || tmp.get(&d_out, (size_t)n, false)) return -1;
+    HIPCHK(hipMemcpyAsync(d_z, z, (size_t)n * sizeof(float), hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_zeta, zeta, (size_t)n * sizeof(float), hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(k_debug_lse_terms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, (const float*)d_z, (const float*)d_zeta, inv_t,
+                       (long long)n, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return 0;
+}
+
 // ---- row gather / scatter micro-benchmark (g4r_micro_kernels.cuh) ------------------------------------------------
 int g4r_bench_rows(int32_t device, int64_t n_items, int32_t W, int64_t rows_per_launch, int32_t launches, int32_t mode, uint64_t seed,
                    double* kernel_us, double* wall_us) {

@@ -186,6 +186,11 @@ struct g4r_model {
     DevBuf<unsigned> sm_rowid;
     DevBuf<int> sm_pick;
     DevBuf<float> sm_z;
+    // its log-probabilities and nucleus (g4r_sample_sessions_lp, g4r_session_log_partition): every row's zeta (the exact selection's top-1,
+    // with the column the merge writes beside it), its integer normaliser Q and the chunk's [rows][steps] log-probabilities
+    DevBuf<float> sm_zeta, sm_lp;
+    DevBuf<int> sm_zcol;
+    DevBuf<unsigned long long> sm_Q;
     // per-row candidate scoring (g4r_score_candidates*): one call's (or chunk's) CSR -- row offsets, candidate item indices, scores
     // in CSR order -- the work items of k_score_cand, the top-k lists of k_cand_pack and the selected (position, score) pairs
     DevBuf<long long> c_offs;
@@ -355,6 +360,8 @@ static constexpr auto k_topk_stored_x = k_topk_range<true, true, TkExcl>;
 static constexpr auto k_topk_fused_g = k_topk_range<false, true, TkGrow>;        // the same two with lists that grow on the device (g4r_continue_sessions)
 static constexpr auto k_topk_stored_g = k_topk_range<true, true, TkGrow>;
 static constexpr auto k_topk_sample = k_topk_range<false, true, TkSample>;      // selection on the Gumbel-perturbed key (g4r_sample_sessions)
+static constexpr auto k_topk_sample_q = k_topk_range<false, true, TkSampleLse>;  // the same draw + the row normaliser Q (g4r_sample_sessions_lp)
+static constexpr auto k_topk_fused_q = k_topk_range<false, true, TkGrowLse>;     // k_topk_fused_g + Q (launched with k = 1)
 static constexpr auto k_topk_rank = k_topk_range<false, false, TkEvents>;        // g4r_recommend_events: k_topk_fused + the rank counters of k_score_count
 static constexpr auto k_topk_rank_x = k_topk_range<false, true, TkEvents>;       // + the session-list / mask exclusions
 static constexpr auto k_topk_stored_ev = k_topk_range<true, true, TkEvents>;     // softmax / softmax_logit with those exclusions (no counters)

@@ -46,7 +46,8 @@ __device__ __forceinline__ unsigned long long topk_key(uint2 e) { return e.y == 
 #define TK_SMEM_FUSED_X (TK_SMEM_FUSED + TK_SEL_X)
 #define TK_SEL_EV (SC_BM * 4)           // TkEvents with EXCL: + every row's position in its session
 // LDS budget (160 KiB per CU): k_topk_stored 77,824 B, 95,744 B with EXCL; k_topk_fused 150,912 B, 152,448 B with EXCL, the four
-// waves' merge scratch (4 x 2,560 B, 4 x 6,656 B = 26,624 B with EXCL) aliasing its 66,560 B A tile
+// waves' merge scratch (4 x 2,560 B, 4 x 6,656 B = 26,624 B with EXCL) aliasing its 66,560 B A tile; 152,976 B for the forms with
+// the row normaliser (TK_SMEM_LSE, below)
 static_assert(4 * TK_SCRATCH_WAVE_X <= SC_BM * (SC_KC + 2) * 4, "the EXCL merge scratch must fit in the fused kernel's A tile");
 static_assert(TK_SMEM_STORED_X + TK_SEL_EV <= 156 * 1024 && TK_SMEM_FUSED_X + TK_SEL_EV <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
 
@@ -116,6 +117,44 @@ __device__ __forceinline__ TkSample tk_sample(TkExcl) { return TkSample{}; }
 __device__ __forceinline__ TkSample tk_sample(TkEvents) { return TkSample{}; }
 __device__ __forceinline__ TkSample tk_sample(TkGrow) { return TkSample{}; }
 __device__ __forceinline__ TkSample tk_sample(TkSample s) { return s; }
+// The row normaliser of g4r_sample_sessions_lp / g4r_session_log_partition: Q[row] = the sum over the row's ELIGIBLE candidate positions
+// of q = lse_term(z, zeta[row * zs], invT), an exact 64-bit integer -- every term is a function of the term alone and integer adds
+// commute, so Q has the same bits however the columns are cut into ranges and whatever order the workgroups finish in.  zeta: the
+// largest eligible z of the row (the exact selection's top-1), so that every term is at most 2^39; Q is zeroed on the stream first.
+struct TkLse { const float* zeta; int zs; unsigned long long* Q; float invT; };
+// q of one score: d = fl32(fl32(z - zeta) * invT) (two roundings, no FMA), q = rn(2^39 * expf(d)) (the library's expf; the product
+// with a power of two is exact); NaN gives 0
+__device__ __forceinline__ unsigned long long lse_term(float z, float zeta, float invT) {
+    const float d = __fmul_rn(__fsub_rn(z, zeta), invT);
+    if (d != d) return 0ull;
+    return __float2ull_rn(0x1p39f * expf(d));
+}
+// The trailing arguments of the two instantiations that form Q in their scan (k_topk_range<false, true, ...>), types of their own again:
+// TkSampleLse = TkSample's draw plus the sum, TkGrowLse = TkGrow's selection (launched with k = 1) plus the sum.
+struct TkSampleLse { TkSample s; TkLse l; };
+struct TkGrowLse { TkGrow g; TkLse l; };
+__device__ __forceinline__ TkExcl tk_excl(TkSampleLse x) { return tk_excl(x.s); }
+__device__ __forceinline__ TkExcl tk_excl(TkGrowLse x) { return tk_excl(x.g); }
+__device__ __forceinline__ TkEvents tk_events(TkSampleLse) { return TkEvents{}; }
+__device__ __forceinline__ TkEvents tk_events(TkGrowLse) { return TkEvents{}; }
+__device__ __forceinline__ TkGrow tk_grow(TkSampleLse x) { return tk_grow(x.s); }
+__device__ __forceinline__ TkGrow tk_grow(TkGrowLse x) { return x.g; }
+__device__ __forceinline__ TkSample tk_sample(TkSampleLse x) { return x.s; }
+__device__ __forceinline__ TkSample tk_sample(TkGrowLse) { return TkSample{}; }
+template <> struct tk_is_grow<TkSampleLse> { static constexpr bool value = true; };
+template <> struct tk_is_grow<TkGrowLse> { static constexpr bool value = true; };
+template <> struct tk_is_sample<TkSampleLse> { static constexpr bool value = true; };
+template <typename... X> struct tk_is_lse { static constexpr bool value = false; };
+template <> struct tk_is_lse<TkSampleLse> { static constexpr bool value = true; };
+template <> struct tk_is_lse<TkGrowLse> { static constexpr bool value = true; };
+__device__ __forceinline__ TkLse tk_lse() { return TkLse{}; }
+template <typename T> __device__ __forceinline__ TkLse tk_lse(T) { return TkLse{}; }
+__device__ __forceinline__ TkLse tk_lse(TkSampleLse x) { return x.l; }
+__device__ __forceinline__ TkLse tk_lse(TkGrowLse x) { return x.l; }
+// LDS of those two: the EXCL fused kernel's + per tile every row's 32-bit word of the columns its own list takes (SC_BM x 4 B) and the
+// word of the columns the global mask takes
+#define TK_SMEM_LSE (TK_SMEM_FUSED_X + (SC_BM + 4) * 4)
+static_assert(TK_SMEM_LSE <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
 // (Every score gets its noise.  Skipping the Philox call and the logarithms of a score whose key cannot beat its row's threshold
 // whatever the noise -- g < 17 -- gives the same results and was measured: it does not pay, profiles/sample_sessions.md.)
 
@@ -209,6 +248,7 @@ __device__ __forceinline__ void topk_merge_row(int r, uint2* L, int k, uint2* sq
 // EXCL: the exclusions (one trailing TkExcl argument) apply at every merge (topk_merge_row), the per-wave scratch grows by the
 // row's list (TK_SCRATCH_WAVE_X).  EXCL = false takes no trailing argument, so its kernel arguments -- and with them its code --
 // are those of the unfiltered kernel.  TkSample (fused, EXCL): the value selected on is the draw's key, see the struct.
+// TkSampleLse / TkGrowLse (fused, EXCL): the scan also adds every ELIGIBLE score's lse_term to the row's Q, see TkLse.
 template <bool STORED, bool EXCL, typename... X>
 __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__ mp, const float* h, int mrows, const int* item_idx,
                                                     long long n_sel, const float* sc, long long ldo, int k, int tpr, uint2* ws,
@@ -220,6 +260,9 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
     constexpr bool SMP = tk_is_sample<X...>::value;      // g4r_sample_sessions: keys in place of scores
     static_assert(!SMP || (EXCL && !STORED), "the sampling form is fused and takes its (possibly empty) lists");
     const TkSample smp = tk_sample(xs...);
+    constexpr bool LSE = tk_is_lse<X...>::value;         // the row normaliser Q formed in the scan (TkLse)
+    static_assert(!LSE || (EXCL && !STORED), "the forms with the row normaliser are fused and take their (possibly empty) lists");
+    const TkLse lse = tk_lse(xs...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, lg = lane >> 4;
     uint2* s_q = reinterpret_cast<uint2*>(smem);
@@ -234,6 +277,8 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
     const int ldk = SC_KC + 2;
     float* sB = sA + SC_BM * ldk;
     int* sItem = reinterpret_cast<int*>(sB + TK_TN * ldk);
+    unsigned* s_rowx = reinterpret_cast<unsigned*>(sItem + TK_TN);      // (LSE only) [SC_BM] the tile's columns taken by the row's list,
+    unsigned* s_dropw = s_rowx + SC_BM;                                 // by the global mask
     char* scratch = tail + wid * (EXCL ? TK_SCRATCH_WAVE_X : TK_SCRATCH_WAVE);
     uint2* sl = reinterpret_cast<uint2*>(scratch);
     unsigned long long* skq = reinterpret_cast<unsigned long long*>(scratch + TK_MAX * 8);
@@ -296,6 +341,37 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) rq[ri][rg] = smp.row_id[min(rbase + 32 * wid + 16 * ri + 4 * lg + rg, mrows - 1)];
     }
+    // (LSE) zeta of the lane's 8 rows and the lane's own share of their Q over the whole range.  Eligibility is decided per score here
+    // (the selection only applies exclusions where a queue is merged): thread r < SC_BM walks row r's sorted list with a cursor --
+    // all-items calls, whose columns are item indices: one lower_bound at c0, then per tile a compare with the next list item held in
+    // a register and a load only on a hit -- or, with a candidate list, searches the row's list for each of the tile's 32 items.
+    // Rows with an empty list do neither.  The lists grow between launches, so nothing is kept across them.
+    float zt[2][4];
+    unsigned long long qa[2][4];
+    long long lx_b = 0;
+    int lx_n = 0, lx_cur = 0, lx_next = 0;
+    if constexpr (LSE) {
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                zt[ri][rg] = lse.zeta[(size_t)min(rbase + 32 * wid + 16 * ri + 4 * lg + rg, mrows - 1) * lse.zs];
+                qa[ri][rg] = 0ull;
+            }
+        if (tid < SC_BM) {
+            lx_b = s_xb[tid];
+            lx_n = s_xn[tid];
+#if defined(G4R_MUTATE) && G4R_MUTATE == 25      // test build: the LAST item of the row's list is never marked, its term is counted
+            if (lx_n > 0) --lx_n;
+#endif
+            if (!item_idx && lx_n > 0) {
+                int a = 0, b = lx_n;
+                while (a < b) { const int mid = (a + b) >> 1; if ((long long)ex.items[lx_b + mid] < c0) a = mid + 1; else b = mid; }
+                lx_cur = a;
+                if (a < lx_n) lx_next = ex.items[lx_b + a];
+            }
+        }
+    }
     for (long long n0 = c0; n0 < c1; n0 += TK_TN) {
         float v[2][2][4];      // [ri][cj][rg]: row 32 wid + 16 ri + 4 lg + rg, column n0 + 16 cj + li (the MFMA accumulator layout)
         if constexpr (!STORED) {
@@ -304,8 +380,34 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
             if (tid < TK_TN) {
                 const long long n = n0 + tid;
                 sItem[tid] = n < c1 ? (item_idx ? item_idx[n] : (int)n) : -1;
+                if constexpr (LSE) {      // the tile's columns the global mask takes: one word, from the 32 threads that load the items
+                    const int item = sItem[tid];
+                    const unsigned long long dr = __ballot(item >= 0 && ex.mask && ((ex.mask[item >> 5] >> (item & 31)) & 1u));
+                    if (tid == 0) *s_dropw = (unsigned)dr;
+                }
             }
             __syncthreads();
+            if constexpr (LSE) {
+                if (tid < SC_BM) {      // row tid's word: the tile's columns whose item is in the row's list
+                    unsigned w = 0u;
+                    if (lx_n > 0 && !item_idx) {
+                        const long long n1 = n0 + TK_TN;
+                        while (lx_cur < lx_n && lx_next < n1) {
+                            w |= 1u << (int)(lx_next - n0);
+                            if (++lx_cur < lx_n) lx_next = ex.items[lx_b + lx_cur];
+                        }
+                    } else if (lx_n > 0) {
+                        for (int j = 0; j < TK_TN; ++j) {
+                            const int item = sItem[j];
+                            if (item < 0) break;      // (the columns past c1 close the last tile)
+                            int a = 0, b = lx_n;
+                            while (a < b) { const int mid = (a + b) >> 1; if (ex.items[lx_b + mid] < item) a = mid + 1; else b = mid; }
+                            if (a < lx_n && ex.items[lx_b + a] == item) w |= 1u << j;
+                        }
+                    }
+                    s_rowx[tid] = w;      // (read after the chain's barriers below, written again after the next tile's first one)
+                }
+            }
             f32x4 acc[2][2];
 #pragma unroll
             for (int a = 0; a < 2; ++a)
@@ -367,9 +469,13 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
             for (int rg = 0; rg < 4; ++rg) {
                 const int r = 32 * wid + 16 * ri + 4 * lg + rg;
                 const unsigned long long t = s_thr[r];
+                unsigned gone = 0u;      // (LSE) the tile's columns that are not eligible in this row
+                if constexpr (LSE) gone = s_rowx[r] | *s_dropw;
 #pragma unroll
                 for (int cj = 0; cj < 2; ++cj) {
                     const long long n = n0 + 16 * cj + li;
+                    if constexpr (LSE)
+                        if (rbase + r < mrows && n < c1 && !((gone >> (16 * cj + li)) & 1u)) qa[ri][rg] += lse_term(v[ri][cj][rg], zt[ri][rg], lse.invT);
                     if constexpr (RANK) {      // in front of every exclusion: those are applied where a queue is merged
                         float x = v[ri][cj][rg];
                         if (ev.tie_col) x += tie_noise(mp->seed, ev.tie_ctr, rbase + r, n + ev.col_off);
@@ -395,6 +501,22 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
             uint2* L = list(r);
             for (int j = s_ln[r] + lane; j < k; j += 64) L[j] = make_uint2(0u, 0xFFFFFFFFu);
         }
+    if constexpr (LSE) {
+        // the 16 lanes that share a row are added up (integers: any order gives the same bits), then one atomic per row and workgroup
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                unsigned long long q = qa[ri][rg];
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) {
+                    const unsigned lo = __shfl_xor((unsigned)q, o), hi = __shfl_xor((unsigned)(q >> 32), o);
+                    q += ((unsigned long long)hi << 32) | lo;
+                }
+                const int row = rbase + 32 * wid + 16 * ri + 4 * lg + rg;
+                if (li == 0 && row < mrows && q) atomicAdd(lse.Q + row, q);
+            }
+    }
     if constexpr (RANK) {
         // the 16 lanes that share a row (same lg) are added up, then one atomic pair per row and workgroup
 #pragma unroll

@@ -100,6 +100,29 @@ def _check_steps(steps):
     return int(steps)
 
 
+def _check_temperature(temperature):
+    """The temperature of sample_sessions / session_log_partition, checked, as a float32."""
+    try:
+        with np.errstate(all='ignore'):
+            t32 = np.float32(temperature) if not isinstance(temperature, (bool, str)) else np.float32('nan')
+            ok = bool(np.isfinite(t32) and t32 > 0 and np.isfinite(np.float32(1) / t32))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('temperature = %r: it must be a finite float > 0 (as a float32, with a finite reciprocal); the greedy limit '
+                         'temperature -> 0 is continue_sessions(k=1)' % (temperature,))
+    return t32
+
+
+LSE_CAND_MAX = 2 ** 24      # G4R_LSE_CAND_MAX: with more candidate positions the exact 64-bit row normaliser could overflow
+
+
+def _check_lse_candidates(n_cand):
+    if n_cand > LSE_CAND_MAX:
+        raise ValueError('%d candidate positions: log-probabilities, top_p and session_log_partition take at most 2^24 (the row '
+                         'normaliser is an exact 64-bit integer)' % n_cand)
+
+
 def _scan_kw(over):      # the keyword of the device model's two-stage selection; the exact one is called without it
     return {} if over is None else dict(oversample=over)
 
@@ -1164,8 +1187,33 @@ class GRU4Rec:
         paths, step_scores = _native.beam_backtrack(parent, cols, sscores)
         return cand[paths], path_scores, step_scores, scale_exp
 
+    def session_log_partition(self, histories, temperature=1.0, predict_for_item_ids=None, exclude_history=False, exclude=None,
+                              exclude_per_row=None, hidden=None):
+        """lse float32[N]: the logarithm of the sum of exp(z / temperature) over every session's eligible candidates, formed on the
+        device in one stateless call.  Not in the reference.  For a model whose score is the logit (every final_act but softmax /
+        softmax_logit), fl32(z / temperature) - lse is the log-probability, under softmax(z / temperature) over the eligible
+        candidates, of any score z that recommend_sessions or score_candidates_sessions returns for the same arguments; for softmax
+        models z is the pre-activation value, as in sample_sessions.  Arguments, eligibility and refusals are recommend_sessions' with
+        k = 1, temperature is sample_sessions'; at most 2^24 candidate positions.  The value is sample_sessions' normaliser:
+        lse = fl32(zeta / temperature + log(Q * 2^-39)) in float64, zeta and the exact integer Q as its docstring defines them, so the
+        same session gives the same bits alone or among others."""
+        if self.error_during_train:
+            raise Exception
+        t32 = _check_temperature(temperature)
+        _check_k(1, self._n_candidates(predict_for_item_ids), bools=True)
+        _check_lse_candidates(self._n_candidates(predict_for_item_ids))
+        N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
+        iidx, cand = self._candidates(predict_for_item_ids)
+        excl = self._session_exclusions(N, lens, hidx, 1, iidx, exclude_history, exclude, exclude_per_row)
+        m = self._ensure_model()
+        zeta, Q = m.session_log_partition(offs, hidx, iidx, float(t32), *excl, hidden=h0)
+        inv_t = np.float64(np.float32(1) / t32)
+        with np.errstate(all='ignore'):
+            return (zeta.astype(np.float64) * inv_t + np.log(Q.astype(np.float64) * 2.0 ** -39)).astype(np.float32)
+
     def sample_sessions(self, histories, steps, samples=1, temperature=1.0, top_k=None, seed=0, first_step=0, no_repeat=True,
-                        predict_for_item_ids=None, exclude=None, exclude_per_row=None, hidden=None, return_hidden=False):
+                        predict_for_item_ids=None, exclude=None, exclude_per_row=None, hidden=None, return_hidden=False, top_p=None,
+                        return_logprobs=False):
         """Stochastic continuations of N whole sessions in one stateless call: `samples` independent draws per session of `steps`
         items each, drawn from the model's own next-item distribution.  Returns (item_ids[N, samples, steps], scores[N, samples,
         steps] float32), plus the hidden state with return_hidden=True.  Not in the reference.  continue_sessions and beam_sessions are
@@ -1205,9 +1253,31 @@ class GRU4Rec:
                            G4R_EXCLUDE_MAX, at least k eligible positions at the last step.
 
         Everything is checked before any device work and the prediction state is neither read nor changed.  N * samples must not
-        exceed 2^31 - 1.  The two-stage scan='bf16' selection is not offered here.  Out of scope as well: the log-probabilities of
-        the drawn items and nucleus (top-p) sampling -- both need a normaliser over the row's whole eligible set, which the
-        selection kernel never forms."""
+        exceed 2^31 - 1.  The two-stage scan='bf16' selection is not offered here.
+
+          return_logprobs  True: logprobs[N, samples, steps] float32, the log-probability with which every item was drawn, is appended
+                           as the LAST element of the returned tuple (after the hidden state, if that is returned too).  Items, scores
+                           and hidden state are, bit for bit, those of the call without it.
+          top_p            None, or a float with 0 < fl32(top_p) <= 1; it needs top_k.  Nucleus sampling: the draw is made among the
+                           shortest prefix of the top_k best whose mass reaches top_p of the WHOLE eligible set's.
+
+        Both rest on a row normaliser formed on the device in the scan of the catalogue, exactly, in 64-bit fixed point, so that they
+        keep the promise above (no dependence on N, the batch, the row order or the chunking).  For one draw at one step, over its
+        eligible candidate positions E (with predict_for_item_ids every position counts, a duplicate once each):
+          zeta     the largest z over E in the selection's order;
+          d_n      fl32(fl32(z_n - zeta) * fl32(1 / temperature)): two roundings, no FMA;
+          q_n      round_to_uint64(2^39 * expf(d_n)), 0 for a NaN d_n: the argmax has 2^39 exactly, terms more than about 27 nats
+                   below it are 0;
+          Q        the sum of q_n over E, an exact integer (more than 2^24 candidate positions are refused with these options);
+          logprob  fl32(float64(d_c) - log(float64(Den) * 2^-39)) of the chosen c, Den the integer mass of the set drawn from: Q when
+                   untruncated; C_t, the sum of q over the top_k best (zeta is then their first z), with top_k alone; C_m with top_p;
+          nucleus  the top_k best in the selection's order, C_j the integer prefix sums of their q: m is the smallest j with
+                   float64(C_j) >= float64(fl32(top_p)) * float64(Q), or top_k if there is none, and the draw is the usual argmax
+                   over the first m entries.  So top_p=1.0 gives top_p=None bit for bit, and a top_p below the first entry's share
+                   gives top_k=1's path with every logprob == 0.0.
+        The untruncated logprob costs a second scan of the catalogue per step (zeta first, then the sum), top_p one more scan;
+        top_k with return_logprobs alone costs none.  Scores that are not finite (zeta NaN or infinite) give undefined
+        log-probabilities.  session_log_partition returns the normaliser itself."""
         if self.error_during_train:
             raise Exception
         steps = _check_steps(steps)
@@ -1218,17 +1288,26 @@ class GRU4Rec:
         if not ok:
             raise ValueError('samples = %r: it must be an integer in [1, G4R_SAMPLE_MAX = %d]' % (samples, _native.G4R_SAMPLE_MAX))
         samples = int(samples)
-        try:
-            with np.errstate(all='ignore'):
-                t32 = np.float32(temperature) if not isinstance(temperature, (bool, str)) else np.float32('nan')
-                ok = bool(np.isfinite(t32) and t32 > 0 and np.isfinite(np.float32(1) / t32))
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError('temperature = %r: it must be a finite float > 0 (as a float32, with a finite reciprocal); the greedy limit '
-                             'temperature -> 0 is continue_sessions(k=1)' % (temperature,))
+        t32 = _check_temperature(temperature)
         if top_k is not None:
             top_k = _check_k(top_k, self._n_candidates(predict_for_item_ids), name='top_k', own_errors=True)
+        if top_p is not None:
+            try:
+                with np.errstate(all='ignore'):
+                    p32 = np.float32(top_p) if not isinstance(top_p, (bool, np.bool_, str)) and np.ndim(top_p) == 0 else np.float32('nan')
+                    ok = bool(0 < p32 <= 1)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError('top_p = %r: it must be None or a float in (0, 1] (as a float32)' % (top_p,))
+            if top_k is None:
+                raise ValueError('top_p = %r needs top_k: the nucleus is sought among the top_k best' % (top_p,))
+            top_p = float(p32)
+        if not isinstance(return_logprobs, (bool, np.bool_)):
+            raise ValueError('return_logprobs = %r: it must be True or False' % (return_logprobs,))
+        return_logprobs = bool(return_logprobs)
+        if top_p is not None or return_logprobs:
+            _check_lse_candidates(self._n_candidates(predict_for_item_ids))
         try:
             ok = not isinstance(seed, bool) and int(seed) == seed and 0 <= seed < 2 ** 64
         except (TypeError, ValueError):
@@ -1248,11 +1327,15 @@ class GRU4Rec:
         iidx, cand = self._candidates(predict_for_item_ids)
         excl = self._session_exclusions(N, lens, hidx, k, iidx, no_repeat, exclude, exclude_per_row, steps=steps)
         m = self._ensure_model()
+        opts = dict(top_p=top_p, return_logprobs=return_logprobs) if top_p is not None or return_logprobs else {}      # (none: the old entry)
         out = m.sample_sessions(offs, hidx, iidx, steps, samples, top_k, float(t32), int(seed), int(first_step), bool(no_repeat), *excl,
-                                hidden=h0, return_hidden=return_hidden)
-        if not return_hidden:
-            return cand[out[0]], out[1]
-        return cand[out[0]], out[1], [h.reshape(N, samples, -1) for h in self._unpad_hidden(out[2])]
+                                hidden=h0, return_hidden=return_hidden, **opts)
+        res = (cand[out[0]], out[1])
+        if return_hidden:
+            res += ([h.reshape(N, samples, -1) for h in self._unpad_hidden(out[2])],)
+        if return_logprobs:
+            res += (out[-1],)
+        return res
 
     # ------------------------------------------------------------------ per-row candidate lists (not in the reference)
     def _candidate_csr(self, candidates, rows, k):

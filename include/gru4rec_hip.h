@@ -294,13 +294,42 @@ int g4r_beam_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* his
  * z, not its key.  out_hidden (NULL: not wanted): per layer n * samples rows, the state that produced the LAST step's scores.  The
  * refusals of g4r_continue_sessions apply with k = top_k, or 1 without it; everything is checked before any launch; the prediction
  * state is neither read nor changed.  One stream synchronisation and one download per chunk of sessions (a chunk holds at most
- * 512 draw rows).  Log-probabilities of the draws and nucleus (top-p) sampling are not offered: both need a row-wide normaliser. */
+ * 512 draw rows).  Log-probabilities of the draws and nucleus (top-p) sampling: g4r_sample_sessions_lp. */
 #define G4R_SAMPLE_MAX 64
 #define G4R_STREAM_GUMBEL 0x47554D42u
 int g4r_sample_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
                         const int32_t* item_idx, int64_t n_sel, int32_t steps, int32_t no_repeat, const int64_t* excl_offs,
                         const int32_t* excl_items, const uint32_t* excl_mask, int32_t samples, int32_t top_k, float temperature,
                         uint64_t seed, int32_t first_step, int32_t* out_cols, float* out_scores, float* const* out_hidden);
+
+/* not in the reference: g4r_sample_sessions plus the log-probability of every drawn item (out_logprobs[n * samples * steps], NULL: not
+ * wanted) and nucleus sampling (top_p in (0, 1], 0: off; it needs top_k).  With both off it makes g4r_sample_sessions' launches and
+ * returns its bits.  Arithmetic of one draw row at one step, E its eligible candidate positions (exactly those the selection may return):
+ *   zeta   the largest z over E in the selection's order (the exact selection's top-1);
+ *   d_n    fl32(fl32(z_n - zeta) * invT), two roundings, no FMA;
+ *   q_n    rn_u64(2^39 * expf(d_n)) (precise expf), 0 where d_n is NaN: the argmax has 2^39 exactly, a term more than about 27 below
+ *          zeta * invT has 0;
+ *   Q      the sum of q_n over E as an exact 64-bit integer: the same bits whatever the row count, the chip, the chunking (more than
+ *          2^24 candidate positions are refused with these options, so Q < 2^63);
+ *   logprob of the chosen position c: fl32((double)d_c - log((double)Den * 2^-39)), Den the integer mass of the set drawn from: Q when
+ *          untruncated; C_t, the sum of q over the row's t = top_k best (zeta their first z), with top_k alone; C_m with top_p;
+ *   top_p  the t best in the selection's order, C_j the integer prefix sums of their q: m is the smallest j with (double)C_j >=
+ *          (double)top_p * (double)Q (none: m = t), and the draw is the argmax of the key over the first m entries.  So top_p = 1 gives
+ *          top_p = 0's results, and a top_p below the first entry's share top_k = 1's with logprob 0.
+ * Scores that are not finite (zeta NaN or infinite) give undefined log-probabilities. */
+int g4r_sample_sessions_lp(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                           const int32_t* item_idx, int64_t n_sel, int32_t steps, int32_t no_repeat, const int64_t* excl_offs,
+                           const int32_t* excl_items, const uint32_t* excl_mask, int32_t samples, int32_t top_k, float temperature,
+                           uint64_t seed, int32_t first_step, int32_t* out_cols, float* out_scores, float* const* out_hidden, float top_p,
+                           float* out_logprobs);
+
+/* not in the reference: the log-partition of n whole sessions, stateless: the replay of g4r_recommend_sessions (its arguments and
+ * refusals with k = 1, at most 2^24 candidate positions), then out_zeta[i] = zeta and out_Q[i] = Q of session i as defined above, over
+ * its eligible candidate positions at the given temperature.  lse = zeta * invT + log(Q * 2^-39) (in double) is the logarithm of the sum
+ * of exp(z * invT) over them: z * invT - lse is the log-probability of any eligible position under softmax(z / temperature). */
+int g4r_session_log_partition(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                              const int32_t* item_idx, int64_t n_sel, const int64_t* excl_offs, const int32_t* excl_items,
+                              const uint32_t* excl_mask, float temperature, float* out_zeta, uint64_t* out_Q);
 
 /* not in the reference: item-to-item neighbours in the model's own embedding space -- the k candidates most similar to each of n
  * query items.  Stateless: the prediction state and the training state are neither read nor changed.
@@ -531,6 +560,9 @@ int g4r_debug_loss_rows(g4r_model* m, float* scores, int64_t count, int32_t M, f
 /* Test support (tests/test_gpu_sample_sessions.py), not in the reference: out[p] = the noise g of g4r_sample_sessions for row id
  * row_id, step `step` and item index items[p] >= 0, p < n, computed by the device function its selection calls. */
 int g4r_debug_gumbel(g4r_model* m, uint64_t seed, uint32_t row_id, uint32_t step, const int32_t* items, int64_t n, float* out);
+/* Test support (tests/test_gpu_sample_logprobs.py), not in the reference: out[p] = the term q of g4r_sample_sessions_lp's row normaliser
+ * for the logit z[p] relative to zeta[p] at the reciprocal temperature inv_t, p < n, computed by the device function its scan calls. */
+int g4r_debug_lse_terms(g4r_model* m, const float* z, const float* zeta, int64_t n, float inv_t, uint64_t* out);
 int g4r_selftest_mfma(float* max_abs_err);
 /* Row gather / scatter micro-benchmark on a table of n_items x W floats (fresh allocation, random rows, every launch its own
  * rows): mode 0 gather to a compact buffer, 1 gather consumed in registers (what the step's fused gathers do), 2 Adagrad scatter

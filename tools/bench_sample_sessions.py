@@ -11,7 +11,9 @@ Shapes: rsc15 = 37,483 items x 100 units, 10M = 10,000,000 items x 256 units (5 
 --warmup, with the spread (max - min) next to it.  At 10M the host loop is timed on --host-rows rows and scaled to 512 (its score rows
 alone are 20 GB per step).  --budget: seconds after which no further case is started (the remaining ones are reported as not measured).
 --label names the library in the table (a kernel experiment is a second run with G4R_LIB set to the variant library).  --md appends
-the table of profiles/sample_sessions.md to FILE.  Kernel times do not come from this script: run it under
+the table of profiles/sample_sessions.md to FILE.  --legs (default logprobs,top_p,partition; '' for none) adds, per (shape, samples, steps) and
+beside the untruncated case: sample_sessions(return_logprobs=True), sample_sessions(top_k=50, top_p=0.9) and -- once per shape and samples --
+session_log_partition on the 512 histories of (a), history excluded.  Kernel times do not come from this script: run it under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_sample_sessions.py --shapes rsc15 --steps 20 --samples 1 --top-ks 0 --reps 3
 --warmup 1 --call-only` in a run of its own."""
 import argparse
@@ -76,10 +78,12 @@ def main():
     ap.add_argument('--budget', type=float, default=600.0)
     ap.add_argument('--label', default='product')
     ap.add_argument('--md', default=None)
+    ap.add_argument('--legs', default='logprobs,top_p,partition', help='the log-probability / nucleus / log-partition legs to time')
     ap.add_argument('--call-only', action='store_true', help='time sample_sessions alone (for a kernel trace)')
     a = ap.parse_args()
     t_start = time.perf_counter()
     rows = []
+    legs = [x for x in a.legs.split(',') if x]
     for name in a.shapes.split(','):
         I, D = SHAPES[name]
         rng = np.random.RandomState(0)
@@ -106,6 +110,16 @@ def main():
                         continue
                     kw = dict(samples=samples, temperature=TEMPERATURE, top_k=top_k or None, seed=7)
                     out['ms_sample'], out['spread_sample'] = timed(lambda: g.sample_sessions(hists, steps, **kw), a.reps, a.warmup)
+                    if not top_k:
+                        if 'logprobs' in legs:
+                            out['ms_logprobs'], out['spread_logprobs'] = timed(lambda: g.sample_sessions(hists, steps, return_logprobs=True, **kw),
+                                                                               a.reps, a.warmup)
+                        if 'top_p' in legs:
+                            kp = dict(kw, top_k=50, top_p=0.9)
+                            out['ms_top_p'], out['spread_top_p'] = timed(lambda: g.sample_sessions(hists, steps, **kp), a.reps, a.warmup)
+                        if 'partition' in legs and steps == int(a.steps.split(',')[0]):
+                            out['ms_partition'], out['spread_partition'] = timed(
+                                lambda: g.session_log_partition(wide, temperature=TEMPERATURE, exclude_history=True), a.reps, a.warmup)
                     if not a.call_only:
                         if base is None:      # (a) does not depend on top_k
                             base = timed(lambda: g.continue_sessions(wide, steps, k=1), a.reps, a.warmup)
@@ -136,6 +150,18 @@ def main():
                 f.write('| %s | %d | %d | %s | %.2f (%.2f) | %.2f (%.2f) | %.2f | %s | %s |\n' % (
                     r['shape'], r['samples'], r['steps'], r['top_k'] or '-', r['ms_sample'], r['spread_sample'], r['ms_continue'],
                     r['spread_continue'], r['sample_over_continue'], host, r.get('host_over_sample', '-')))
+    if a.md and legs and any('ms_logprobs' in r or 'ms_top_p' in r or 'ms_partition' in r for r in rows):
+        cell = (lambda r, k: '%.2f (%.2f)' % (r['ms_' + k], r['spread_' + k]) if 'ms_' + k in r else '-')
+        with open(a.md, 'a') as f:
+            f.write('\n### %s: log-probabilities, nucleus, log-partition\n\n| shape | samples | steps | sample_sessions ms (spread) | return_logprobs ms '
+                    '(spread) | logprobs / plain | top_k=50, top_p=0.9 ms (spread) | session_log_partition, 512 sessions ms (spread) |\n'
+                    '|---|---|---|---|---|---|---|---|\n' % a.label)
+            for r in rows:
+                if r['top_k'] or 'ms_sample' not in r:
+                    continue
+                ratio = '%.2f' % (r['ms_logprobs'] / r['ms_sample']) if 'ms_logprobs' in r else '-'
+                f.write('| %s | %d | %d | %s | %s | %s | %s | %s |\n' % (r['shape'], r['samples'], r['steps'], cell(r, 'sample'), cell(r, 'logprobs'), ratio,
+                                                                       cell(r, 'top_p'), cell(r, 'partition')))
 
 
 if __name__ == '__main__':
