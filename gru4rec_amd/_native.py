@@ -20,6 +20,7 @@ BEAM_COMBINE = {'sum': 0, 'product': 1}      # G4R_BEAM_*
 G4R_EXCLUDE_MAX = 1024  # most distinct items one row of g4r_recommend_step_filtered may exclude
 G4R_CAND_MAX = 2 ** 31 - 256  # most candidate positions of one g4r_score_candidates* call
 G4R_DIVERSIFY_POOL_MAX = 128  # largest pool of g4r_diversify_lists / g4r_diversify_sessions
+G4R_GROUP_PRIOR_MAX = 1024  # most prior groups of one row of g4r_continue_sessions_capped / g4r_cap_lists
 G4R_SCAN_CAND_MAX = 1024  # most candidates per row (k * oversample) of g4r_recommend_step_scan / g4r_recommend_sessions_scan
 LOSS_IDS = {'cross-entropy': 0, 'bpr-max': 1, 'top1-max': 2, 'bpr': 3, 'top1': 4, 'xe_logit': 5}
 ACT_IDS = {'linear': 0, 'relu': 1, 'tanh': 2, 'leaky': 3, 'elu': 4, 'selu': 5, 'softmax': 6, 'softmax_logit': 7}
@@ -53,7 +54,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_set_item_groups', 'g4r_get_item_groups', 'g4r_recommend_sessions_capped', 'g4r_continue_sessions_capped', 'g4r_cap_lists', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_debug_gumbel', 'g4r_debug_lse_terms', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -145,6 +146,13 @@ def lib():
     L.g4r_diversify_lists.argtypes = [vp, i32, i32, i32p, f32p, i64, i32, i32, C.c_float, i32, i32p, f32p]
     L.g4r_diversify_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i64p, i32p, u32p, i32, i32, C.c_float, i32,
                                          i32p, f32p, i32p, f32p, f32pp]
+    L.g4r_set_item_groups.argtypes = [vp, i32p, i64]
+    L.g4r_get_item_groups.argtypes = [vp, i32p, i64]
+    L.g4r_recommend_sessions_capped.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i64p, i32p, u32p, i32, i32p, f32p, i32p,
+                                                i32p, f32pp]
+    L.g4r_continue_sessions_capped.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i32, i32, i64p, i32p, u32p, i32, i64p,
+                                               i32p, i32p, f32p, i32p, f32pp]
+    L.g4r_cap_lists.argtypes = [vp, i32p, i64, i32, i32, i32, i64p, i32p, i32p, i32p]
     L.g4r_score_candidates.argtypes = [vp, i32p, i32, i64p, i32p, i32, f32p, i32p]
     L.g4r_score_candidates_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i64p, i32p, i32, f32p, i32p, f32pp]
     L.g4r_rank_targets.argtypes = [vp, i32p, i32, i64, i32, f32p]
@@ -699,6 +707,80 @@ class Model:
                                           _i64(xo), _i32(xi), _u32(mask), SIM_SPACES[space], SIM_METRICS[metric], float(lam),
                                           1 if normalize else 0, _i32(cols), _f32(scores), _i32(pos), _f32(values), houtp))
         return (cols, scores, pos, values, hout) if return_hidden else (cols, scores, pos, values)
+
+    # -- item groups and per-group caps
+    def set_item_groups(self, groups):
+        """The model's group table (g4r_set_item_groups): int32[n_items], -1 = ungrouped; None clears it."""
+        if groups is None:
+            _chk(lib().g4r_set_item_groups(self.h, None, 0))
+            return
+        g = np.ascontiguousarray(groups, dtype=np.int32)
+        _chk(lib().g4r_set_item_groups(self.h, _i32(g), g.size))
+
+    def get_item_groups(self):
+        out = np.empty(self.cfg.n_items, dtype=np.int32)
+        _chk(lib().g4r_get_item_groups(self.h, _i32(out), out.size))
+        return out
+
+    @staticmethod
+    def _priors(n, prior_offs, prior_groups):
+        """The prior lists of n rows: (offsets int64[n + 1] or None, group indices int32 -- empty without lists, never None)."""
+        offs = _arr(prior_offs, np.int64)
+        groups = np.ascontiguousarray(np.zeros(0) if prior_groups is None else prior_groups, dtype=np.int32)
+        if offs is not None and (len(offs) != n + 1 or offs[-1] > len(groups) or offs[0] < 0):
+            raise ValueError('prior_offs must hold n + 1 offsets into prior_groups')
+        return offs, groups
+
+    def recommend_sessions_capped(self, hist_offs, hist_items, item_idx=None, k=20, pool=100, cap=1, excl_offs=None, excl_items=None,
+                                  excl_mask=None, hidden=None, return_hidden=False, oversample=None):
+        """recommend_sessions with k = pool followed on the device by the cap rule over every session's pool
+        (g4r_recommend_sessions_capped): (cols int32[n, k], scores float32[n, k], pos int32[n, k], kept int32[n]), + the hidden states
+        with return_hidden=True.  Entries at and after kept[i] are pads (-1, NaN, -1).  The other arguments as in recommend_sessions."""
+        offs, hi, n = _hist(hist_offs, hist_items)
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        xo, xi, mask = _excl(n, excl_offs, excl_items, excl_mask, self.cfg.n_items, 'n')
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        hout, houtp = _hidden_out(n, self.layers, return_hidden)
+        cols, scores = _topk_out((n, k))
+        pos, kept = np.empty((n, k), dtype=np.int32), np.empty(n, dtype=np.int32)
+        _chk(lib().g4r_recommend_sessions_capped(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, k, pool,
+                                                 0 if oversample is None else int(oversample), _i64(xo), _i32(xi), _u32(mask), int(cap),
+                                                 _i32(cols), _f32(scores), _i32(pos), _i32(kept), houtp))
+        return (cols, scores, pos, kept, hout) if return_hidden else (cols, scores, pos, kept)
+
+    def continue_sessions_capped(self, hist_offs, hist_items, item_idx=None, k=1, pool=100, cap=1, steps=1, no_repeat=True, excl_offs=None,
+                                 excl_items=None, excl_mask=None, prior_offs=None, prior_groups=None, hidden=None, return_hidden=False,
+                                 oversample=None):
+        """continue_sessions with the cap rule between every step's selection of `pool` and its feedback
+        (g4r_continue_sessions_capped): (cols int32[n, steps, k], scores float32[n, steps, k], kept int32[n, steps]), + the hidden
+        states with return_hidden=True.  prior_offs / prior_groups: every session's prior group indices (CSR)."""
+        offs, hi, n = _hist(hist_offs, hist_items)
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError('steps must be at least 1')
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        xo, xi, mask = _excl(n, excl_offs, excl_items, excl_mask, self.cfg.n_items, 'n')
+        po, pg = self._priors(n, prior_offs, prior_groups)
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        hout, houtp = _hidden_out(n, self.layers, return_hidden)
+        cols, scores = _topk_out((n, steps, k))
+        kept = np.empty((n, steps), dtype=np.int32)
+        _chk(lib().g4r_continue_sessions_capped(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, k, pool,
+                                                0 if oversample is None else int(oversample), steps, 1 if no_repeat else 0, _i64(xo), _i32(xi),
+                                                _u32(mask), int(cap), _i64(po), _i32(pg), _i32(cols), _f32(scores), _i32(kept), houtp))
+        return (cols, scores, kept, hout) if return_hidden else (cols, scores, kept)
+
+    def cap_lists(self, items, k, cap, prior_offs=None, prior_groups=None):
+        """The cap rule over supplied lists (g4r_cap_lists; stateless): items int32[n, P] (item indices) -> (pos int32[n, k] kept
+        positions in list order, then -1; kept int32[n])."""
+        it = np.ascontiguousarray(items, dtype=np.int32)
+        if it.ndim != 2:
+            raise ValueError('items must be an array of shape [n, P]')
+        n, P = it.shape
+        po, pg = self._priors(n, prior_offs, prior_groups)
+        pos, kept = np.empty((n, k), dtype=np.int32), np.empty(n, dtype=np.int32)
+        _chk(lib().g4r_cap_lists(self.h, _i32(it), n, P, k, int(cap), _i64(po), _i32(pg), _i32(pos), _i32(kept)))
+        return pos, kept
 
     def sim_norms(self):
         """State of the inverse-norm cache of similar_items: (bytes held, valid, builds so far)."""

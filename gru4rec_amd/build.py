@@ -64,7 +64,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            24: "k_mmr_rerank (g4r_diversify_*): from the second update on, a position's largest similarity to the picks is OVERWRITTEN by "
                "its similarity to the last pick instead of max-ed with it",
            25: "the per-score eligibility of the row normaliser (g4r_sample_sessions_lp, g4r_session_log_partition) never marks the LAST "
-               "item of a row's sorted list, so that item's term is counted in Q"}
+               "item of a row's sorted list, so that item's term is counted in Q",
+           26: "k_group_cap (g4r_*_capped, g4r_cap_lists) counts a position's earlier same-group positions from the start of its OWN wave "
+               "only: the positions of earlier waves are forgotten, so pools of more than 64 keep too many"}
 
 
 def mutant_path(k):

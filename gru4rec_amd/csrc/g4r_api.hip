@@ -22,6 +22,7 @@
 #include "g4r_scan_kernels.cuh"
 #include "g4r_sim_kernels.cuh"
 #include "g4r_mmr_kernels.cuh"
+#include "g4r_group_kernels.cuh"
 #include "g4r_sync_kernels.cuh"
 #include "g4r_micro_kernels.cuh"
 #include "g4r_wide_kernels.cuh"
@@ -43,6 +44,7 @@ extern "C" {
 #include "g4r_host_events.hpp"
 #include "g4r_host_similar.hpp"
 #include "g4r_host_diversify.hpp"
+#include "g4r_host_groups.hpp"
 #include "g4r_host_comm.hpp"
 #include "g4r_host_sync.hpp"
 #include "g4r_host_debug.hpp"

@@ -220,7 +220,17 @@ struct g4r_model {
     // position, value and, after a session selection, the picked candidates' columns and model scores
     DevBuf<int> dv_items, dv_pos, dv_cols;
     DevBuf<float> dv_rel, dv_val, dv_scores;
-    unsigned tie_ctr = 0;                       // evaluation step counter of the 'tiebreaking' noise stream
+    // item groups and per-group caps (g4r_set_item_groups, g4r_*_capped, g4r_cap_lists; k_group_cap): the group table [n_items] (-1 =
+    // ungrouped; it does not depend on the weights, so weights_changed leaves it alone) and the number of groups; a chunk's supplied
+    // lists [rows][P]; what the rule keeps [rows][k] -- column, score, position -- and the counts [rows][steps]; the rows' prior lists
+    // (begin, current length, the lists with their slack)
+    DevBuf<int> gc_groups;
+    bool gc_set = false;
+    int32_t gc_ngroups = 0;
+    DevBuf<int> gc_items, gc_cols, gc_pos, gc_kept, gc_plen, gc_prior;
+    DevBuf<float> gc_scores;
+    DevBuf<long long> gc_pbeg;
+    unsigned tie_ctr = 0;                      // evaluation step counter of the 'tiebreaking' noise stream
     // the last g4r_recommend_events call (g4r_get_debug "events_launches"): its steps, the launches whose grid spans the candidate
     // columns, all its launches, the pieces its lists came back in
     int64_t ev_steps = 0, ev_scans = 0, ev_launches = 0, ev_pieces = 0;
@@ -263,6 +273,15 @@ struct MmrStage {
     float lam; int normalize;
     int k;                               // picks per row
     int32_t* out_pos; float* out_value;  // host, [n][k] next to sessions_run's out_cols / out_scores
+};
+
+// The other optional stage in that place (g4r_recommend_sessions_capped / g4r_continue_sessions_capped; g4r_host_groups.hpp): the
+// selection runs with k = the pool, k_group_cap keeps up to `k` of every list by the cap rule -- with steps >= 1 on every step, between
+// the merge and k_rollout_feed, which is pointed at what it kept -- and the chunk downloads that instead of the pools
+struct CapStage {
+    int cap, k;                                                  // positions of a group a row may keep; entries a row returns per step
+    const int64_t* prior_offs; const int32_t* prior_groups;      // host: every session's prior groups (CSR; NULL: none)
+    int32_t* out_pos; int32_t* out_kept;                         // host: [n][k] (NULL: not wanted), [n][max(steps, 1)]
 };
 
 // every entry that may rewrite Wy / E calls this: the bf16 shadow table of the two-stage top-k and the inverse norms of

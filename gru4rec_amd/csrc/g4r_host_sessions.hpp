@@ -1,6 +1,7 @@
 // g4r_host_sessions.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
 // instantiated there).  Holds: the stateless entries that replay whole histories: the replay (replay_chunks), g4r_recommend_sessions(_scan),
-// g4r_continue_sessions, and the per-row candidate lists (g4r_score_candidates, g4r_score_candidates_sessions).
+// g4r_continue_sessions, the optional stages behind the selection (sessions_run), and the per-row candidate lists (g4r_score_candidates,
+// g4r_score_candidates_sessions).
 // ------------------------------------------------------------------------------------------------ stateless session replay
 // Rows per chunk of g4r_recommend_sessions: its score matrix (softmax / softmax_logit) is then never larger than g4r_recommend_step's
 // at 512 rows.  G4R_SESSIONS_CHUNK > 0 (read per call) forces a smaller chunk: tests show the results do not depend on it.
@@ -161,12 +162,21 @@ static int no_repeat_check(g4r_model* m, const int32_t* item_idx, int64_t n_sel)
 // to the row's exclusion list.  One synchronisation and one download per chunk whatever `steps` is.
 // mmr (g4r_diversify_sessions; steps = 0, k = the pool): k_mmr_rerank picks mmr->k of every row's k selected candidates on the device
 // and the chunk downloads those picks (columns, scores, pool positions, values) instead of the lists.  NULL: nothing is added.
+// caps (g4r_recommend_sessions_capped, g4r_continue_sessions_capped; k = the pool, the caller has run cap_check): k_group_cap keeps up to
+// caps->k of every row's k selected candidates by the cap rule.  steps = 0: the chunk downloads what it kept, with the pool positions
+// and the counts.  steps >= 1: it runs on every step between the merge and k_rollout_feed, which is pointed at the kept lists with
+// their k -- slot 0 is the capped winner --; the rows' prior lists grow on the device like the exclusion lists, and the counts
+// come back as [rows][steps].  NULL: nothing is added.
 static int mmr_prepare(g4r_model* m, const MmrStage& st, int rows);
 static int mmr_enqueue(g4r_model* m, const MmrStage& st, int rows, int pool, const int* d_items, int64_t n_sel);
+static int cap_prepare(g4r_model* m, const CapStage& st, int rows, int n_step);
+static void cap_priors(const CapStage& st, int32_t n, std::vector<long long>& offs, std::vector<int32_t>& groups);
+static int cap_priors_upload(g4r_model* m, int rows, const std::vector<long long>& offs, const std::vector<int32_t>& groups, const std::vector<int32_t>& len);
+static int cap_enqueue(g4r_model* m, const CapStage& st, int rows, int pool, const int* d_items, int64_t n_sel, int steps, int s);
 static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
                         const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample, int32_t steps, int32_t no_repeat,
                         const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask, int32_t* out_cols,
-                        float* out_scores, float* const* out_hidden, const MmrStage* mmr = nullptr) {
+                        float* out_scores, float* const* out_hidden, const MmrStage* mmr = nullptr, const CapStage* caps = nullptr) {
     // ---- every check before any kernel is launched.  cand_upload, among them, stages the candidate items (it may drain the stream, grow
     // p_items and enqueue the copy), and the no_repeat and excl_pack refusals come after it: nothing here has state to advance
     int32_t scan_c = 0;
@@ -185,6 +195,9 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
     const bool excl = excl_offs || excl_mask || grow;
     if (excl && excl_pack(m, n, item_idx, n_sel, k, excl_offs, excl_items, excl_mask, xoffs, xitems, grow ? steps - 1 : 0)) return -1;
     const bool lists = excl_offs || grow;
+    std::vector<long long> poffs;      // caps, steps >= 1: every session's prior groups
+    std::vector<int32_t> pgroups;
+    if (caps && rollout) cap_priors(*caps, n, poffs, pgroups);
     if (rollout) ++m->ro_calls;
     // ---- buffers
     const int C = replay_chunk_rows(n);
@@ -192,17 +205,23 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
     const bool sm = is_softmax(d);
     const int64_t ldo = (n_sel + 3) & ~3LL;
     if (sm && m->r_scores.reserve(m, (int64_t)C * ldo)) return -1;
-    const int64_t per_row = mmr ? mmr->k : (int64_t)n_step * k;      // entries a row downloads
+    const int ko = caps ? caps->k : k;                               // entries of a row's list as it leaves
+    const int64_t per_row = mmr ? mmr->k : (int64_t)n_step * ko;     // entries a row downloads
     if (mmr && mmr_prepare(m, *mmr, C)) return -1;
+    if (caps && cap_prepare(m, *caps, C, n_step)) return -1;
     if (rollout && (m->ro_cols.reserve(m, (int64_t)C * per_row) || m->ro_scores.reserve(m, (int64_t)C * per_row) || m->ro_in.reserve(m, (int64_t)C) ||
                     (grow && m->ro_xlen.reserve(m, (int64_t)C))))
         return -1;
     std::vector<int32_t> tcols((size_t)C * per_row);
     std::vector<float> tscores((size_t)C * per_row);
-    std::vector<int32_t> tpos(mmr ? (size_t)C * per_row : 0);
+    const bool cpos = caps && !rollout && caps->out_pos;
+    std::vector<int32_t> tpos(mmr || cpos ? (size_t)C * per_row : 0);
+    std::vector<int32_t> tkept(caps ? (size_t)C * n_step : 0);
     std::vector<float> tval(mmr ? (size_t)C * per_row : 0);
     std::vector<long long> coffs;
     std::vector<int32_t> citems, clen;
+    std::vector<long long> pcoffs;
+    std::vector<int32_t> pcgroups, pclen;
     const GruBufs rb = replay_bufs(m);
     int final_half = -1;
     // ---- chunk by chunk: the replay, then the selections; one synchronisation per chunk
@@ -216,6 +235,10 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
                 HIPCHK(hipMemcpyAsync(m->ro_xlen.p, clen.data(), (size_t)Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
                 gx = TkGrow{ex.offs, (const int*)m->ro_xlen.p, ex.items, ex.mask};
             }
+        }
+        if (caps && rollout) {      // the prior lists through the same packer and permutation, steps - 1 slots of slack behind each
+            excl_chunk(poffs, pgroups, caps->prior_offs != nullptr, c0, Cc, perm, steps - 1, pcoffs, pcgroups, pclen);
+            if (cap_priors_upload(m, Cc, pcoffs, pcgroups, pclen)) return -1;
         }
         const TkExcl* exp = (excl && !grow) ? &ex : nullptr;
         const TkGrow* gxp = grow ? &gx : nullptr;
@@ -233,9 +256,11 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
             if (scan_c > 0) {
                 if (topk_select_scan(m, hsrc, Cc, d_items, n_sel, k, scan_c, exp, gxp, s > 0)) return -1;
             } else if (topk_select(m, hsrc, Cc, d_items, n_sel, k, exp, (const float*)m->r_scores.p, ldo, gxp)) return -1;
+            if (caps && cap_enqueue(m, *caps, Cc, k, d_items, n_sel, steps, s)) return -1;
             if (rollout) {
                 const bool last = s == steps - 1;
-                hipLaunchKernelGGL(k_rollout_feed, dim3(Cc), dim3(64), 0, m->stream, (const int*)m->p_tcols.p, (const float*)m->p_tscores.p, (int)k,
+                hipLaunchKernelGGL(k_rollout_feed, dim3(Cc), dim3(64), 0, m->stream, caps ? (const int*)m->gc_cols.p : (const int*)m->p_tcols.p,
+                                   caps ? (const float*)m->gc_scores.p : (const float*)m->p_tscores.p, ko,
                                    (int)steps, s, d_items, m->ro_cols.p, m->ro_scores.p, last ? (int*)nullptr : m->ro_in.p, gx.beg,
                                    last ? (int*)nullptr : const_cast<int*>(gx.len), const_cast<int*>(gx.items));      // (gx: all NULL unless the lists grow)
             }
@@ -246,8 +271,12 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
             HIPCHK(hipMemcpyAsync(tpos.data(), m->dv_pos.p, (size_t)Cc * per_row * sizeof(int), hipMemcpyDeviceToHost, m->stream));
             HIPCHK(hipMemcpyAsync(tval.data(), m->dv_val.p, (size_t)Cc * per_row * sizeof(float), hipMemcpyDeviceToHost, m->stream));
         }
-        HIPCHK(hipMemcpyAsync(tcols.data(), mmr ? m->dv_cols.p : rollout ? m->ro_cols.p : m->p_tcols.p, (size_t)Cc * per_row * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipMemcpyAsync(tscores.data(), mmr ? m->dv_scores.p : rollout ? m->ro_scores.p : m->p_tscores.p, (size_t)Cc * per_row * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        if (caps) {
+            if (cpos) HIPCHK(hipMemcpyAsync(tpos.data(), m->gc_pos.p, (size_t)Cc * per_row * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+            HIPCHK(hipMemcpyAsync(tkept.data(), m->gc_kept.p, (size_t)Cc * n_step * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        }
+        HIPCHK(hipMemcpyAsync(tcols.data(), mmr ? m->dv_cols.p : rollout ? m->ro_cols.p : caps ? m->gc_cols.p : m->p_tcols.p, (size_t)Cc * per_row * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(tscores.data(), mmr ? m->dv_scores.p : rollout ? m->ro_scores.p : caps ? m->gc_scores.p : m->p_tscores.p, (size_t)Cc * per_row * sizeof(float), hipMemcpyDeviceToHost, m->stream));
         return 0;
     };
     // sorted row r is session c0 + perm[r]
@@ -258,6 +287,10 @@ static int sessions_run(g4r_model* m, const int64_t* hist_offs, const int32_t* h
             if (mmr) {
                 memcpy(mmr->out_pos + (size_t)(c0 + perm[r]) * per_row, tpos.data() + (size_t)r * per_row, (size_t)per_row * sizeof(int32_t));
                 memcpy(mmr->out_value + (size_t)(c0 + perm[r]) * per_row, tval.data() + (size_t)r * per_row, (size_t)per_row * sizeof(float));
+            }
+            if (caps) {
+                if (cpos) memcpy(caps->out_pos + (size_t)(c0 + perm[r]) * per_row, tpos.data() + (size_t)r * per_row, (size_t)per_row * sizeof(int32_t));
+                memcpy(caps->out_kept + (size_t)(c0 + perm[r]) * n_step, tkept.data() + (size_t)r * n_step, (size_t)n_step * sizeof(int32_t));
             }
         }
     };

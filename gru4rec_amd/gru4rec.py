@@ -201,6 +201,9 @@ class GRU4Rec:
         # flush launch runs at ~60 % of the HBM peak at BASELINE configs[2] -- and the step gets 2-5 % slower: off
         # unless asked for
         self.defer_updates = False
+        # item groups (set_item_groups): int32[n_items] aligned with itemidmap, -1 = ungrouped, and the labels in group-index order
+        self.item_groups = None
+        self.group_labels = None
         self._model = None
         self._dist = None
         self._cpu_store = False
@@ -417,6 +420,8 @@ class GRU4Rec:
             if os.environ.get('G4R_P2P') == '1' and nranks <= 8:
                 # the switch next to the RCCL all-reduce: every rank reads its peers' gradients over xGMI itself (g4r_p2p_enable)
                 m.p2p_enable()
+        if getattr(self, 'item_groups', None) is not None:
+            m.set_item_groups(self.item_groups)
         return m
 
     # ---- device layout: the library wants layer / embedding widths that are multiples of 4 (16-byte rows).  Other widths are
@@ -589,6 +594,9 @@ class GRU4Rec:
                     ', '.join(diff), ', '.join('%s=%r' % (k, saved_cfg[k]) for k in diff)))
             if self.train_random_order and self.optimizer_state.get('np_random_state') is None:
                 raise ValueError('resume=True with train_random_order: the checkpoint does not hold the random stream of the session order')
+        if getattr(self, 'item_groups', None) is not None and not (
+                len(itemids) == len(self.item_groups) and np.array_equal(np.asarray(itemidmap.index), np.asarray(self.itemidmap.index))):
+            self.item_groups = self.group_labels = None      # groups of another item map: set them again after fit
         self.n_items = len(itemids)
         self.itemidmap = itemidmap
         datatools.sort_if_needed(data, [self.session_key, self.time_key])
@@ -870,10 +878,11 @@ class GRU4Rec:
         seen = self._seen_after(plan) if exclude_seen else None
         return self._pack_exclusions(len(np.ravel(plan[3])), k, cand_idx, seen, 'the items seen', exclude, exclude_per_row)
 
-    def _pack_exclusions(self, rows, k, cand_idx, extra, extra_name, exclude, exclude_per_row, grow=0):
+    def _pack_exclusions(self, rows, k, cand_idx, extra, extra_name, exclude, exclude_per_row, grow=0, exclude_groups=None):
         """_exclusions for `rows` rows; extra: (rows, item indices) the call adds to the per-row lists (the items seen, the
         histories) or None; extra_name names them in the G4R_EXCLUDE_MAX error.  grow (continue_sessions with no_repeat): the items
-        every row's list gains on the device, one eligible candidate position each."""
+        every row's list gains on the device, one eligible candidate position each.  exclude_groups: group labels whose items join
+        `exclude`."""
         n_items = len(self.itemidmap)
         pr, pi = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
         if exclude_per_row is not None:
@@ -887,7 +896,7 @@ class GRU4Rec:
         if extra is not None:
             pr.append(np.asarray(extra[0], dtype=np.int64))
             pi.append(np.asarray(extra[1], dtype=np.int64))
-        gidx, mask = self._global_exclude(exclude)
+        gidx, mask = self._global_exclude(exclude, exclude_groups)
         key = np.unique(np.concatenate(pr) * n_items + np.concatenate(pi))
         r, it = key // n_items, key % n_items
         counts = np.bincount(r, minlength=rows)
@@ -923,30 +932,34 @@ class GRU4Rec:
             items = it.astype(np.int32)
         return offs, items, mask
 
-    def _global_exclude(self, exclude):
-        """`exclude`, the item ids excluded in every row, as (their distinct item indices, sorted, int64; the bit mask of
-        g4r_recommend_step_filtered over them, None when there are none)."""
+    def _global_exclude(self, exclude, exclude_groups=None):
+        """`exclude`, the item ids excluded in every row, and `exclude_groups`, the group labels all of whose items are, as (their
+        distinct item indices, sorted, int64; the bit mask of g4r_recommend_step_filtered over them, None when there are none)."""
         gidx, mask = np.zeros(0, dtype=np.int64), None
         if exclude is not None:
             ex = exclude if isinstance(exclude, np.ndarray) else list(exclude)
             if len(ex):
                 gidx = np.unique(self.itemidmap[np.ravel(ex)].values.astype(np.int64))
-                mask = np.zeros((len(self.itemidmap) + 31) // 32, dtype=np.uint32)
-                np.bitwise_or.at(mask, gidx >> 5, np.left_shift(1, gidx & 31).astype(np.uint32))
+        if exclude_groups is not None:
+            gi = self._group_indices(exclude_groups, 'exclude_groups')
+            gidx = np.union1d(gidx, np.flatnonzero(np.isin(self.item_groups, gi))).astype(np.int64)
+        if len(gidx):
+            mask = np.zeros((len(self.itemidmap) + 31) // 32, dtype=np.uint32)
+            np.bitwise_or.at(mask, gidx >> 5, np.left_shift(1, gidx & 31).astype(np.uint32))
         return gidx, mask
 
-    def _session_exclusions(self, N, lens, hidx, k, iidx, history, exclude, exclude_per_row, steps=None):
+    def _session_exclusions(self, N, lens, hidx, k, iidx, history, exclude, exclude_per_row, steps=None, exclude_groups=None):
         """_pack_exclusions for a stateless call over N histories (lengths lens, item indices hidx).  history: every row's list holds
         its own history (exclude_history, no_repeat).  steps (None: the call generates nothing): with history, every row's list gains
         steps - 1 generated items on the device, which needs duplicate-free candidates."""
         if steps is not None and history and iidx is not None and len(np.unique(iidx)) != len(iidx):
             raise ValueError('no_repeat needs duplicate-free predict_for_item_ids: every generated item must take exactly one candidate '
                              'position')
-        if not history and exclude is None and exclude_per_row is None:
+        if not history and exclude is None and exclude_per_row is None and exclude_groups is None:
             return None, None, None
         hist_rows = (np.repeat(np.arange(N), lens), hidx) if history else None
         return self._pack_exclusions(N, k, iidx, hist_rows, 'the history', exclude, exclude_per_row,
-                                     grow=steps - 1 if steps is not None and history else 0)
+                                     grow=steps - 1 if steps is not None and history else 0, exclude_groups=exclude_groups)
 
     def _n_candidates(self, predict_for_item_ids):
         return len(self.itemidmap) if predict_for_item_ids is None else len(predict_for_item_ids)
@@ -1059,7 +1072,7 @@ class GRU4Rec:
         return N, lens, offs, hidx, h0
 
     def recommend_sessions(self, histories, k=20, predict_for_item_ids=None, exclude_history=False, exclude=None, exclude_per_row=None,
-                           hidden=None, return_hidden=False, scan='fp32', oversample=8):
+                           hidden=None, return_hidden=False, scan='fp32', oversample=8, max_per_group=None, pool=None, exclude_groups=None):
         """Top-k next items of N whole sessions in one stateless call: (item_ids[N, k], scores[N, k] float32), plus the new hidden
         state with return_hidden=True.  Not in the reference.
 
@@ -1072,6 +1085,19 @@ class GRU4Rec:
           predict_for_item_ids, exclude, exclude_per_row, k: as in recommend_next_batch (exclude_per_row: N lists).
           scan, oversample as in recommend_next_batch: scan='bf16' is the two-stage selection (bf16 scan, exact fp32 re-rank); the
                            replay, and so the returned hidden state, is the same either way.
+          exclude_groups   group labels (set_item_groups): every item of these groups joins `exclude`.
+          max_per_group    None: nothing changes.  An integer c >= 1 (it needs set_item_groups): a row receives at most c items of one
+                           group, and the call returns (item_ids[N, k], scores[N, k], n_kept[N] int32), plus the hidden state when
+                           asked.  The row's pool is what this call returns with k = pool and max_per_group=None; the walk down the
+                           pool keeps an item iff it is ungrouped or fewer than c items of its group were kept before it, and
+                           stops after k kept items (the cap rule of include/gru4rec_hip.h, on the device behind the selection).
+                           n_kept[i] <= k is the number kept; entries at and after it have score NaN and an unspecified id (that
+                           of candidate 0).  Scores are recommend_sessions' bit patterns.  A row is exact over the WHOLE catalogue
+                           when n_kept[i] == k -- the walk finished inside the pool, so a longer pool would not change it -- and
+                           when pool equals the row's eligible candidate positions; otherwise a longer pool may add items.
+          pool             the pool of max_per_group, k <= pool <= min(number of candidates, G4R_TOPK_MAX = 256); None:
+                           min(G4R_TOPK_MAX, number of candidates, 4 * k).  The k / exclusion / oversample checks then apply with
+                           k = pool: every session needs `pool` eligible candidate positions.
 
         Row i equals, items and score bits, what recommend_next_batch returns for a session whose first T - 1 items went through
         predict_next_batch from a fresh prediction state and whose last item is the recommend_next_batch input (exclude_history as
@@ -1083,18 +1109,25 @@ class GRU4Rec:
         if self.error_during_train:
             raise Exception
         k = _check_k(k, self._n_candidates(predict_for_item_ids), bools=True)
-        over = self._scan_oversample(scan, oversample, k)
+        cap, pool = self._cap_args(max_per_group, pool, k, self._n_candidates(predict_for_item_ids))
+        ksel = k if cap is None else pool      # what the selection returns per row
+        over = self._scan_oversample(scan, oversample, ksel)
         N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
         iidx, cand = self._candidates(predict_for_item_ids)
-        excl = self._session_exclusions(N, lens, hidx, k, iidx, exclude_history, exclude, exclude_per_row)
+        excl = self._session_exclusions(N, lens, hidx, ksel, iidx, exclude_history, exclude, exclude_per_row, exclude_groups=exclude_groups)
         m = self._ensure_model()
+        if cap is not None:
+            out = m.recommend_sessions_capped(offs, hidx, iidx, k, pool, cap, *excl, hidden=h0, return_hidden=return_hidden, oversample=over)
+            res = (cand[np.maximum(out[0], 0)], out[1], out[3])
+            return res + (self._unpad_hidden(out[4]),) if return_hidden else res
         out = m.recommend_sessions(offs, hidx, iidx, k, *excl, hidden=h0, return_hidden=return_hidden, **_scan_kw(over))
         if not return_hidden:
             return cand[out[0]], out[1]
         return cand[out[0]], out[1], self._unpad_hidden(out[2])
 
     def continue_sessions(self, histories, steps, k=1, no_repeat=True, predict_for_item_ids=None, exclude=None, exclude_per_row=None,
-                          hidden=None, return_hidden=False, scan='fp32', oversample=8):
+                          hidden=None, return_hidden=False, scan='fp32', oversample=8, max_per_group=None, pool=None, count_history=False,
+                          exclude_groups=None):
         """The next `steps` items of N whole sessions in one stateless call: (item_ids[N, steps, k], scores[N, steps, k] float32),
         plus the hidden state with return_hidden=True.  Not in the reference.
 
@@ -1114,6 +1147,18 @@ class GRU4Rec:
                            continue_sessions([[path[i, a - 1]]], b, hidden=H_a, exclude_per_row=h_i + path[i, :a]).
           k, predict_for_item_ids, exclude, exclude_per_row, hidden, scan, oversample: as in recommend_sessions, with its refusals.
                            softmax / softmax_logit scores are not renormalised over the remaining items.
+          exclude_groups   as in recommend_sessions.
+          max_per_group    None: nothing changes.  An integer c >= 1 (it needs set_item_groups): at most c items of one group along a
+                           row's path, and the call returns (item_ids[N, steps, k], scores[N, steps, k], n_kept[N, steps] int32),
+                           plus the hidden state when asked.  Every step selects `pool` items (pool as in recommend_sessions, the
+                           checks with k = pool) and recommend_sessions' walk keeps up to k of them, counting on top of the row's
+                           prior: the groups of the winners of the steps before, plus the groups of histories[i] with
+                           count_history=True.  [:, s, 0], the first kept item, is the winner that is fed back.  n_kept[i, s] == 0
+                           marks a fallback step: the pool held no item the cap allows, column 0 is then the unconstrained best (it
+                           is fed back, and its group counts like any winner's) and the other columns are pads.  The walk, the
+                           prior and the feedback stay on the device.  The result equals the loop of recommend_sessions(k=pool)
+                           calls described above with the walk on the host between them.  A row's prior plus steps - 1 may not
+                           exceed G4R_GROUP_PRIOR_MAX = 1024 groups.
 
         Everything is checked before any device work and the prediction state is neither read nor changed.  steps must be an integer
         >= 1.  With no_repeat, predict_for_item_ids must be duplicate-free (every fed-back item then removes exactly one eligible
@@ -1124,10 +1169,19 @@ class GRU4Rec:
             raise Exception
         steps = _check_steps(steps)
         k = _check_k(k, self._n_candidates(predict_for_item_ids), bools=True)
-        over = self._scan_oversample(scan, oversample, k)
+        cap, pool = self._cap_args(max_per_group, pool, k, self._n_candidates(predict_for_item_ids), count_history)
+        ksel = k if cap is None else pool
+        over = self._scan_oversample(scan, oversample, ksel)
         N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
         iidx, cand = self._candidates(predict_for_item_ids)
-        excl = self._session_exclusions(N, lens, hidx, k, iidx, no_repeat, exclude, exclude_per_row, steps=steps)
+        excl = self._session_exclusions(N, lens, hidx, ksel, iidx, no_repeat, exclude, exclude_per_row, steps=steps, exclude_groups=exclude_groups)
+        if cap is not None:
+            prior = self._prior_groups(N, (np.repeat(np.arange(N), lens), hidx) if count_history else None, steps - 1)
+            m = self._ensure_model()
+            out = m.continue_sessions_capped(offs, hidx, iidx, k, pool, cap, steps, bool(no_repeat), *excl, *prior, hidden=h0,
+                                             return_hidden=return_hidden, oversample=over)
+            res = (cand[np.maximum(out[0], 0)], out[1], out[2])
+            return res + (self._unpad_hidden(out[3]),) if return_hidden else res
         m = self._ensure_model()
         out = m.continue_sessions(offs, hidx, iidx, k, steps, bool(no_repeat), *excl, hidden=h0, return_hidden=return_hidden, oversample=over)
         if not return_hidden:
@@ -1513,7 +1567,7 @@ class GRU4Rec:
 
     def diversify_sessions(self, histories, k=20, pool=100, trade_off=0.7, metric='cosine', space='output', normalize=True,
                            predict_for_item_ids=None, exclude_history=False, exclude=None, exclude_per_row=None, hidden=None,
-                           return_hidden=False, scan='fp32', oversample=8, return_details=False):
+                           return_hidden=False, scan='fp32', oversample=8, return_details=False, exclude_groups=None):
         """Diversified top-k next items of N whole sessions in one stateless call: (item_ids[N, k], scores[N, k] float32).  Not in
         the reference.  Maximal marginal relevance: the pool of a session is what recommend_sessions(k=pool) returns for it with the
         same histories, candidates, exclusions, hidden and scan arguments; k of the pool are picked greedily on the device, each pick
@@ -1532,7 +1586,7 @@ class GRU4Rec:
         nor changed.  Everything is checked before any device work: ValueError for a k outside [1, pool], a pool outside
         [1, min(number of candidates, G4R_DIVERSIFY_POOL_MAX = 128)], a trade_off outside [0, 1], a bad metric or space, and
         recommend_sessions' own refusals with k = pool (every session needs `pool` eligible candidate positions); KeyError for an
-        unknown item id; NotImplementedError for space='input' on a one-hot input model."""
+        unknown item id; NotImplementedError for space='input' on a one-hot input model.  exclude_groups: as in recommend_sessions."""
         if self.error_during_train:
             raise Exception
         pool = _check_k(pool, self._n_candidates(predict_for_item_ids), name='pool', cap=_native.G4R_DIVERSIFY_POOL_MAX)
@@ -1541,7 +1595,7 @@ class GRU4Rec:
         over = self._scan_oversample(scan, oversample, pool)
         N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
         iidx, cand = self._candidates(predict_for_item_ids)
-        excl = self._session_exclusions(N, lens, hidx, pool, iidx, exclude_history, exclude, exclude_per_row)
+        excl = self._session_exclusions(N, lens, hidx, pool, iidx, exclude_history, exclude, exclude_per_row, exclude_groups=exclude_groups)
         m = self._ensure_model()
         out = m.diversify_sessions(offs, hidx, iidx, k, pool, lam, metric, space, bool(normalize), *excl, hidden=h0,
                                    return_hidden=return_hidden, **_scan_kw(over))
@@ -1595,6 +1649,133 @@ class GRU4Rec:
         m = self._ensure_model()
         return m.diversify_lists(idx, rel32, k, lam, metric, space, bool(normalize))
 
+    # ------------------------------------------------------------------ item groups, per-group caps (not in the reference)
+    def set_item_groups(self, groups):
+        """Gives the items their groups (a brand, an artist, a category, a parent product): a dict or pandas.Series mapping item id ->
+        group label, any hashable; None clears them.  Items of the model that are not mentioned are ungrouped and never capped; an id
+        the model does not know raises KeyError, a call before the model has an itemidmap (before fit / loadmodel) ValueError.
+        Stores item_groups (int32[n_items] aligned with itemidmap, -1 = ungrouped, otherwise a dense group index) and group_labels
+        (the labels in group-index order); both are pickled with the model and uploaded to the device model, now if there is one.
+        Used by max_per_group / exclude_groups of recommend_sessions, continue_sessions, diversify_sessions and by cap_lists.  fit on
+        data with another item map drops them."""
+        if groups is None:
+            self.item_groups = self.group_labels = None
+            if self._model is not None:
+                self._model.set_item_groups(None)
+            return
+        if getattr(self, 'itemidmap', None) is None:
+            raise ValueError('set_item_groups needs the item id map of a fitted or loaded model')
+        if isinstance(groups, pd.Series):
+            ids, labels = groups.index.values, groups.tolist()
+        elif isinstance(groups, dict):
+            ids, labels = list(groups.keys()), list(groups.values())
+        else:
+            raise ValueError('groups must be a dict or a pandas.Series mapping item id -> group label, or None')
+        idx = self.itemidmap[ids].values.astype(np.int64) if len(ids) else np.zeros(0, dtype=np.int64)
+        index_of = {}
+        table = np.full(len(self.itemidmap), -1, dtype=np.int32)
+        table[idx] = [index_of.setdefault(lab, len(index_of)) for lab in labels]
+        arr = np.empty(len(index_of), dtype=object)
+        for lab, i in index_of.items():
+            arr[i] = lab
+        try:
+            plain = np.asarray(list(index_of))
+            if plain.shape == arr.shape and plain.dtype != object and plain.tolist() == list(index_of):
+                arr = plain      # labels of one plain type: an array of that type
+        except (TypeError, ValueError):
+            pass
+        self.item_groups, self.group_labels = table, arr
+        if self._model is not None:
+            self._model.set_item_groups(table)
+
+    def _group_indices(self, labels, name):
+        """Group labels -> their group indices (int64); ValueError without groups, KeyError for an unknown label."""
+        if getattr(self, 'item_groups', None) is None:
+            raise ValueError('%s needs item groups: call set_item_groups first' % name)
+        index_of = {lab: i for i, lab in enumerate(self.group_labels.tolist())}
+        lab = labels.tolist() if isinstance(labels, np.ndarray) else list(labels)
+        missing = [x for x in lab if x not in index_of]
+        if missing:
+            raise KeyError('%s: unknown group label %r' % (name, missing[0]))
+        return np.array([index_of[x] for x in lab], dtype=np.int64)
+
+    def _cap_args(self, max_per_group, pool, k, n_cand, count_history=False):
+        """The checks of max_per_group / pool (after the k check): (cap, pool) as ints, (None, None) without max_per_group."""
+        if max_per_group is None:
+            if pool is not None or count_history:
+                raise ValueError('pool and count_history belong to max_per_group, which is None')
+            return None, None
+        if getattr(self, 'item_groups', None) is None:
+            raise ValueError('max_per_group needs item groups: call set_item_groups first')
+        try:
+            ok = not isinstance(max_per_group, bool) and int(max_per_group) == max_per_group and 1 <= max_per_group <= 2 ** 31 - 1
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('max_per_group = %r: it must be None or an integer >= 1' % (max_per_group,))
+        if pool is None:
+            pool = min(_native.G4R_TOPK_MAX, n_cand, 4 * k)
+        else:
+            pool = _check_k(pool, n_cand, name='pool', own_errors=True)
+            if k > pool:
+                raise ValueError('k = %r: it must be an integer in [1, pool = %d]' % (k, pool))
+        return int(max_per_group), pool
+
+    def _prior_groups(self, N, extra, grow):
+        """The prior lists of N rows as (offsets int64[N + 1], group indices int32): the groups of `extra` = (rows, item indices),
+        ungrouped items dropped (None: every list is empty).  grow: the groups every list gains on the device."""
+        counts, gg = np.zeros(N, dtype=np.int64), np.zeros(0, dtype=np.int32)
+        if extra is not None:
+            rows, g = np.asarray(extra[0], dtype=np.int64), self.item_groups[np.asarray(extra[1], dtype=np.int64)]
+            order = np.argsort(rows[g >= 0], kind='stable')
+            gg = g[g >= 0][order].astype(np.int32)
+            counts = np.bincount(rows[g >= 0], minlength=N)
+        big = np.flatnonzero(counts + grow > _native.G4R_GROUP_PRIOR_MAX)
+        if len(big):
+            raise ValueError('row %d has %d prior groups%s, more than G4R_GROUP_PRIOR_MAX = %d' % (
+                big[0], counts[big[0]], ' and gains steps - 1 = %d more' % grow if grow else '', _native.G4R_GROUP_PRIOR_MAX))
+        return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), gg
+
+    def cap_lists(self, item_lists, k, max_per_group, prior=None):
+        """The walk of recommend_sessions(max_per_group=) for lists from any source: (pos[N, k] int32, n_kept[N] int32).  Not in the
+        reference.
+
+          item_lists     [N, P] item ids in rank order, 1 <= P <= G4R_TOPK_MAX = 256; duplicates allowed, every position counts.
+          max_per_group  the cap c >= 1 (it needs set_item_groups).
+          prior          None, or N sequences of item ids whose groups count against the cap before the list starts (what a page
+                         already shows); at most G4R_GROUP_PRIOR_MAX = 1024 grouped items per row.
+        Row i keeps position j iff its item is ungrouped or fewer than c positions of its group lie in the prior and ahead of j in
+        the list; pos[i] holds the first k kept positions in list order, then -1, n_kept[i] their number.  Stateless.  Everything is
+        checked before any device work: ragged lists, a P, k or max_per_group out of range, a prior of the wrong length raise
+        ValueError, an unknown item id KeyError."""
+        if self.error_during_train:
+            raise Exception
+        try:
+            ids = np.asarray(item_lists)
+        except (TypeError, ValueError):
+            ids = None
+        if ids is None or ids.dtype == object or ids.ndim != 2 or ids.shape[0] < 1:
+            raise ValueError('item_lists must be an [N, P] array, N >= 1 (ragged lists are not supported)')
+        N, P = ids.shape
+        if not 1 <= P <= _native.G4R_TOPK_MAX:
+            raise ValueError('the lists hold P = %d items: between 1 and G4R_TOPK_MAX = %d are needed' % (P, _native.G4R_TOPK_MAX))
+        k = self._mmr_k(k, P)
+        if max_per_group is None:
+            raise ValueError('max_per_group = None: it must be an integer >= 1')
+        cap, _ = self._cap_args(max_per_group, P, k, P)
+        idx = self.itemidmap[ids.ravel()].values.astype(np.int32).reshape(ids.shape)
+        extra = None
+        if prior is not None:
+            if len(prior) != N:
+                raise ValueError('prior holds %d lists, one per row (%d) is needed' % (len(prior), N))
+            lists = [np.ravel(x) if isinstance(x, np.ndarray) else list(x) for x in prior]
+            lens = np.array([len(x) for x in lists], dtype=np.int64)
+            flat = np.concatenate([np.asarray(x) for x in lists if len(x)]) if lens.sum() else np.zeros(0, dtype=np.int64)
+            extra = (np.repeat(np.arange(N), lens), self.itemidmap[flat].values if len(flat) else flat)
+        po, pg = self._prior_groups(N, extra, 0)
+        m = self._ensure_model()
+        return m.cap_lists(idx, k, cap, po, pg)
+
     def symbolic_predict(self, X, Y, M, items, batch_size):
         raise NotImplementedError('symbolic_predict builds a Theano graph (gru4rec.py:729-741); the MI355X path '
                                   'exposes the same computation through gru4rec_amd.evaluation.evaluate_gpu')
@@ -1618,6 +1799,8 @@ class GRU4Rec:
         self.__dict__.setdefault('optimizer_state', None)
         self.__dict__.setdefault('epochs_done', 0)
         self.__dict__.setdefault('error_during_train', False)
+        self.__dict__.setdefault('item_groups', None)
+        self.__dict__.setdefault('group_labels', None)
         self.set_loss_function(self.loss)
         self.set_final_activation(self.final_act)
         self.set_hidden_activation(self.hidden_act)

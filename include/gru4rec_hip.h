@@ -400,6 +400,58 @@ int g4r_diversify_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t
                            int32_t metric, float lam, int32_t normalize, int32_t* out_cols, float* out_scores, int32_t* out_pos,
                            float* out_value, float* const* out_hidden);
 
+/* not in the reference: item groups (a brand, an artist, a category, a parent product) and per-group caps: "at most c per group" in a
+ * top-k list or along a generated path.
+ *
+ * g4r_set_item_groups gives the model its group table: groups[n], n == n_items, entry i the dense group index of item i or -1 for an
+ * ungrouped item (never capped); an entry below -1 is refused.  groups NULL with n 0 clears the table.  The number of groups is the
+ * largest entry + 1.  The table is a device array of the model that only grows; it does not depend on the weights (no entry that
+ * changes them touches it) and g4r_destroy frees it.  g4r_get_item_groups copies it back (out[n], n == n_items; refused without one).
+ *
+ * The cap rule.  A row has a list of P positions in selection order, position j with the column c_j and the score s_j; its item is
+ * i_j = item_idx[c_j] (c_j itself without item_idx) and its group g_j = groups[i_j].  With a cap c >= 1 and a prior multiset of
+ * groups (possibly empty; n0(g) the number of times g occurs in it), position j is KEPT iff
+ *     g_j < 0   or   n0(g_j) + #{i < j : g_i == g_j} < c
+ * -- the greedy walk down the list with one counter per group.  The result is the first min(k, kept) kept positions in list order:
+ * n_kept is that count, entries at and after n_kept are pads (column -1, score NaN, position -1).  Scores are copied, never
+ * recomputed: a returned score is g4r_recommend_sessions' bit pattern.  1 <= k <= P <= G4R_TOPK_MAX; a prior list holds at most
+ * G4R_GROUP_PRIOR_MAX entries, each in [0, number of groups).
+ *
+ * g4r_recommend_sessions_capped takes the arguments of g4r_recommend_sessions_scan with k = pool (oversample = 0: the exact selection;
+ * otherwise the bf16 scan with pool * oversample <= G4R_SCAN_CAND_MAX): the list of session i is what that call returns for it, the
+ * prior is empty, and the rule runs on the device behind the selection.  out_cols / out_scores / out_pos[n * k] receive the kept
+ * positions' columns, scores and positions in the pool, out_kept[n] the counts, out_hidden as there.  A row with out_kept == k is
+ * exact over the whole catalogue (the walk ended inside the pool); so is one whose pool held all its eligible positions.
+ *
+ * g4r_continue_sessions_capped takes the arguments of g4r_continue_sessions the same way: every step selects `pool` positions, the
+ * rule keeps up to k of them -- out_cols / out_scores[n * steps * k], out_kept[n * steps] -- and the first kept one is the winner:
+ * it is fed back as the row's next input, joins the exclusion list with no_repeat as there, and its group, if it has one, joins
+ * the row's prior.  The prior of session i at step 0 is prior_groups[prior_offs[i] .. prior_offs[i + 1]) (prior_offs NULL: empty).
+ * A step at which the rule keeps nothing (out_kept == 0) falls back to the unconstrained best: list position 0 leaves in slot 0,
+ * is fed back, and its group joins the prior like any winner's.  Every row needs pool + steps - 1 eligible candidate positions with
+ * no_repeat, and a prior list plus steps - 1 must not exceed G4R_GROUP_PRIOR_MAX.
+ *
+ * g4r_cap_lists applies the rule to n supplied lists items[n * P] (item indices, duplicates allowed), each with its own prior
+ * (prior_offs NULL: none): out_pos[n * k] and out_kept[n].  Stateless; rows go in chunks, one synchronisation each.
+ *
+ * Everything is checked before any device work, each refusal naming the limit or the row: no group table, cap < 1, pool outside
+ * [1, G4R_TOPK_MAX], k outside [1, pool], a prior list too long, a prior group out of range, and the refusals of the uncapped entry
+ * with k = pool.  The prediction state is neither read nor changed. */
+#define G4R_GROUP_PRIOR_MAX 1024
+int g4r_set_item_groups(g4r_model* m, const int32_t* groups, int64_t n);
+int g4r_get_item_groups(g4r_model* m, int32_t* out, int64_t n);
+int g4r_recommend_sessions_capped(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                                  const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t pool, int32_t oversample,
+                                  const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask, int32_t cap,
+                                  int32_t* out_cols, float* out_scores, int32_t* out_pos, int32_t* out_kept, float* const* out_hidden);
+int g4r_continue_sessions_capped(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                                 const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t pool, int32_t oversample, int32_t steps,
+                                 int32_t no_repeat, const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask,
+                                 int32_t cap, const int64_t* prior_offs, const int32_t* prior_groups, int32_t* out_cols,
+                                 float* out_scores, int32_t* out_kept, float* const* out_hidden);
+int g4r_cap_lists(g4r_model* m, const int32_t* items, int64_t n, int32_t P, int32_t k, int32_t cap, const int64_t* prior_offs,
+                  const int32_t* prior_groups, int32_t* out_pos, int32_t* out_kept);
+
 /* not in the reference: scores of per-row candidate lists (the re-ranking stage behind a retrieval stage).  Row r's list is the
  * item indices cand_items[cand_offs[r] .. cand_offs[r + 1]) (at least one; cand_offs rises strictly; duplicates allowed, every
  * position is scored), at most G4R_CAND_MAX positions in all.  g4r_score_candidates advances the prediction state exactly as

@@ -49,12 +49,16 @@ NEIGHBOR_OPTIONS = [
     (None, '--neighbors_k', dict(metavar='K', type=int, default=20, help='neighbours per item of --save_neighbors (default 20)')),
     (None, '--neighbors_metric', dict(metavar='METRIC', choices=['cosine', 'dot'], default='cosine', help='similarity of --save_neighbors (default cosine)')),
 ]
+# item groups (not in the reference): a table of their own as well
+GROUP_OPTIONS = [
+    (None, '--item_groups', dict(metavar='FILE', help='after training or loading (not in the reference): a TAB separated file of two columns, item id and group label, without a header; the groups are set on the model (GRU4Rec.set_item_groups: max_per_group / exclude_groups of the recommendation calls), so a model saved with -s carries them.  --save_recs is unaffected')),
+]
 
 
 def build_parser():
     ap = argparse.ArgumentParser(description='Train a GRU4Rec model on an MI355X (or load one) and report Recall@N / MRR@N.')
     ap.add_argument('path', metavar='PATH', help='training data (.tsv / .txt with TAB separators, or a pickled DataFrame) -- or the model file when -l is given')
-    for short, long_, kw in OPTIONS + NEIGHBOR_OPTIONS:
+    for short, long_, kw in OPTIONS + NEIGHBOR_OPTIONS + GROUP_OPTIONS:
         ap.add_argument(*([short, long_] if short else [long_]), **kw)
     return ap
 
@@ -104,6 +108,20 @@ def hyper_parameters(opts):
     return OrderedDict(item.split('=') for item in opts.parameter_string.split(','))
 
 
+def set_item_groups(model, fname):
+    """--item_groups: the (item id, group label) rows of a TAB separated file onto the model; items of the file the model does not
+    know are dropped (a catalogue file usually lists more than the training data holds)."""
+    import pandas as pd
+    if not hasattr(model, 'set_item_groups'):
+        print('ERROR. The model class {} does not support --item_groups'.format(type(model).__module__))
+        sys.exit(1)
+    table = pd.read_csv(fname, sep='\t', header=None, names=['item', 'group'], dtype=str, keep_default_na=False)
+    known = table[table['item'].isin(model.itemidmap.index.astype(str))].drop_duplicates('item', keep='last')
+    ids = dict(zip(model.itemidmap.index.astype(str), model.itemidmap.index))      # (a pickled table may hold ids that are not strings)
+    model.set_item_groups({ids[i]: g for i, g in zip(known['item'], known['group'])})
+    print('Item groups from {}: {} of {} items in {} groups'.format(fname, len(known), len(model.itemidmap), len(model.group_labels)))
+
+
 def train(model_cls, opts):
     params = hyper_parameters(opts)
     print('Creating GRU4Rec model')
@@ -138,6 +156,8 @@ def train(model_cls, opts):
     if world > 1:
         from gru4rec_amd import launch
         launch.cleanup(rank)
+    if opts.item_groups:
+        set_item_groups(model, opts.item_groups)
     if opts.save_model is not None:
         print('Saving trained model to: {}'.format(opts.save_model))
         model.savemodel(opts.save_model)
@@ -196,6 +216,11 @@ def main(argv=None):
     if opts.load_model:
         print('Loading trained model from file: {}'.format(opts.path))
         model = model_cls.loadmodel(opts.path)
+        if opts.item_groups:      # a loaded model gets its groups, and -s writes it back with them
+            set_item_groups(model, opts.item_groups)
+            if opts.save_model is not None:
+                print('Saving the model to: {}'.format(opts.save_model))
+                model.savemodel(opts.save_model)
     else:
         model = train(model_cls, opts)
     if opts.save_neighbors:
