@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Benchmark of the GRU4Rec session-parallel training hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the plan and the model, warms up, times the K steps, writes
+`--dump-outputs` if asked, and prints the result line.  `--full` adds everything else the benchmark measures, each with the switch it always
+had: the 2000-step `long_run` behind a short timed region, the per-kernel passes with their roofline figures (`--profile-steps`), the
+reconciliation measurements and the 8-GPU projection of the one-rank communicator, the row gather / scatter micro-benchmark, the two
+large-catalogue legs and the CPU baseline.  The plan is laid out for all of them either way, so the warm-up and the timed steps see the same
+inputs with and without `--full`.
 
 A "step" is one mini-batch of the reference's `train_function` (gru4rec.py:623) at BASELINE.json config #2:
 RSC15-shaped synthetic sessions (I = 37,483 items), layers=[100], batch=128, n_sample=2048, BPR-max,
@@ -136,7 +143,7 @@ def rocprof_means(config):
     return out
 
 
-def make_plan(cfg, n_steps, rank, nranks, seed=42, session_items=0):
+def make_plan(cfg, n_steps, rank, nranks, seed=42, session_items=0, cache_dir=None):
     """RSC15-shaped sessions -> (plan, number of sessions).  Enough sessions for n_steps full-batch steps.
     session_items: distinct items the SESSIONS are drawn from (0 = the whole catalogue); a smaller set is spread over the catalogue
     by a fixed random injection (round 1-3 used 200,000 for the 3 M / 10 M-item configs: input / target rows were more
@@ -145,14 +152,16 @@ def make_plan(cfg, n_steps, rank, nranks, seed=42, session_items=0):
     B = cfg['batch_size']
     n_sessions = int(n_steps * B / 2.6) + 8 * B           # ~2.9 scoring events per session
     n_items = min(cfg['n_items'], session_items) if session_items > 0 else cfg['n_items']
-    # the generator is deterministic; its output for a 10 M-item catalogue takes ~20 s of host time, so consecutive invocations on
-    # one box (profile passes) share it through a file in the temp directory.  The file name carries a digest of the generator's
+    # the generator is deterministic; its output for a 10 M-item catalogue takes ~20 s of host time.  A run generates its own sessions
+    # and reads nothing an earlier run left behind, unless the caller names a directory (--synth-cache) for the runs of ONE series
+    # (the large-catalogue legs, a profile script's passes) to share them through.  The file name carries a digest of the generator's
     # source: a checkout whose generator differs never reads another checkout's sessions
-    import hashlib
-    import tempfile
-    gen = hashlib.sha1(open(synth.__file__, 'rb').read()).hexdigest()[:12]
-    cache = os.path.join(tempfile.gettempdir(), 'g4r_synth_%d_%d_%d_%s.npz' % (n_sessions * nranks, n_items, seed, gen))
-    if os.path.exists(cache):
+    cache = None
+    if cache_dir:
+        import hashlib
+        gen = hashlib.sha1(open(synth.__file__, 'rb').read()).hexdigest()[:12]
+        cache = os.path.join(cache_dir, 'g4r_synth_%d_%d_%d_%s.npz' % (n_sessions * nranks, n_items, seed, gen))
+    if cache and os.path.exists(cache):
         z = np.load(cache)
         sizes, ids, items_all = z['sizes'], z['ids'], z['items_all']
     else:
@@ -161,9 +170,11 @@ def make_plan(cfg, n_steps, rank, nranks, seed=42, session_items=0):
         ids, inv = np.unique(data.ItemId.values, return_inverse=True)
         items_all = inv.astype(np.int32)
         try:
-            tmp = cache + '.%d.npz' % os.getpid()
-            np.savez(tmp, sizes=sizes, ids=ids, items_all=items_all)
-            os.replace(tmp, cache)
+            if cache:
+                os.makedirs(cache_dir, exist_ok=True)
+                tmp = cache + '.%d.npz' % os.getpid()
+                np.savez(tmp, sizes=sizes, ids=ids, items_all=items_all)
+                os.replace(tmp, cache)
         except OSError:
             pass
     offs = np.zeros(len(sizes) + 1, dtype=np.int64)
@@ -311,11 +322,14 @@ def dump_outputs(m, cfg, plan, t_last, losses, out_dir):
 def large_catalogue_legs(timeout=150):
     """`bench.py --config cfg4m` without / with --defer in child processes -> {'immediate': {...}, 'deferred': {...}} (mini-batches/s, us per
     step, the update launch, and for the deferred run the flush launch priced on the bytes it moves)."""
+    import shutil
     import subprocess
+    import tempfile
     res = {'config': 'cfg4m: B = 512, n_sample = 8192, layers = [256], BPR-max over a 2,000,000-item catalogue (item table 2 GB + 2 GB accumulators)'}
+    shared = tempfile.mkdtemp(prefix='g4r_legs_')      # the two legs train on the same sessions: the second reads what the first generated
     for key, extra in (('immediate', []), ('deferred', ['--defer'])):
-        cmd = [sys.executable, os.path.abspath(__file__), '--config', 'cfg4m', '--steps', '600', '--warmup', '100', '--profile-steps', '128', '--long-steps', '0',
-               '--no-cpu-baseline', '--no-micro', '--no-defer-leg'] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), '--config', 'cfg4m', '--steps', '600', '--warmup', '100', '--full', '--profile-steps', '128',
+               '--long-steps', '0', '--no-cpu-baseline', '--no-micro', '--no-defer-leg', '--synth-cache', shared] + extra
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -333,6 +347,7 @@ def large_catalogue_legs(timeout=150):
                         'deferred_flush': g.get('deferred_flush')}
         except Exception as e:      # noqa: BLE001
             res[key] = {'error': '%s: %s' % (type(e).__name__, e)}
+    shutil.rmtree(shared, ignore_errors=True)
     return res
 
 
@@ -342,6 +357,10 @@ def main():
     ap.add_argument('--steps', type=int, default=6000)
     ap.add_argument('--warmup', type=int, default=600)
     ap.add_argument('--config', default='cfg2', choices=sorted(CONFIGS))
+    ap.add_argument('--full', action='store_true', help='besides the timed steps, run everything else the benchmark measures: the long run behind a '
+                    'short timed region, the per-kernel passes and their roofline figures, the reconciliation measurements of the N > 1 data '
+                    'path, the row gather / scatter micro-benchmark, the large-catalogue legs and the CPU baseline (each with its own switch '
+                    'below).  Without it a run sets up, warms up, times --steps steps and prints the result line')
     ap.add_argument('--profile-steps', type=int, default=300)
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -352,13 +371,15 @@ def main():
                     'item rows + reconciliation: per-occurrence gradient rows all-gathered every step, nothing to reconcile')
     ap.add_argument('--session-items', type=int, default=0, help='distinct items the synthetic sessions are drawn from (0 = the whole catalogue of the '
                     'config; rounds 1-3 used 200000 for cfg3 / cfg4)')
-    ap.add_argument('--no-defer-leg', action='store_true', help='default line only: skip the two short large-catalogue legs (BASELINE configs[3] shape over a '
+    ap.add_argument('--no-defer-leg', action='store_true', help='the default config under --full only: skip the two short large-catalogue legs (BASELINE configs[3] shape over a '
                     '2 M-item catalogue, without / with deferred row updates) that fill roofline_gather_scatter.deferred_flush and large_catalogue')
     ap.add_argument('--long-steps', type=int, default=2000, help='a run of --steps below this also times that many steps behind the timed region and '
                     'reports them as "long_run" (a 20-step window is ~1 ms; 0 = off)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what they computed -- the losses of the '
                     'timed steps, the parameters and hidden state after the last one -- as DIR/<name>.npy (float32; at most 64 MB, a fixed '
                     'sample of item rows beyond that), rank 0 only, so that two builds can be compared output for output')
+    ap.add_argument('--synth-cache', metavar='DIR', default=None, help='keep the generated sessions in DIR and read them from there when they are '
+                    'present: for a series of runs over one large catalogue (default: every run generates its own and reads nothing an earlier run wrote)')
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
@@ -380,7 +401,11 @@ def main():
     n_profile = args.profile_steps
     n_long = args.long_steps if (0 < args.steps < args.long_steps) else 0
     total_steps = args.warmup + args.steps + n_long + n_profile + max(8, n_profile // 4) + 8 + 64 + (min(args.steps, 2000) if (world > 1 or os.environ.get('G4R_FORCE_STAGED')) else 0)
-    plan, support = make_plan(cfg, total_steps, rank, world, session_items=args.session_items)
+    # the generator's output depends on the number of sessions asked for, so the plan is laid out for the passes of --full whether or
+    # not they run: the same arguments give the timed steps the same inputs in a plain run and in a full one
+    run_long = n_long if args.full else 0
+    run_profile = n_profile if args.full else 0
+    plan, support = make_plan(cfg, total_steps, rank, world, session_items=args.session_items, cache_dir=args.synth_cache)
     assert plan['T'] >= total_steps, 'synthetic plan too short: %d < %d' % (plan['T'], total_steps)
     assert (plan['M'][:total_steps] == cfg['batch_size']).all()
     m = create_model(cfg, support, rank, world, local_rank if world > 1 else 0, unique_id, use_graph=not args.no_graph, sparse_exact=args.sparse_exact, defer=args.defer)
@@ -430,7 +455,7 @@ def main():
         # read back before any later step (long run, per-kernel passes) moves the model on
         dumped = dump_outputs(m, cfg, plan, args.warmup + args.steps - 1, losses, args.dump_outputs)
     long_run = None
-    if n_long:
+    if run_long:
         # the same measurement over >= 2000 steps right behind the timed region (the driver's --steps 20 is a ~1 ms window)
         barrier()
         t1 = time.perf_counter()
@@ -463,6 +488,7 @@ def main():
         'loss_finite': bool(np.isfinite(losses).all()),
     }
     out['config']['defer_updates'] = bool(args.defer)
+    out['full'] = bool(args.full)
     if dumped:
         out['dump_outputs'] = dumped
     if long_run:
@@ -471,7 +497,7 @@ def main():
         m.set_sync_every(0)      # the per-kernel passes below time the bare step
     kt = {}
     defer_rows = None
-    if n_profile > 0:
+    if run_profile > 0:
         # per-kernel durations: HIP events on the library's own stream, eager launches over the next plan steps
         d0 = m.get_debug('defer_stats', 4) if args.defer else None
         m.profile(True)
@@ -483,7 +509,7 @@ def main():
             defer_rows = (float(d1[0] - d0[0]), float(d1[1] - d0[1])) if d1[2] else None
     staged = (world > 1 or bool(os.environ.get('G4R_FORCE_STAGED'))) and not args.sparse_exact
     kt_split = {}
-    if n_profile > 0 and world == 1 and not staged:
+    if run_profile > 0 and world == 1 and not staged:
         # the same again with the update launch split into its two roles (g4r_profile(m, 2)): the embedding gather / scatter -- the
         # kernel north_star prices against the HBM roofline -- timed ALONE, next to the merged launch the step actually runs
         n_split = max(8, n_profile // 4)
@@ -492,7 +518,7 @@ def main():
         m.profile(False)
         kt_split = m.kernel_times()
     reconcile = None
-    if staged:
+    if staged and (args.full or (world > 1 and not sync_in_timed)):      # (a plain N > 1 run measures it only where `value` is made of it)
         # The timed region is the training step north_star defines for N > 1 (dense-gradient all-reduce every step, item rows
         # GPU-local).  GRU4Rec.fit also reconciles the item tables every `sync_every` steps (without it the
         # replicas drift apart); that cost is measured here, separately, over the rows the next `sync_every` steps touch, and
@@ -584,10 +610,10 @@ def main():
             'kernel_us_rank0': {k: 1000.0 * v[0] / max(v[1], 1) for k, v in kt.items()}, 'reconciliation': reconcile,
             'note': 'rank_ms_per_step: every rank\'s own wall time of the timed region / steps (value uses the max); all-reduce / dense '
                     'apply: HIP events around the eager launches of %d profile steps on rank 0 (every step synchronises there, so the '
-                    'all-reduce time includes the skew between ranks)' % n_profile}
+                    'all-reduce time includes the skew between ranks; no such steps without --full)' % run_profile}
     if world == 1 and reconcile is not None:
         out['reconciliation_one_rank_communicator'] = reconcile
-    if world == 1 and os.environ.get('G4R_FORCE_STAGED'):
+    if world == 1 and os.environ.get('G4R_FORCE_STAGED') and args.full:
         # What 8 GPUs would do, from the pieces one GPU can measure + the two numbers it cannot (stated, with a range): the latency of
         # the 8-rank collectives over xGMI.  The driver's SCALE run replaces this with a measurement.
         step_us = 1e6 * dt / args.steps
@@ -645,7 +671,7 @@ def main():
         proj['step_us_8_gpus'] = [lo, hi]
         proj['mini_batches_per_s_8_gpus'] = [8e6 / hi, 8e6 / lo]
         out['projection_8_gpus'] = proj
-    if rank == 0 and world == 1 and n_profile > 0:
+    if rank == 0 and world == 1 and run_profile > 0:
         alg = algorithmic_cost(cfg)
         kern = {}
         for name, (ms, n) in kt.items():

@@ -10,12 +10,13 @@ import glob
 import json
 import os
 import sys
+import tempfile
 
 import numpy as np
 import pytest
 
 import bench
-from gru4rec_amd import _native, launch
+from gru4rec_amd import _native, launch, synth
 
 
 class FakeModel:
@@ -80,7 +81,7 @@ def test_bench_main_as_rank_0_of_2(monkeypatch, capsys, extra):
     monkeypatch.setattr(_native, 'Model', FakeModel)
     monkeypatch.setattr(launch, 'unique_id', lambda rank, world, **kw: b'\0' * 128)
     monkeypatch.setattr(launch, 'cleanup', lambda rank: None)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '2', '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-micro',
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '2', '--steps', '20', '--warmup', '5', '--full', '--no-cpu-baseline', '--no-micro',
                                       '--profile-steps', '16'] + extra)
     bench.main()
     lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
@@ -108,7 +109,97 @@ def test_bench_main_as_rank_0_of_2(monkeypatch, capsys, extra):
         assert all(c[2] == 0 for c in m.calls if len(c) == 4 and c[3] != 0), 'the per-kernel passes time the bare step'
 
 
-def _run_one_rank(monkeypatch, capsys, argv):
+def _boom(name):
+    def f(*a, **k):
+        raise AssertionError('a plain run must not reach %s' % name)
+    return f
+
+
+MOVED_KEYS = ('long_run', 'kernels', 'kernel_time_sum_us_per_step', 'dominant_kernel', 'roofline', 'roofline_gather_scatter', 'gather_scatter_micro',
+              'large_catalogue', 'cpu_baseline', 'projection_8_gpus', 'reconciliation_one_rank_communicator', 'value_step_only')
+
+
+def test_plain_run_times_its_steps_and_nothing_else(monkeypatch, capsys, tmp_path):
+    """Without --full: warm-up, the timed steps, the dump, the result line.  No other step, no per-kernel pass, no micro-benchmark, no
+    child run, no CPU baseline -- with none of the --no-... switches given -- and no file of an earlier run read."""
+    monkeypatch.setattr(bench, 'cpu_baseline', _boom('cpu_baseline'))
+    monkeypatch.setattr(bench, 'large_catalogue_legs', _boom('large_catalogue_legs'))
+    monkeypatch.setattr(_native, 'bench_rows', _boom('bench_rows'))
+    d = str(tmp_path / 'plain')
+    with monkeypatch.context() as mp:
+        mp.setattr(np, 'load', _boom('np.load'))
+        mp.setattr(np, 'savez', _boom('np.savez'))
+        out, m = _run_one_rank(mp, capsys, ['--steps', '7', '--warmup', '3', '--long-steps', '50', '--dump-outputs', d], flags=[])
+    assert out['full'] is False and out['steps'] == 7 and out['warmup'] == 3
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'n_gpus', 'config', 'events_per_s', 'loss_first', 'loss_last', 'dump_outputs'):
+        assert k in out
+    assert out['unit'] == 'mini-batches/s' and out['higher_is_better'] is True and out['dtype'] == 'f32'
+    assert out['value'] > 0 and abs(out['value'] * out['ms_per_step'] - 1000.0) < 1e-6 * 1000.0
+    assert not [k for k in MOVED_KEYS if k in out]
+    assert [c for c in m.calls if c[0] != 'get'] == [(0, 3, 0, 0), (3, 7, 0, 0)], 'warm-up, then the timed steps, then nothing'
+    assert m.profile_mode == 0
+    # the same arguments with --full: the same plan, weights and popularity go in, the same arrays come out
+    d2 = str(tmp_path / 'full')
+    out2, m2 = _run_one_rank(monkeypatch, capsys, ['--steps', '7', '--warmup', '3', '--long-steps', '50', '--full', '--dump-outputs', d2])
+    assert out2['full'] is True and 'long_run' in out2 and 'kernels' in out2
+    steps2 = [c for c in m2.calls if len(c) == 4]
+    assert steps2[:2] == [(0, 3, 0, 0), (3, 7, 0, 0)] and len(steps2) > 2
+    assert out2['metric'] == out['metric'] and out2['config'] == out['config']
+    assert sorted(m.inputs, key=str) == sorted(m2.inputs, key=str)
+    for k, v in m.inputs.items():
+        w = m2.inputs[k]
+        for x, y in (zip(v.values(), w.values()) if isinstance(v, dict) else zip(v, w) if isinstance(v, list) else [(v, w)]):
+            assert (x is None and y is None) or np.array_equal(x, y)
+    got, got2 = _dumped(d), _dumped(d2)
+    assert sorted(got) == sorted(got2)
+    for k in got:
+        np.testing.assert_array_equal(got[k], got2[k])
+
+
+@pytest.mark.parametrize('extra', [[], ['--sparse-exact']], ids=['gpu_local_rows', 'exact_replicas'])
+def test_plain_run_as_rank_0_of_2(monkeypatch, capsys, extra):
+    """N > 1 without --full: the timed region as ever (with the on-stream reconciliation for GPU-local rows), no step behind it."""
+    FakeModel.instances.clear()
+    monkeypatch.setenv('RANK', '0')
+    monkeypatch.setenv('LOCAL_RANK', '0')
+    monkeypatch.setenv('WORLD_SIZE', '2')
+    monkeypatch.delenv('G4R_FORCE_STAGED', raising=False)
+    monkeypatch.setattr(_native, 'device_count', lambda: 2)
+    monkeypatch.setattr(_native, 'Model', FakeModel)
+    monkeypatch.setattr(launch, 'unique_id', lambda rank, world, **kw: b'\0' * 128)
+    monkeypatch.setattr(launch, 'cleanup', lambda rank: None)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '2', '--steps', '20', '--warmup', '5', '--long-steps', '50', '--profile-steps', '16'] + extra)
+    bench.main()
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    m = FakeModel.instances[0]
+    k = 0 if extra else 4
+    assert m.calls == [(0, 5, k, 0), (5, 20, k, 0)]
+    assert out['n_gpus'] == 2 and out['full'] is False and out['value'] > 0 and out['multi_gpu']['ncclCommCount'] == 2
+    assert ('value_source' in out) == (not extra) and not [k for k in MOVED_KEYS if k in out]
+    assert out['multi_gpu']['reconciliation'] is None
+
+
+def test_synth_cache_is_opt_in(monkeypatch, tmp_path):
+    """make_plan keeps the generated sessions only in a directory the caller names, and a plan read from there equals a generated one."""
+    cfg = bench.CONFIGS['cfg1']
+    monkeypatch.setattr(tempfile, 'tempdir', str(tmp_path / 'tmp'))
+    os.makedirs(tempfile.gettempdir())
+    fresh, sup = bench.make_plan(cfg, 40, 0, 1)
+    assert os.listdir(tempfile.gettempdir()) == []
+    shared = str(tmp_path / 'shared')
+    first, _ = bench.make_plan(cfg, 40, 0, 1, cache_dir=shared)
+    assert len(os.listdir(shared)) == 1 and os.listdir(tempfile.gettempdir()) == []
+    monkeypatch.setattr(synth, 'make_sessions', _boom('the generator when the sessions are in the directory'))
+    again, sup2 = bench.make_plan(cfg, 40, 0, 1, cache_dir=shared)
+    for k in ('in_idx', 'out_idx', 'reset', 'M'):
+        np.testing.assert_array_equal(fresh[k], first[k])
+        np.testing.assert_array_equal(fresh[k], again[k])
+    np.testing.assert_array_equal(sup, sup2)
+
+
+def _run_one_rank(monkeypatch, capsys, argv, flags=('--no-cpu-baseline', '--no-micro')):
     FakeModel.instances.clear()
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'G4R_FORCE_STAGED'):
         monkeypatch.delenv(k, raising=False)
@@ -116,7 +207,7 @@ def _run_one_rank(monkeypatch, capsys, argv):
     monkeypatch.setattr(_native, 'Model', FakeModel)
     monkeypatch.setattr(launch, 'unique_id', lambda rank, world, **kw: None)
     monkeypatch.setattr(launch, 'cleanup', lambda rank: None)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--no-cpu-baseline', '--no-micro'] + argv)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1'] + list(flags) + argv)
     bench.main()
     lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -131,7 +222,7 @@ def test_bench_dump_outputs_reads_back_the_timed_steps(monkeypatch, capsys, tmp_
     runs = []
     for name in ('a', 'b'):
         d = str(tmp_path / name)
-        out, m = _run_one_rank(monkeypatch, capsys, ['--steps', '7', '--warmup', '3', '--profile-steps', '16', '--long-steps', '50',
+        out, m = _run_one_rank(monkeypatch, capsys, ['--steps', '7', '--warmup', '3', '--full', '--profile-steps', '16', '--long-steps', '50',
                                                      '--dump-outputs', d])
         runs.append((out, m, _dumped(d)))
     (out, m, got), (_, m2, got2) = runs

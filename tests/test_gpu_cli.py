@@ -111,3 +111,27 @@ def test_bench_gpus_flag_on_a_one_gpu_box_fails_fast_and_loud():
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     assert 'rank 1' in r.stderr and '"n_gpus": 2' not in r.stdout
+
+
+def test_plain_bench_run_is_lean():
+    """`python bench.py --gpus 1 --steps N --warmup W` in a fresh process: one result line with the headline figure and none of the
+    measurements that --full adds, and at most 30 s of the whole run -- start of the process to its exit -- outside its N + W steps."""
+    import json
+    import time
+    n, w = 200, 50
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(n), '--warmup', str(w)],
+                       capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out['full'] is False and out['steps'] == n and out['warmup'] == w and out['n_gpus'] == 1
+    assert out['unit'] == 'mini-batches/s' and out['higher_is_better'] is True and out['dtype'] == 'f32' and out['metric'].startswith('mini-batches/sec')
+    assert out['value'] > 0 and out['loss_finite'] and abs(out['value'] * out['ms_per_step'] / 1000.0 - 1.0) < 1e-9
+    for k in ('long_run', 'kernels', 'roofline', 'roofline_gather_scatter', 'gather_scatter_micro', 'large_catalogue', 'cpu_baseline'):
+        assert k not in out
+    outside = wall - (n + w) * out['ms_per_step'] / 1000.0
+    print('plain bench run: %.2f s from start to exit, %.2f s outside its %d steps' % (wall, outside, n + w))
+    assert outside <= 30.0

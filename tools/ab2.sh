@@ -7,7 +7,7 @@ for v in $1; do
   for c in ${2:-cfg2}; do
     steps=3000; [ $c != cfg2 ] && [ $c != cfg1 ] && [ $c != cfg5 ] && steps=1000
     if [ "$lib" = base ]; then unset G4R_LIB; else export G4R_LIB=$ROOT/$lib; fi
-    timeout 300 python bench.py --config $c --steps $steps --warmup 300 --no-cpu-baseline --no-micro $3 > $OUT/ab_${name}_${c}_$rep.json 2> $OUT/ab_${name}_${c}_$rep.err
+    timeout 300 python bench.py --config $c --steps $steps --warmup 300 --full --no-cpu-baseline --no-micro $3 > $OUT/ab_${name}_${c}_$rep.json 2> $OUT/ab_${name}_${c}_$rep.err
     echo "== $name $c rep $rep"; python tools/benchsum.py $OUT/ab_${name}_${c}_$rep.json
   done
 done

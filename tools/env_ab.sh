@@ -5,7 +5,7 @@ if [ -n "$4" ]; then timeout 900 python -m pytest $4 -x -q > $OUT/tests.log 2>&1
 for rep in 1 2; do
 for c in $CFGS; do
 for v in $VALS; do
-  env $VAR=$v timeout 300 python bench.py --config $c --steps 1000 --warmup 300 --no-cpu-baseline --no-micro > $OUT/${c}_${VAR}${v}_$rep.json 2> $OUT/${c}_${VAR}${v}_$rep.err
+  env $VAR=$v timeout 300 python bench.py --config $c --steps 1000 --warmup 300 --full --no-cpu-baseline --no-micro > $OUT/${c}_${VAR}${v}_$rep.json 2> $OUT/${c}_${VAR}${v}_$rep.err
   echo "== $c $VAR=$v rep $rep"; python tools/benchsum.py $OUT/${c}_${VAR}${v}_$rep.json
 done
 done

@@ -3,7 +3,7 @@
 TAG=${1:-r05}; CFGS=${2:-"cfg3 cfg4"}
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=$ROOT/gpurun_out/final; mkdir -p $OUT; B="python $ROOT/bench.py"
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-micro --profile-steps 0 --long-steps 0"
+COMMON="--no-cpu-baseline --no-micro --profile-steps 0 --long-steps 0 --synth-cache $TMPDIR/g4r_synth"      # (the passes of a config share its generated sessions)
 for c in $CFGS; do
   rm -rf /tmp/out_f /tmp/out_w
   timeout 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/out_f -- $B --config $c --steps 256 --warmup 64 --defer --no-graph $COMMON > $OUT/pmc_f_${c}_defer.log 2>&1
