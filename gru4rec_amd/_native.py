@@ -54,7 +54,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_set_item_groups', 'g4r_get_item_groups', 'g4r_recommend_sessions_capped', 'g4r_continue_sessions_capped', 'g4r_cap_lists', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_set_item_groups', 'g4r_get_item_groups', 'g4r_recommend_sessions_capped', 'g4r_continue_sessions_capped', 'g4r_cap_lists', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_loglik_events', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_debug_gumbel', 'g4r_debug_lse_terms', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -159,6 +159,8 @@ def lib():
     L.g4r_evaluate.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32p, i32, i32, f64p, f64p, i64p]
     L.g4r_recommend_events.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i32, i64p, i64, i32,
                                        u32p, i64p, i32p, i32p, i64, i32p, i32p, i32p, f32p, f32p, f32p]
+    L.g4r_loglik_events.argtypes = [vp, i32p, i32p, u8p, i32p, i64, i32, i64p, i32p, i64, i32p, i64, i64p, i64,
+                                    u32p, i64p, i32p, i32p, i64, i32p, i32p, C.c_float, f32p, f32p, u64p, u8p]
     L.g4r_comm_unique_id.argtypes = [C.c_char_p]
     L.g4r_comm_init.argtypes = [vp, C.c_char_p, i32, i32]
     L.g4r_comm_sync_sparse.argtypes = [vp]
@@ -858,14 +860,7 @@ class Model:
         if sl.size != T * batch:
             raise ValueError('slot must hold T * batch = %d entries' % (T * batch))
         mask = _mask(excl_mask, self.cfg.n_items)
-        if seen is None:
-            st = (None, None, None, 0, None, None)
-        else:
-            so, si, sf, ss, sp = (np.ascontiguousarray(seen[key], dtype=t) for key, t in (
-                ('offs', np.int64), ('items', np.int32), ('first', np.int32), ('sess', np.int32), ('pos', np.int32)))
-            if ss.size != T * batch or sp.size != T * batch or len(si) != len(sf) or so[-1] > len(si):
-                raise ValueError('seen tables: sess / pos must hold T * batch entries, items / first one entry per offset')
-            st = (_i64(so), _i32(si), _i32(sf), len(so) - 1, _i32(ss), _i32(sp))
+        st, _keep = self._seen_args(seen, T, batch)
         oi, os_ = _topk_out((n_slots, k)) if want_lists else (None, None)
         rk = np.empty(n_slots, dtype=np.float32)
         ts = np.empty(n_slots, dtype=np.float32)
@@ -874,8 +869,40 @@ class Model:
                                         _i32(oi), _f32(os_), _f32(rk), _f32(ts)))
         return oi, os_, rk, ts
 
+    @staticmethod
+    def _seen_args(seen, T, batch):
+        """The six seen-table arguments of g4r_recommend_events / g4r_loglik_events (and the arrays they point into)."""
+        if seen is None:
+            return (None, None, None, 0, None, None), ()
+        so, si, sf, ss, sp = (np.ascontiguousarray(seen[key], dtype=t) for key, t in (
+            ('offs', np.int64), ('items', np.int32), ('first', np.int32), ('sess', np.int32), ('pos', np.int32)))
+        if ss.size != T * batch or sp.size != T * batch or len(si) != len(sf) or so[-1] > len(si):
+            raise ValueError('seen tables: sess / pos must hold T * batch entries, items / first one entry per offset')
+        return (_i64(so), _i32(si), _i32(sf), len(so) - 1, _i32(ss), _i32(sp)), (so, si, sf, ss, sp)
+
+    def loglik_events(self, plan, batch, items, slot, n_slots, temperature=1.0, excl_mask=None, seen=None):
+        """Target logit, zeta, the integer normaliser Q and the target's eligibility of every event of an evaluation plan in one call
+        (g4r_loglik_events; plan, items, slot, excl_mask and seen as in recommend_events).  Returns (z float32[n_slots], zeta
+        float32[n_slots], Q uint64[n_slots], eligible bool[n_slots])."""
+        T = int(plan['T'])
+        it = _arr(items, np.int32)
+        in_idx, out_idx, reset, M, cs, cm, nc = _plan(plan, batch)
+        sl = np.ascontiguousarray(slot, dtype=np.int64)
+        if sl.size != T * batch:
+            raise ValueError('slot must hold T * batch = %d entries' % (T * batch))
+        mask = _mask(excl_mask, self.cfg.n_items)
+        st, _keep = self._seen_args(seen, T, batch)
+        z = np.zeros(n_slots, dtype=np.float32)
+        zeta = np.zeros(n_slots, dtype=np.float32)
+        Q = np.zeros(n_slots, dtype=np.uint64)
+        el = np.zeros(n_slots, dtype=np.uint8)
+        _chk(lib().g4r_loglik_events(self.h, _i32(in_idx), _i32(out_idx), _u8(reset), _i32(M), T, batch, _i64(cs), _i32(cm), nc,
+                                     _i32(it), 0 if it is None else len(it), _i64(sl), n_slots, _u32(mask), *st,
+                                     float(np.float32(temperature)), _f32(z), _f32(zeta), _u64(Q), _u8(el)))
+        return z, zeta, Q, el.astype(bool)
+
     def events_launches(self):
-        """(steps, launches that scan the candidate columns, all launches, pieces) of the last recommend_events call."""
+        """(steps, launches that scan the candidate columns, all launches, pieces) of the last recommend_events / loglik_events call."""
         return tuple(int(x) for x in self.get_debug('events_launches', 4))
 
     def comm_init(self, unique_id, nranks, rank):

@@ -66,7 +66,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            25: "the per-score eligibility of the row normaliser (g4r_sample_sessions_lp, g4r_session_log_partition) never marks the LAST "
                "item of a row's sorted list, so that item's term is counted in Q",
            26: "k_group_cap (g4r_*_capped, g4r_cap_lists) counts a position's earlier same-group positions from the start of its OWN wave "
-               "only: the positions of earlier waves are forgotten, so pools of more than 64 keep too many"}
+               "only: the positions of earlier waves are forgotten, so pools of more than 64 keep too many",
+           27: "the row normaliser of g4r_loglik_events takes a session item as seen only when its first occurrence is BEFORE the input "
+               "event (s_first < position): the input event's own item, first shown there, stays in Q"}
 
 
 def mutant_path(k):

@@ -42,6 +42,7 @@ extern "C" {
 #include "g4r_host_beam.hpp"
 #include "g4r_host_sample.hpp"
 #include "g4r_host_events.hpp"
+#include "g4r_host_loglik.hpp"
 #include "g4r_host_similar.hpp"
 #include "g4r_host_diversify.hpp"
 #include "g4r_host_groups.hpp"

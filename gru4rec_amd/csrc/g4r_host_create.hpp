@@ -325,7 +325,7 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
         (const void*)k_gru_bwd_a_w4, (const void*)k_gru_bwd_a_w8d, (const void*)k_gru_bwd_b, (const void*)k_dense_grad<32>,
         (const void*)k_score_store, (const void*)k_score_count, (const void*)k_topk_fused, (const void*)k_topk_stored, (const void*)k_topk_fused_x,
         (const void*)k_topk_stored_x, (const void*)k_topk_fused_g, (const void*)k_topk_stored_g, (const void*)k_topk_sample, (const void*)k_topk_rank,
-        (const void*)k_topk_rank_x, (const void*)k_topk_stored_ev, (const void*)k_sim_range<false>, (const void*)k_sim_range<true>,
+        (const void*)k_topk_rank_x, (const void*)k_topk_stored_ev, (const void*)k_topk_events_q, (const void*)k_sim_range<false>, (const void*)k_sim_range<true>,
         (const void*)k_mmr_rerank<false>, (const void*)k_mmr_rerank<true>,
         (const void*)k_scan_bf16<2>, (const void*)k_scan_bf16<4>, (const void*)k_scan_bf16<8>, (const void*)k_scan_bf16<2, TkGrow>,
         (const void*)k_scan_bf16<4, TkGrow>, (const void*)k_scan_bf16<8, TkGrow>};

@@ -45,7 +45,7 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
         host[0] = (float)m->ro_calls; host[1] = (float)m->ro_steps;
         return 0;
     }
-    else if (s == "events_launches") {      // the last g4r_recommend_events call: (steps, launches that scan the candidate columns, all launches, pieces)
+    else if (s == "events_launches") {      // the last g4r_recommend_events / g4r_loglik_events call: (steps, launches that scan the candidate columns, all launches, pieces)
         if (count < 4) return fail("count");
         host[0] = (float)m->ev_steps; host[1] = (float)m->ev_scans; host[2] = (float)m->ev_launches; host[3] = (float)m->ev_pieces;
         return 0;

@@ -8,13 +8,14 @@
 // (k_score_store, k_softmax_rows, k_rank_rows), then selected from memory (k_topk_stored) -- two passes and more (with `items` the
 // row is normalised over [targets | items] for the rank, as g4r_evaluate does, and once more over `items` alone for the list, as
 // g4r_recommend_step does).  Results stay on the device until the end of the call, or of a piece of it.
-int g4r_recommend_events(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, const uint8_t* reset, const int32_t* M, int64_t T,
-                         int32_t batch, const int64_t* compact_steps, const int32_t* compact_maps, int64_t n_compact,
-                         const int32_t* items, int64_t n_items_sel, int32_t mode, const int64_t* slot, int64_t n_slots, int32_t k,
-                         const uint32_t* excl_mask, const int64_t* seen_offs, const int32_t* seen_items, const int32_t* seen_first,
-                         int64_t n_seen, const int32_t* seen_sess, const int32_t* seen_pos, int32_t* out_items, float* out_scores,
-                         float* out_rank, float* out_target_score) {
-    // ---- every check before any device work
+//
+// events_check: every check of the call's plan, slots, seen tables and exclusions (each session keeps at least k eligible candidate
+// positions at its last event), before any device work.  g4r_loglik_events (g4r_host_loglik.hpp) shares them, with k = 1.
+static int events_check(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, const uint8_t* reset, const int32_t* M, int64_t T,
+                        int32_t batch, const int64_t* compact_steps, const int32_t* compact_maps, int64_t n_compact, const int32_t* items,
+                        int64_t n_items_sel, int32_t mode, const int64_t* slot, int64_t n_slots, int32_t k, const uint32_t* excl_mask,
+                        const int64_t* seen_offs, const int32_t* seen_items, const int32_t* seen_first, int64_t n_seen,
+                        const int32_t* seen_sess, const int32_t* seen_pos) {
     if (!m || !in_idx || !out_idx || !reset || !M || !slot) return fail("null argument");
     if (T < 0 || batch < 1 || n_slots < 0) return fail("bad evaluation sizes");
     if (plan_mode_check(mode, compact_steps, compact_maps, n_compact)) return -1;
@@ -87,6 +88,23 @@ int g4r_recommend_events(g4r_model* m, const int32_t* in_idx, const int32_t* out
             }
         }
     }
+    return 0;
+}
+
+int g4r_recommend_events(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, const uint8_t* reset, const int32_t* M, int64_t T,
+                         int32_t batch, const int64_t* compact_steps, const int32_t* compact_maps, int64_t n_compact,
+                         const int32_t* items, int64_t n_items_sel, int32_t mode, const int64_t* slot, int64_t n_slots, int32_t k,
+                         const uint32_t* excl_mask, const int64_t* seen_offs, const int32_t* seen_items, const int32_t* seen_first,
+                         int64_t n_seen, const int32_t* seen_sess, const int32_t* seen_pos, int32_t* out_items, float* out_scores,
+                         float* out_rank, float* out_target_score) {
+    // ---- every check before any device work
+    if (events_check(m, in_idx, out_idx, reset, M, T, batch, compact_steps, compact_maps, n_compact, items, n_items_sel, mode, slot, n_slots, k,
+                     excl_mask, seen_offs, seen_items, seen_first, n_seen, seen_sess, seen_pos))
+        return -1;
+    DevModel& d = m->dm;
+    const int B = batch;
+    const int64_t I = d.n_items, n_cand = items ? n_items_sel : I;
+    const bool seen = seen_offs != nullptr;
     const bool excl = seen || excl_mask;
     const bool sm = is_softmax(d);
     // ---- pieces: the lists of at most `cap` events are held on the device at a time.  One piece: an event's place is its slot and

@@ -231,7 +231,7 @@ struct g4r_model {
     DevBuf<float> gc_scores;
     DevBuf<long long> gc_pbeg;
     unsigned tie_ctr = 0;                      // evaluation step counter of the 'tiebreaking' noise stream
-    // the last g4r_recommend_events call (g4r_get_debug "events_launches"): its steps, the launches whose grid spans the candidate
+    // the last g4r_recommend_events / g4r_loglik_events call (g4r_get_debug "events_launches"): its steps, the launches whose grid spans the candidate
     // columns, all its launches, the pieces its lists came back in
     int64_t ev_steps = 0, ev_scans = 0, ev_launches = 0, ev_pieces = 0;
     // rccl
@@ -384,6 +384,7 @@ static constexpr auto k_topk_fused_q = k_topk_range<false, true, TkGrowLse>;    
 static constexpr auto k_topk_rank = k_topk_range<false, false, TkEvents>;        // g4r_recommend_events: k_topk_fused + the rank counters of k_score_count
 static constexpr auto k_topk_rank_x = k_topk_range<false, true, TkEvents>;       // + the session-list / mask exclusions
 static constexpr auto k_topk_stored_ev = k_topk_range<true, true, TkEvents>;     // softmax / softmax_logit with those exclusions (no counters)
+static constexpr auto k_topk_events_q = k_topk_range<false, true, TkEventsLse>;  // g4r_loglik_events: the row normaliser Q under those exclusions (k = 1)
 
 static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 // dynamic LDS of the tile-GEMM kernels (g4r_gemm.cuh)

@@ -155,6 +155,20 @@ __device__ __forceinline__ TkLse tk_lse(TkGrowLse x) { return x.l; }
 // word of the columns the global mask takes
 #define TK_SMEM_LSE (TK_SMEM_FUSED_X + (SC_BM + 4) * 4)
 static_assert(TK_SMEM_LSE <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
+// The trailing argument of the g4r_loglik_events instantiation (k_topk_range<false, true, TkEventsLse>): the row normaliser under
+// TkEvents' eligibility.  The rows' lists are the SESSION-level ones (e.seen / e.s_items / e.s_first), so the per-tile word of a row
+// marks a column only when its item is found in the session list with s_first <= the row's position; the mask as before.  No rank
+// counters (e.tscore / e.cnt / e.tie_col are not read); launched with k = 1, its lists unused.  A type of its own once more.
+struct TkEventsLse { TkEvents e; TkLse l; };
+__device__ __forceinline__ TkExcl tk_excl(TkEventsLse x) { return tk_excl(x.e); }
+__device__ __forceinline__ TkEvents tk_events(TkEventsLse x) { return x.e; }
+__device__ __forceinline__ TkSample tk_sample(TkEventsLse) { return TkSample{}; }
+__device__ __forceinline__ TkLse tk_lse(TkEventsLse x) { return x.l; }
+template <> struct tk_is_events<TkEventsLse> { static constexpr bool value = true; };
+template <> struct tk_is_lse<TkEventsLse> { static constexpr bool value = true; };
+// LDS: the forms' with the row normaliser + every row's position in its session (TK_SEL_EV): 153,488 B
+#define TK_SMEM_LSE_EV (TK_SMEM_LSE + TK_SEL_EV)
+static_assert(TK_SMEM_LSE_EV <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
 // (Every score gets its noise.  Skipping the Philox call and the logarithms of a score whose key cannot beat its row's threshold
 // whatever the noise -- g < 17 -- gives the same results and was measured: it does not pay, profiles/sample_sessions.md.)
 
@@ -249,6 +263,7 @@ __device__ __forceinline__ void topk_merge_row(int r, uint2* L, int k, uint2* sq
 // row's list (TK_SCRATCH_WAVE_X).  EXCL = false takes no trailing argument, so its kernel arguments -- and with them its code --
 // are those of the unfiltered kernel.  TkSample (fused, EXCL): the value selected on is the draw's key, see the struct.
 // TkSampleLse / TkGrowLse (fused, EXCL): the scan also adds every ELIGIBLE score's lse_term to the row's Q, see TkLse.
+// TkEventsLse (fused, EXCL): that sum under TkEvents' session-list eligibility (g4r_loglik_events).
 template <bool STORED, bool EXCL, typename... X>
 __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__ mp, const float* h, int mrows, const int* item_idx,
                                                     long long n_sel, const float* sc, long long ldo, int k, int tpr, uint2* ws,
@@ -320,7 +335,7 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
         __syncthreads();
     };
     // rank counters (events form, fused): every lane's own share of its 8 rows' (greater, equal) counts over the whole range
-    constexpr bool RANK = EV && !STORED;
+    constexpr bool RANK = EV && !STORED && !LSE;      // (TkEventsLse: the normaliser, no counters)
     float tt[2][4];
     int cg[2][4], ce[2][4];
     if constexpr (RANK) {
@@ -346,10 +361,26 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
     // all-items calls, whose columns are item indices: one lower_bound at c0, then per tile a compare with the next list item held in
     // a register and a load only on a hit -- or, with a candidate list, searches the row's list for each of the tile's 32 items.
     // Rows with an empty list do neither.  The lists grow between launches, so nothing is kept across them.
+    // TkEventsLse: row r's list is its SESSION's, and an item found there takes its column only when its first occurrence is at or
+    // before the row's position (lx_seen: one more load, on a hit only) -- merge-time TkEvents eligibility, decided per score.
     float zt[2][4];
     unsigned long long qa[2][4];
     long long lx_b = 0;
-    int lx_n = 0, lx_cur = 0, lx_next = 0;
+    int lx_n = 0, lx_cur = 0, lx_next = 0, lx_pos = 0;
+    auto lx_seen = [&](int j) -> bool {
+        if constexpr (EV) {
+#if defined(G4R_MUTATE) && G4R_MUTATE == 27      // test build: the input event's own item (first occurrence AT the position) stays in Q
+            return ev.s_first[lx_b + j] < lx_pos;
+#else
+            return ev.s_first[lx_b + j] <= lx_pos;
+#endif
+        } else {
+            (void)j;
+            return true;
+        }
+    };
+    if constexpr (LSE && EV)
+        if (tid < SC_BM) lx_pos = s_xp[tid];
     if constexpr (LSE) {
 #pragma unroll
         for (int ri = 0; ri < 2; ++ri)
@@ -393,7 +424,7 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
                     if (lx_n > 0 && !item_idx) {
                         const long long n1 = n0 + TK_TN;
                         while (lx_cur < lx_n && lx_next < n1) {
-                            w |= 1u << (int)(lx_next - n0);
+                            if (lx_seen(lx_cur)) w |= 1u << (int)(lx_next - n0);
                             if (++lx_cur < lx_n) lx_next = ex.items[lx_b + lx_cur];
                         }
                     } else if (lx_n > 0) {
@@ -402,7 +433,7 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
                             if (item < 0) break;      // (the columns past c1 close the last tile)
                             int a = 0, b = lx_n;
                             while (a < b) { const int mid = (a + b) >> 1; if (ex.items[lx_b + mid] < item) a = mid + 1; else b = mid; }
-                            if (a < lx_n && ex.items[lx_b + a] == item) w |= 1u << j;
+                            if (a < lx_n && ex.items[lx_b + a] == item && lx_seen(a)) w |= 1u << j;
                         }
                     }
                     s_rowx[tid] = w;      // (read after the chain's barriers below, written again after the next tile's first one)
@@ -630,6 +661,17 @@ template __global__ void k_topk_range<true, true, TkGrow>(const DevModel*, const
 template __global__ void k_topk_range<false, false, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
 template __global__ void k_topk_range<false, true, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
 template __global__ void k_topk_range<true, true, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
+template __global__ void k_topk_range<false, true, TkEventsLse>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEventsLse);
+// g4r_loglik_events: row r of one step is the event at place[r] (as k_events_merge places it): its target's z, the row's zeta and Q
+// go there.  Clears the rank counters the k = 1 selection (k_topk_range<false, true, TkEvents>) left behind, as k_rank_counts does.
+__global__ __launch_bounds__(256) void k_loglik_finish(const long long* place, const float* tz, const float* zeta, const unsigned long long* Q,
+                                                       int* cnt, int mrows, float* out_z, float* out_zeta, unsigned long long* out_Q) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= mrows) return;
+    const size_t s = (size_t)place[r];
+    out_z[s] = tz[r]; out_zeta[s] = zeta[r]; out_Q[s] = Q[r];
+    cnt[2 * r] = 0; cnt[2 * r + 1] = 0;
+}
 
 // ---- stateless replay of session histories (g4r_recommend_sessions) ---------------------------------------------------------
 // A chunk's rows are sorted by history length, descending; perm[r] is the chunk row (caller's order) of sorted row r, len[r] its

@@ -11,6 +11,9 @@ host-driven variant (one `g4r_predict_step` + `g4r_rank_targets` per step), kept
 
 Not in the reference: `recommend_gpu` runs the same loop (`g4r_recommend_events`) and returns, for every scored event, its top-k
 list, the rank of its target and the target's score; `list_metrics` turns that into recall, MRR, NDCG and item coverage.
+`loglik_gpu` runs it once more (`g4r_loglik_events`) for the log-probability the model gives to the item that actually came next at
+every event -- sample_sessions' distribution, its exact integer normaliser formed on the device -- and `loglik_metrics` turns that
+into the held-out negative log-likelihood, the perplexity and per-session sequence likelihoods.
 """
 import numpy as np
 import pandas as pd
@@ -187,37 +190,10 @@ def seen_tables(titems, offs):
                 first=p[head].astype(np.int32))
 
 
-def recommend_gpu(gru, test_data, k=20, items=None, session_key='SessionId', item_key='ItemId', time_key='Time', batch_size=100,
-                  mode='standard', exclude_seen=False, exclude=None):
-    """The top-k list and the target's rank at EVERY event of a test set, in one device call (g4r_recommend_events): the loop of
-    evaluate_gpu -- same preparation, same plan, same ranks -- that keeps what evaluate_gpu folds into two sums.
-
-    Returns a dict of NumPy arrays with one entry per scored event (every event of the sorted test table that has a successor in
-    its session), in the order of that table:
-      row           index of the input event in the sorted test table (events of unknown items dropped, sorted by session, time, item)
-      session       its session id
-      target        item id of the next event of the session
-      rank          the target's rank among the candidates (`mode` as in evaluate_gpu): sum(rank <= c) / n is evaluate_gpu's recall@c
-      target_score  the target's score
-      items         [n, k] item ids, best first: what recommend_sessions returns for the session's prefix up to the input event
-      scores        [n, k] float32, predict_next_batch's bit patterns
-    items: candidate item ids (default: all); the list is chosen among them, the rank counts them (the target itself is ranked
-    whether listed or not, as in evaluate_gpu).  exclude_seen: an event's list leaves out the items its session has shown up to and
-    including the input event (recommend_sessions' exclude_history); exclude: item ids left out of every list.  Exclusions never
-    change `rank`.  A session with more than G4R_EXCLUDE_MAX distinct items, or exclusions that leave fewer than k candidates at
-    some event, raise ValueError naming the session before anything runs."""
+def _events_inputs(gru, titems, offs, sess_ids, batch_size, exclude_seen, exclude):
+    """What recommend_gpu and loglik_gpu hand to the device besides the candidates: (device model, plan, slot int64[T, batch], rows =
+    the scored events' rows of the sorted table, exclusion mask or None, seen tables or None, the session id of every session)."""
     from . import _native
-    if gru.error_during_train:
-        raise Exception
-    if mode not in ('standard', 'conservative', 'median', 'tiebreaking'):
-        raise NotImplementedError
-    n_sel = len(gru.itemidmap) if items is None else len(items)
-    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
-        raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
-    k = int(k)
-    if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
-        raise ValueError('batch_size = %r: it must be a positive integer' % (batch_size,))
-    titems, item_idxs, offs, sess_ids = _prepare(gru, test_data, items, session_key, item_key, time_key, want_sessions=True)
     n_sessions = len(offs) - 1
     if n_sessions < batch_size:
         raise IndexError('fewer test sessions ({}) than batch_size ({})'.format(n_sessions, batch_size))
@@ -251,15 +227,55 @@ def recommend_gpu(gru, test_data, k=20, items=None, session_key='SessionId', ite
         safe = np.maximum(table, 0)
         seen['sess'] = row_sess[safe].astype(np.int32)
         seen['pos'] = (safe - offs[row_sess[safe]]).astype(np.int32)
+    return model, plan, slot, rows, mask, seen, first_sess
+
+
+def _events_refusal(e, first_sess):
+    """The device call's refusals that are the caller's doing, as ValueError (the session by its id); anything else returns."""
+    import re
+    hit = re.search(r'session (\d+) has', str(e))
+    if hit:
+        raise ValueError('session %s: %s' % (first_sess[int(hit.group(1))], e)) from None
+    if 'eligible candidate positions' in str(e):
+        raise ValueError(str(e)) from None
+
+
+def recommend_gpu(gru, test_data, k=20, items=None, session_key='SessionId', item_key='ItemId', time_key='Time', batch_size=100,
+                  mode='standard', exclude_seen=False, exclude=None):
+    """The top-k list and the target's rank at EVERY event of a test set, in one device call (g4r_recommend_events): the loop of
+    evaluate_gpu -- same preparation, same plan, same ranks -- that keeps what evaluate_gpu folds into two sums.
+
+    Returns a dict of NumPy arrays with one entry per scored event (every event of the sorted test table that has a successor in
+    its session), in the order of that table:
+      row           index of the input event in the sorted test table (events of unknown items dropped, sorted by session, time, item)
+      session       its session id
+      target        item id of the next event of the session
+      rank          the target's rank among the candidates (`mode` as in evaluate_gpu): sum(rank <= c) / n is evaluate_gpu's recall@c
+      target_score  the target's score
+      items         [n, k] item ids, best first: what recommend_sessions returns for the session's prefix up to the input event
+      scores        [n, k] float32, predict_next_batch's bit patterns
+    items: candidate item ids (default: all); the list is chosen among them, the rank counts them (the target itself is ranked
+    whether listed or not, as in evaluate_gpu).  exclude_seen: an event's list leaves out the items its session has shown up to and
+    including the input event (recommend_sessions' exclude_history); exclude: item ids left out of every list.  Exclusions never
+    change `rank`.  A session with more than G4R_EXCLUDE_MAX distinct items, or exclusions that leave fewer than k candidates at
+    some event, raise ValueError naming the session before anything runs."""
+    from . import _native
+    if gru.error_during_train:
+        raise Exception
+    if mode not in ('standard', 'conservative', 'median', 'tiebreaking'):
+        raise NotImplementedError
+    n_sel = len(gru.itemidmap) if items is None else len(items)
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(n_sel, _native.G4R_TOPK_MAX):
+        raise ValueError('k = %r: it must be an integer in [1, min(number of candidates = %d, %d)]' % (k, n_sel, _native.G4R_TOPK_MAX))
+    k = int(k)
+    if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError('batch_size = %r: it must be a positive integer' % (batch_size,))
+    titems, item_idxs, offs, sess_ids = _prepare(gru, test_data, items, session_key, item_key, time_key, want_sessions=True)
+    model, plan, slot, rows, mask, seen, first_sess = _events_inputs(gru, titems, offs, sess_ids, batch_size, exclude_seen, exclude)
     try:
         li, ls, rank, ts = model.recommend_events(plan, batch_size, item_idxs, mode, slot, len(rows), k, mask, seen)
     except _native.NativeError as e:
-        import re
-        hit = re.search(r'session (\d+) has', str(e))
-        if hit:
-            raise ValueError('session %s: %s' % (first_sess[int(hit.group(1))], e)) from None
-        if 'eligible candidate positions' in str(e):
-            raise ValueError(str(e)) from None
+        _events_refusal(e, first_sess)
         raise
     finally:
         gru.predict = None      # the call used the model's prediction state (see evaluate_gpu)
@@ -290,3 +306,81 @@ def list_metrics(result, cut_off=[5, 10, 20], n_items=None):
                 raise ValueError('coverage at cut-off %d needs lists of at least that length (k = %d)' % (c, lists.shape[1]))
             out['coverage'].append(len(np.unique(lists[:, :c])) / float(n_items))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- per-event log-likelihood (not in the reference)
+def _loglik_events(gru, titems, item_idxs, offs, sess_ids, batch_size, t32, exclude_seen, exclude):
+    """loglik_gpu behind its preparation (GRU4Rec.session_log_likelihood enters here): one g4r_loglik_events call, then the two
+    float64 formulas of the contract in NumPy."""
+    from . import _native
+    model, plan, slot, rows, mask, seen, first_sess = _events_inputs(gru, titems, offs, sess_ids, batch_size, exclude_seen, exclude)
+    try:
+        z, zeta, Q, eligible = model.loglik_events(plan, batch_size, item_idxs, slot, len(rows), float(t32), mask, seen)
+    except _native.NativeError as e:
+        _events_refusal(e, first_sess)
+        raise
+    finally:
+        gru.predict = None      # the call used the model's prediction state (see evaluate_gpu)
+    inv_t = np.float32(1) / t32
+    with np.errstate(all='ignore'):
+        logq = np.log(Q.astype(np.float64) * 2.0 ** -39)
+        lse = (zeta.astype(np.float64) * np.float64(inv_t) + logq).astype(np.float32)
+        d = ((z - zeta).astype(np.float32) * inv_t).astype(np.float32)
+        logprob = np.where(eligible, (d.astype(np.float64) - logq).astype(np.float32), np.float32(-np.inf)).astype(np.float32)
+    ids = gru.itemidmap.index.values
+    return dict(row=rows, session=np.asarray(sess_ids)[rows], target=ids[titems[rows + 1]], logprob=logprob, lse=lse, target_logit=z,
+                zeta=zeta, Q=Q, eligible=eligible)
+
+
+def loglik_gpu(gru, test_data, items=None, temperature=1.0, exclude_seen=False, exclude=None, session_key='SessionId', item_key='ItemId',
+               time_key='Time', batch_size=None):
+    """The log-probability the model gives to the item that actually came next, at EVERY event of a test set, in one device call
+    (g4r_loglik_events): held-out negative log-likelihood / perplexity (loglik_metrics), the target-policy propensity
+    pi(logged item | prefix) of off-policy evaluation, per-session sequence likelihoods.  Same preparation, plan and seen tables as
+    recommend_gpu, and the distribution is sample_sessions': softmax(z / temperature) over the event's eligible candidate positions.
+
+    Returns a dict of NumPy arrays with one entry per scored event, in the order of the sorted test table; row / session / target
+    are recommend_gpu's, so the two results join on `row`:
+      logprob       float32: fl32(d_t - log(Q * 2^-39)) in float64, d_t = fl32(fl32(z_t - zeta) / temperature); -inf when the target
+                    holds no eligible position
+      lse           float32: fl32(zeta / temperature + log(Q * 2^-39)), session_log_partition's bits for the session's prefix
+      target_logit  float32 z_t: the target's predict_next_batch score, the pre-activation value for final_act softmax / softmax_logit
+                    (reported for ineligible targets too)
+      zeta, Q       the largest eligible z of the event and the exact integer normaliser (uint64), as sample_sessions defines them
+      eligible      bool: the target holds an eligible position
+    Eligible positions of an event: all items, or the positions of `items` (a duplicate id counts once per position), minus
+    `exclude`, minus -- exclude_seen -- the items its session has shown up to and including the input event: the positions
+    recommend_gpu's list may hold under the same arguments.  Every value is a function of exact device outputs, so it does not depend
+    on batch_size (None: min(512, number of sessions)).  An unknown id raises KeyError; a session with more than G4R_EXCLUDE_MAX
+    distinct items, or an event left without an eligible position, ValueError naming the session; more than 2^24 candidate positions
+    or a bad temperature ValueError; fewer sessions than an explicit batch_size IndexError -- all before anything runs."""
+    from .gru4rec import _check_lse_candidates, _check_temperature
+    if gru.error_during_train:
+        raise Exception
+    t32 = _check_temperature(temperature)
+    if batch_size is not None and (isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1):
+        raise ValueError('batch_size = %r: it must be a positive integer or None' % (batch_size,))
+    n_sel = len(gru.itemidmap) if items is None else len(items)
+    if n_sel < 1:
+        raise ValueError('items is empty: at least one candidate is needed')
+    _check_lse_candidates(n_sel)
+    titems, item_idxs, offs, sess_ids = _prepare(gru, test_data, items, session_key, item_key, time_key, want_sessions=True)
+    if batch_size is None:
+        batch_size = max(1, min(512, len(offs) - 1))
+    return _loglik_events(gru, titems, item_idxs, offs, sess_ids, int(batch_size), t32, exclude_seen, exclude)
+
+
+def loglik_metrics(result):
+    """Metrics of a loglik_gpu result: dict(n = scored events, n_ineligible = those whose target held no eligible position, nll = the
+    float64 mean of -logprob over the eligible events, perplexity = exp(nll), sessions = the distinct session ids, session_logprob =
+    the float64 sum of logprob over every session's eligible events, session_events = their number).  nll and perplexity are nan
+    when no event is eligible."""
+    lp = np.asarray(result['logprob'], dtype=np.float64)
+    ok = np.asarray(result['eligible'], dtype=bool)
+    n_ok = int(ok.sum())
+    nll = float(-lp[ok].sum() / n_ok) if n_ok else float('nan')
+    sessions, inv = np.unique(np.asarray(result['session']), return_inverse=True)
+    inv = np.ravel(inv)
+    return dict(n=len(lp), n_ineligible=len(lp) - n_ok, nll=nll, perplexity=float(np.exp(nll)), sessions=sessions,
+                session_logprob=np.bincount(inv[ok], weights=lp[ok], minlength=len(sessions)).astype(np.float64),
+                session_events=np.bincount(inv[ok], minlength=len(sessions)).astype(np.int64))

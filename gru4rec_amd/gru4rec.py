@@ -1265,6 +1265,37 @@ class GRU4Rec:
         with np.errstate(all='ignore'):
             return (zeta.astype(np.float64) * inv_t + np.log(Q.astype(np.float64) * 2.0 ** -39)).astype(np.float32)
 
+    def session_log_likelihood(self, histories, temperature=1.0, predict_for_item_ids=None, exclude_seen=False, exclude=None,
+                               return_details=False):
+        """Teacher forcing over N sessions given as lists of item ids, in one device call: (logprobs float32[sum(len_i - 1)], offsets
+        int64[N + 1]).  Not in the reference.  Event t of row i has input histories[i][t] and target histories[i][t + 1];
+        logprobs[offsets[i] + t] is the log-probability sample_sessions' distribution -- softmax(z / temperature) over the eligible
+        candidate positions after the prefix histories[i][:t + 1] -- gives that target, -inf when the target holds no eligible
+        position (excluded, already shown with exclude_seen, or not among predict_for_item_ids).  The contract, the arguments'
+        meaning and the refusals are evaluation.loglik_gpu's (exclude_seen: its exclude_seen, which is sample_sessions' no_repeat);
+        the histories are checked as recommend_sessions checks them.  A one-item history contributes no event; no scored event at all
+        is a ValueError.  return_details: a third value, loglik_gpu's dict for the same events (session = the row i)."""
+        from . import evaluation
+        if self.error_during_train:
+            raise Exception
+        t32 = _check_temperature(temperature)
+        n_cand = self._n_candidates(predict_for_item_ids)
+        _check_k(1, n_cand, bools=True)
+        _check_lse_candidates(n_cand)
+        N, lens, offs, hidx, _ = self._session_inputs(histories, None)
+        iidx, _ = self._candidates(predict_for_item_ids)
+        out_offs = np.concatenate([[0], np.cumsum(lens - 1)]).astype(np.int64)
+        if out_offs[-1] == 0:
+            raise ValueError('no scored event: every history holds a single item')
+        keep = np.flatnonzero(lens > 1)                       # (a one-item session has no event to score and takes no row of the plan)
+        on = np.repeat(lens > 1, lens)
+        koffs = np.concatenate([[0], np.cumsum(lens[keep])]).astype(np.int64)
+        res = evaluation._loglik_events(self, hidx[on], None if iidx is None else iidx.astype(np.int32), koffs, np.repeat(keep, lens[keep]),
+                                        int(min(512, len(keep))), t32, exclude_seen, exclude)
+        if return_details:
+            return res['logprob'], out_offs, res
+        return res['logprob'], out_offs
+
     def sample_sessions(self, histories, steps, samples=1, temperature=1.0, top_k=None, seed=0, first_step=0, no_repeat=True,
                         predict_for_item_ids=None, exclude=None, exclude_per_row=None, hidden=None, return_hidden=False, top_p=None,
                         return_logprobs=False):

@@ -517,6 +517,32 @@ int g4r_recommend_events(g4r_model* m, const int32_t* in_idx, const int32_t* out
                          int64_t n_seen, const int32_t* seen_sess, const int32_t* seen_pos, int32_t* out_items, float* out_scores,
                          float* out_rank, float* out_target_score);
 
+/* not in the reference: the log-likelihood of the logged next item at EVERY event of a test set -- g4r_recommend_events' plan loop
+ * giving every event what g4r_session_log_partition gives its replayed prefix, plus the z of its target.  Plan arguments, slot,
+ * excl_mask and the seen_* tables as in g4r_recommend_events; temperature as in g4r_session_log_partition.
+ * Contract (g4r_sample_sessions_lp's, so that the two agree).  For the event whose input is position p of its session and whose
+ * target t is the session's next item, E = the eligible candidate positions: all items, or the positions of `items` (a duplicate
+ * counts once per position), minus excl_mask, minus -- with the seen tables -- the items the session has shown up to and including
+ * position p.  E is the set of positions g4r_recommend_events' list may hold for the event.
+ *   z_n      g4r_predict_step's score of candidate n, bit for bit; the pre-activation value for softmax / softmax_logit
+ *   zeta     the largest z over E in the selection's order (NaN below every number, -0.0 == +0.0)
+ *   d_n      fl32(fl32(z_n - zeta) * fl32(1 / temperature)),  q_n = rn(2^39 * expf(d_n)) (0 for NaN),  Q = the exact sum of q_n over E
+ * Outputs by slot: out_z[n_slots] = z_t (also for an ineligible target), out_zeta[n_slots], out_Q[n_slots], out_eligible[n_slots]
+ * = 1 iff t holds a position in E.  From them, in float64 on the host:
+ *   lse      fl32(zeta * invT + log(Q * 2^-39)): g4r_session_log_partition's bits for the prefix
+ *   logprob  fl32(d_t - log(Q * 2^-39)) for an eligible target, -inf otherwise
+ * Q is an integer sum, so every output is independent of batch, of how the columns are cut into ranges and of the pieces.
+ * Everything is checked before the first launch: g4r_recommend_events' checks with k = 1 (every session keeps at least one eligible
+ * position at its last event; the refusal names the session), the temperature, at most 2^24 candidate positions.  Per step and
+ * whatever the final activation: two scans of the candidates' Wy rows (zeta, then Q relative to it), no score matrix.  Pieces of
+ * G4R_EVENTS_PIECE_BYTES (16 bytes an event), one synchronisation and one download each.  Uses the prediction state like
+ * g4r_evaluate. */
+int g4r_loglik_events(g4r_model* m, const int32_t* in_idx, const int32_t* out_idx, const uint8_t* reset, const int32_t* M, int64_t T,
+                      int32_t batch, const int64_t* compact_steps, const int32_t* compact_maps, int64_t n_compact, const int32_t* items,
+                      int64_t n_items_sel, const int64_t* slot, int64_t n_slots, const uint32_t* excl_mask, const int64_t* seen_offs,
+                      const int32_t* seen_items, const int32_t* seen_first, int64_t n_seen, const int32_t* seen_sess,
+                      const int32_t* seen_pos, float temperature, float* out_z, float* out_zeta, uint64_t* out_Q, uint8_t* out_eligible);
+
 /* ---- input pipeline: the pandas work in front of fit() for TAB separated files -------------
  * run.py:45-78 `pd.read_csv(sep='\t', usecols, dtype={session: int32, item: str})` + gru4rec.py:534-538
  * `itemids = data[item_key].unique(); itemidmap = Series(arange, index=itemids); data['ItemIdx'] = itemidmap[...]`.

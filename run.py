@@ -54,11 +54,17 @@ GROUP_OPTIONS = [
     (None, '--item_groups', dict(metavar='FILE', help='after training or loading (not in the reference): a TAB separated file of two columns, item id and group label, without a header; the groups are set on the model (GRU4Rec.set_item_groups: max_per_group / exclude_groups of the recommendation calls), so a model saved with -s carries them.  --save_recs is unaffected')),
 ]
 
+# held-out log-likelihood (not in the reference): one more table
+LOGLIK_OPTIONS = [
+    (None, '--loglik', dict(action='store_true', help='with -t (not in the reference): also print the held-out negative log-likelihood and perplexity of the test set -- the mean of -log softmax(z / T)[next item] over its events (evaluation.loglik_gpu)')),
+    (None, '--loglik_temperature', dict(metavar='T', type=float, default=1.0, help='temperature T of --loglik (default 1.0)')),
+]
+
 
 def build_parser():
     ap = argparse.ArgumentParser(description='Train a GRU4Rec model on an MI355X (or load one) and report Recall@N / MRR@N.')
     ap.add_argument('path', metavar='PATH', help='training data (.tsv / .txt with TAB separators, or a pickled DataFrame) -- or the model file when -l is given')
-    for short, long_, kw in OPTIONS + NEIGHBOR_OPTIONS + GROUP_OPTIONS:
+    for short, long_, kw in OPTIONS + NEIGHBOR_OPTIONS + GROUP_OPTIONS + LOGLIK_OPTIONS:
         ap.add_argument(*([short, long_] if short else [long_]), **kw)
     return ap
 
@@ -177,6 +183,10 @@ def evaluate(model, opts):
         print('Evaluation took {:.2f}s'.format(time.time() - started))
         for pos, cut in enumerate(opts.measure):
             print('Recall@{}: {:.6f} MRR@{}: {:.6f}'.format(cut, scores[0][pos], cut, scores[1][pos]))
+        if opts.loglik:
+            lm = evaluation.loglik_metrics(evaluation.loglik_gpu(model, events, temperature=opts.loglik_temperature, item_key=opts.item_key,
+                                                                 session_key=opts.session_key, time_key=opts.time_key))
+            print('NLL: {:.6f} Perplexity: {:.6f} Events: {} Ineligible: {}'.format(lm['nll'], lm['perplexity'], lm['n'], lm['n_ineligible']))
         if opts.log_primary_metric:
             print('PRIMARY METRIC: {}'.format(scores[which][0]))
         if opts.save_recs:
