@@ -323,12 +323,14 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
         (const void*)k_score_fwd_k64, (const void*)k_score_fwd_t2, (const void*)k_score_fwd_t3, (const void*)k_score_mt_4s, (const void*)k_score_bmt,
         (const void*)k_score_bwd_n, (const void*)k_gru_bwd_fused, (const void*)k_gru_fwd_fused, (const void*)k_score_bwd_w, (const void*)k_score_bwd2,
         (const void*)k_gru_bwd_a_w4, (const void*)k_gru_bwd_a_w8d, (const void*)k_gru_bwd_b, (const void*)k_dense_grad<32>,
-        (const void*)k_score_store, (const void*)k_score_count, (const void*)k_topk_fused, (const void*)k_topk_stored, (const void*)k_topk_fused_x,
-        (const void*)k_topk_stored_x, (const void*)k_topk_fused_g, (const void*)k_topk_stored_g, (const void*)k_topk_sample, (const void*)k_topk_rank,
-        (const void*)k_topk_rank_x, (const void*)k_topk_stored_ev, (const void*)k_topk_events_q, (const void*)k_sim_range<false>, (const void*)k_sim_range<true>,
+        (const void*)k_score_store, (const void*)k_score_count, (const void*)k_sim_range<false>, (const void*)k_sim_range<true>,
         (const void*)k_mmr_rerank<false>, (const void*)k_mmr_rerank<true>,
-        (const void*)k_scan_bf16<2>, (const void*)k_scan_bf16<4>, (const void*)k_scan_bf16<8>, (const void*)k_scan_bf16<2, TkGrow>,
-        (const void*)k_scan_bf16<4, TkGrow>, (const void*)k_scan_bf16<8, TkGrow>};
+#define TK_PTR(name, ...) (const void*)name,
+#define SCAN_PTR(NCH, E) (const void*)k_scan_bf16<NCH, E>,
+        TK_FORMS(TK_PTR) SCAN_FORMS(SCAN_PTR)      // every form of the two range kernels: the lists themselves
+#undef TK_PTR
+#undef SCAN_PTR
+    };
     auto opt_in = [&](const void* kern) { return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, big); };
     for (const void* kern : lds_kernels) HIPCHK(opt_in(kern));
     for (auto& row : K_LOSS_ROWS) for (auto kern : row) HIPCHK(opt_in((const void*)kern));

@@ -199,20 +199,14 @@ int g4r_recommend_events(g4r_model* m, const int32_t* in_idx, const int32_t* out
             // the noise key of a column and of the target are g4r_evaluate's, which scores [targets | items]: column Mt + j, target i
             const int* tie_col = items ? (const int*)e_iota : tgt;
             const TkRanges g = tk_ranges(m, Mt, n_cand, TK_TN);
-            const int tpr = g.tpr, R = g.R;
-            const dim3 grid(R, g.row_blocks);
             const TkEvents ev = {e_ts, m->p_cnt, mode == G4R_RANK_TIEBREAKING ? tie_col : (const int*)nullptr, items ? (long long)Mt : 0LL, (unsigned)t,
                                  seen ? (const int4*)(e_seen + t * B) : (const int4*)nullptr, e_sitems, e_sfirst, e_mask};
             if (!sm) {
                 predict_gru(m, e_in + t * B, Mt);
                 const float* hsrc = (const float*)m->phout[top];
                 hipLaunchKernelGGL(k_score_cand, dim3(Mt), dim3(256), 0, s, (const DevModel*)m->d_dm, hsrc, tgt, (const int4*)e_work, e_ts, 1);
-                if (excl)
-                    hipLaunchKernelGGL(k_topk_rank_x, grid, dim3(256), TK_SMEM_FUSED_X + TK_SEL_EV, s, (const DevModel*)m->d_dm, hsrc, Mt, d_items,
-                                       (long long)n_cand, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk.p, ev);
-                else
-                    hipLaunchKernelGGL(k_topk_rank, grid, dim3(256), TK_SMEM_FUSED, s, (const DevModel*)m->d_dm, hsrc, Mt, d_items,
-                                       (long long)n_cand, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk.p, ev);
+                if (excl) tk_launch<false, true>(m, s, g, hsrc, Mt, d_items, n_cand, nullptr, 0, k, ev);      // k_topk_rank_x
+                else tk_launch<false, false>(m, s, g, hsrc, Mt, d_items, n_cand, nullptr, 0, k, ev);          // k_topk_rank
                 hipLaunchKernelGGL(k_rank_counts, dim3(cdiv(Mt, 256)), dim3(256), 0, s, m->p_cnt, Mt, (int)mode, m->p_ranks);
                 m->ev_scans += 1;
                 m->ev_launches += 2 * d.n_layers + 3;
@@ -239,16 +233,13 @@ int g4r_recommend_events(g4r_model* m, const int32_t* in_idx, const int32_t* out
                     m->ev_scans += 2;
                     m->ev_launches += 2;
                 }
-                if (excl)
-                    hipLaunchKernelGGL(k_topk_stored_ev, grid, dim3(256), TK_SMEM_STORED_X + TK_SEL_EV, s, (const DevModel*)m->d_dm, (const float*)m->phout[top],
-                                       Mt, d_items, (long long)n_cand, (const float*)m->p_scores.p, (long long)ldo, (int)k, tpr, m->p_topk.p, ev);
-                else
-                    hipLaunchKernelGGL(k_topk_stored, grid, dim3(256), TK_SMEM_STORED, s, (const DevModel*)m->d_dm, (const float*)m->phout[top],
-                                       Mt, d_items, (long long)n_cand, (const float*)m->p_scores.p, (long long)ldo, (int)k, tpr, m->p_topk.p);
+                const float* hsrc = (const float*)m->phout[top];
+                if (excl) tk_launch<true, true>(m, s, g, hsrc, Mt, d_items, n_cand, (const float*)m->p_scores.p, ldo, k, ev);      // k_topk_stored_ev
+                else tk_launch<true, false>(m, s, g, hsrc, Mt, d_items, n_cand, (const float*)m->p_scores.p, ldo, k);              // k_topk_stored
                 m->ev_scans += 1;
                 m->ev_launches += 1;
             }
-            hipLaunchKernelGGL(k_events_merge, dim3(Mt), dim3(256), 0, s, (const uint2*)m->p_topk.p, R, (int)k, (const long long*)(e_place + t * B), d_items,
+            hipLaunchKernelGGL(k_events_merge, dim3(Mt), dim3(256), 0, s, (const uint2*)m->p_topk.p, g.R, (int)k, (const long long*)(e_place + t * B), d_items,
                                (const float*)m->p_ranks, (const float*)e_ts, o_items, o_scores, o_rank, o_ts);
             // hidden rows of sessions that ended with this step start from zero
             state_zero_rows(m, e_reset + t * B, Mt);

@@ -135,18 +135,16 @@ int g4r_loglik_events(g4r_model* m, const int32_t* in_idx, const int32_t* out_id
             const int* tgt = e_out + t * B;
             const int* d_items = items ? (const int*)e_items : (const int*)nullptr;
             const TkRanges g = tk_ranges(m, Mt, n_cand, TK_TN);
-            const dim3 grid(g.R, g.row_blocks);
             const TkEvents ev = {e_ts, m->p_cnt, (const int*)nullptr, 0LL, (unsigned)t, seen ? (const int4*)(e_seen + t * B) : (const int4*)nullptr,
                                  e_sitems, e_sfirst, e_mask};
             predict_gru(m, e_in + t * B, Mt);
             const float* hsrc = (const float*)m->phout[top];
             hipLaunchKernelGGL(k_score_cand, dim3(Mt), dim3(256), 0, s, (const DevModel*)m->d_dm, hsrc, tgt, (const int4*)e_work, e_ts, 1);
-            hipLaunchKernelGGL(k_topk_rank_x, grid, dim3(256), TK_SMEM_FUSED_X + TK_SEL_EV, s, (const DevModel*)m->d_dm, hsrc, Mt, d_items,
-                               (long long)n_cand, (const float*)nullptr, 0LL, 1, g.tpr, m->p_topk.p, ev);
+            tk_launch<false, true>(m, s, g, hsrc, Mt, d_items, n_cand, nullptr, 0, 1, ev);      // pass A: k_topk_rank_x
             hipLaunchKernelGGL(k_topk_merge, dim3(Mt), dim3(256), 0, s, (const uint2*)m->p_topk.p, g.R, 1, m->sm_zcol.p, m->sm_zeta.p);
             HIPCHK(hipMemsetAsync(m->sm_Q.p, 0, (size_t)Mt * sizeof(unsigned long long), s));
-            hipLaunchKernelGGL(k_topk_events_q, grid, dim3(256), TK_SMEM_LSE_EV, s, (const DevModel*)m->d_dm, hsrc, Mt, d_items, (long long)n_cand,
-                               (const float*)nullptr, 0LL, 1, g.tpr, m->p_topk.p, TkEventsLse{ev, TkLse{(const float*)m->sm_zeta.p, 1, m->sm_Q.p, invT}});
+            tk_launch<false, true>(m, s, g, hsrc, Mt, d_items, n_cand, nullptr, 0, 1,
+                                   TkEventsLse{ev, TkLse{(const float*)m->sm_zeta.p, 1, m->sm_Q.p, invT}});      // pass B: k_topk_events_q
             hipLaunchKernelGGL(k_loglik_finish, dim3(cdiv(Mt, 256)), dim3(256), 0, s, (const long long*)(e_place + t * B), (const float*)e_ts,
                                (const float*)m->sm_zeta.p, (const unsigned long long*)m->sm_Q.p, m->p_cnt, Mt, o_z, o_zeta, o_Q);
             // hidden rows of sessions that ended with this step start from zero

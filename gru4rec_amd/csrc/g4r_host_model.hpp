@@ -372,19 +372,10 @@ static inline bool is_softmax(const DevModel& d) { return d.final_act == G4R_ACT
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static constexpr auto k_score_store = k_score_all<32, false>;     // scores -> memory
 static constexpr auto k_score_count = k_score_all<32, true>;      // scores compared with the row's target on the fly
-static constexpr auto k_topk_fused = k_topk_range<false, false>;         // scores selected as they are produced (element-wise final activation)
-static constexpr auto k_topk_stored = k_topk_range<true, false>;         // selection over p_scores (softmax / softmax_logit)
-static constexpr auto k_topk_fused_x = k_topk_range<false, true, TkExcl>;        // the same two with exclusions (g4r_recommend_step_filtered)
-static constexpr auto k_topk_stored_x = k_topk_range<true, true, TkExcl>;
-static constexpr auto k_topk_fused_g = k_topk_range<false, true, TkGrow>;        // the same two with lists that grow on the device (g4r_continue_sessions)
-static constexpr auto k_topk_stored_g = k_topk_range<true, true, TkGrow>;
-static constexpr auto k_topk_sample = k_topk_range<false, true, TkSample>;      // selection on the Gumbel-perturbed key (g4r_sample_sessions)
-static constexpr auto k_topk_sample_q = k_topk_range<false, true, TkSampleLse>;  // the same draw + the row normaliser Q (g4r_sample_sessions_lp)
-static constexpr auto k_topk_fused_q = k_topk_range<false, true, TkGrowLse>;     // k_topk_fused_g + Q (launched with k = 1)
-static constexpr auto k_topk_rank = k_topk_range<false, false, TkEvents>;        // g4r_recommend_events: k_topk_fused + the rank counters of k_score_count
-static constexpr auto k_topk_rank_x = k_topk_range<false, true, TkEvents>;       // + the session-list / mask exclusions
-static constexpr auto k_topk_stored_ev = k_topk_range<true, true, TkEvents>;     // softmax / softmax_logit with those exclusions (no counters)
-static constexpr auto k_topk_events_q = k_topk_range<false, true, TkEventsLse>;  // g4r_loglik_events: the row normaliser Q under those exclusions (k = 1)
+// the forms of k_topk_range by name: k_topk_fused, k_topk_stored, ... (TK_FORMS, g4r_topk_kernels.cuh, says which is which)
+#define TK_NAME(name, STORED, EXCL, ...) static constexpr auto name = k_topk_range<STORED, EXCL, ##__VA_ARGS__>;
+TK_FORMS(TK_NAME)
+#undef TK_NAME
 
 static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 // dynamic LDS of the tile-GEMM kernels (g4r_gemm.cuh)

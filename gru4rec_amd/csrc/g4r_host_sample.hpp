@@ -137,34 +137,27 @@ static int sample_run(g4r_model* m, const int64_t* hist_offs, const int32_t* his
         }
         const TkGrow gx{(const long long*)m->p_xoffs.p, (const int*)m->ro_xlen.p, (const int*)m->p_xitems.p, d_mask};
         hipLaunchKernelGGL(k_sample_expand, dim3(rows), dim3(64), 0, m->stream, from_replay, (const int*)m->r_len, S, hsess, m->rz[L - 1], d.Dtop);
-        const TkRanges g = tk_ranges(m, rows, n_sel, TK_TN);
-        if (m->p_topk.reserve(m, (int64_t)rows * g.R * k)) return -1;
-        const dim3 grid(g.R, g.row_blocks);
+        TkRanges g;
+        if (tk_reserve(m, rows, n_sel, TK_TN, k, &g)) return -1;
+        auto range = [&](const float* hsrc, int kk, auto x) { tk_launch<false, true>(m, m->stream, g, hsrc, rows, d_items, n_sel, nullptr, 0, kk, x); };
         for (int s = 0; s < steps; ++s) {
             if (s > 0) gru_step(m, bb, (s - 1) & 1, (const int*)m->ro_in.p, rows);
             const float* hsrc = s > 0 ? (const float*)m->rhout[L - 1] : (const float*)m->rz[L - 1];
             const unsigned step = (unsigned)(first_step + s);
             const TkSample sx{gx.beg, gx.len, gx.items, gx.mask, (const unsigned*)m->sm_rowid.p, (unsigned long long)seed, step, invT};
             if (top_k)
-                hipLaunchKernelGGL(k_topk_fused_g, grid, dim3(256), TK_SMEM_FUSED_X, m->stream, (const DevModel*)m->d_dm, hsrc, rows, d_items,
-                                   (long long)n_sel, (const float*)nullptr, 0LL, (int)k, g.tpr, m->p_topk.p, gx);
+                range(hsrc, k, gx);                                                                         // k_topk_fused_g
             else if (lp) {      // zeta first: the exact selection's top-1, then the draw's scan forms Q relative to it
-                hipLaunchKernelGGL(k_topk_fused_g, grid, dim3(256), TK_SMEM_FUSED_X, m->stream, (const DevModel*)m->d_dm, hsrc, rows, d_items,
-                                   (long long)n_sel, (const float*)nullptr, 0LL, 1, g.tpr, m->p_topk.p, gx);
+                range(hsrc, 1, gx);
                 hipLaunchKernelGGL(k_topk_merge, dim3(rows), dim3(256), 0, m->stream, (const uint2*)m->p_topk.p, g.R, 1, m->sm_zcol.p, m->sm_zeta.p);
                 HIPCHK(hipMemsetAsync(m->sm_Q.p, 0, (size_t)rows * sizeof(unsigned long long), m->stream));
-                hipLaunchKernelGGL(k_topk_sample_q, grid, dim3(256), TK_SMEM_LSE, m->stream, (const DevModel*)m->d_dm, hsrc, rows, d_items,
-                                   (long long)n_sel, (const float*)nullptr, 0LL, 1, g.tpr, m->p_topk.p,
-                                   TkSampleLse{sx, TkLse{(const float*)m->sm_zeta.p, 1, m->sm_Q.p, invT}});
+                range(hsrc, 1, TkSampleLse{sx, TkLse{(const float*)m->sm_zeta.p, 1, m->sm_Q.p, invT}});     // k_topk_sample_q
             } else
-                hipLaunchKernelGGL(k_topk_sample, grid, dim3(256), TK_SMEM_SAMPLE, m->stream, (const DevModel*)m->d_dm, hsrc, rows, d_items,
-                                   (long long)n_sel, (const float*)nullptr, 0LL, 1, g.tpr, m->p_topk.p, sx);
+                range(hsrc, 1, sx);                                                                         // k_topk_sample
             hipLaunchKernelGGL(k_topk_merge, dim3(rows), dim3(256), 0, m->stream, (const uint2*)m->p_topk.p, g.R, (int)k, m->p_tcols.p, m->p_tscores.p);
             if (nucleus) {      // Q over the whole eligible set, relative to the list's first z; the k = 1 lists it leaves in p_topk are not read
                 HIPCHK(hipMemsetAsync(m->sm_Q.p, 0, (size_t)rows * sizeof(unsigned long long), m->stream));
-                hipLaunchKernelGGL(k_topk_fused_q, grid, dim3(256), TK_SMEM_LSE, m->stream, (const DevModel*)m->d_dm, hsrc, rows, d_items,
-                                   (long long)n_sel, (const float*)nullptr, 0LL, 1, g.tpr, m->p_topk.p,
-                                   TkGrowLse{gx, TkLse{(const float*)m->p_tscores.p, (int)k, m->sm_Q.p, invT}});
+                range(hsrc, 1, TkGrowLse{gx, TkLse{(const float*)m->p_tscores.p, (int)k, m->sm_Q.p, invT}});     // k_topk_fused_q
             }
             if (top_k && (lp || nucleus))
                 hipLaunchKernelGGL(k_sample_pick_lp, dim3(rows), dim3(64), 0, m->stream, (const int*)m->p_tcols.p, (const float*)m->p_tscores.p, (int)k,
@@ -269,16 +262,13 @@ int g4r_session_log_partition(g4r_model* m, const int64_t* hist_offs, const int3
         if (!citems.empty()) HIPCHK(hipMemcpyAsync(m->p_xitems.p, citems.data(), citems.size() * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
         const TkGrow gx{(const long long*)m->p_xoffs.p, (const int*)m->ro_xlen.p, (const int*)m->p_xitems.p,
                         excl_mask ? (const unsigned*)m->p_xmask.p : nullptr};
-        const TkRanges g = tk_ranges(m, Cc, n_sel, TK_TN);
-        if (m->p_topk.reserve(m, (int64_t)Cc * g.R)) return -1;
-        const dim3 grid(g.R, g.row_blocks);
-        hipLaunchKernelGGL(k_topk_fused_g, grid, dim3(256), TK_SMEM_FUSED_X, m->stream, (const DevModel*)m->d_dm, hsrc, Cc, d_items,
-                           (long long)n_sel, (const float*)nullptr, 0LL, 1, g.tpr, m->p_topk.p, gx);
+        TkRanges g;
+        if (tk_reserve(m, Cc, n_sel, TK_TN, 1, &g)) return -1;
+        tk_launch<false, true>(m, m->stream, g, hsrc, Cc, d_items, n_sel, nullptr, 0, 1, gx);      // k_topk_fused_g
         hipLaunchKernelGGL(k_topk_merge, dim3(Cc), dim3(256), 0, m->stream, (const uint2*)m->p_topk.p, g.R, 1, m->sm_zcol.p, m->sm_zeta.p);
         HIPCHK(hipMemsetAsync(m->sm_Q.p, 0, (size_t)Cc * sizeof(unsigned long long), m->stream));
-        hipLaunchKernelGGL(k_topk_fused_q, grid, dim3(256), TK_SMEM_LSE, m->stream, (const DevModel*)m->d_dm, hsrc, Cc, d_items,
-                           (long long)n_sel, (const float*)nullptr, 0LL, 1, g.tpr, m->p_topk.p,
-                           TkGrowLse{gx, TkLse{(const float*)m->sm_zeta.p, 1, m->sm_Q.p, invT}});
+        tk_launch<false, true>(m, m->stream, g, hsrc, Cc, d_items, n_sel, nullptr, 0, 1,
+                               TkGrowLse{gx, TkLse{(const float*)m->sm_zeta.p, 1, m->sm_Q.p, invT}});      // k_topk_fused_q
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(tz.data(), m->sm_zeta.p, (size_t)Cc * sizeof(float), hipMemcpyDeviceToHost, m->stream));
         HIPCHK(hipMemcpyAsync(tq.data(), m->sm_Q.p, (size_t)Cc * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));

@@ -1,6 +1,6 @@
 // g4r_host_topk.hpp -- part of libgru4rec_hip.so's host code; included once, by g4r_api.hip (one translation unit: the kernels are templates
 // instantiated there).  Holds: top-k selection over rows of the top layer's output: the k checks, the range geometry, the candidate upload,
-// topk_select, the exclusion lists and masks, the two-stage bf16 scan (topk_select_scan, g4r_scan_table_release).
+// the one launch of each range kernel (tk_launch, scan_launch), topk_select, the exclusion lists and masks, the two-stage bf16 scan (topk_select_scan, g4r_scan_table_release).
 // ------------------------------------------------------------------------------------------------ exact top-k
 // the k checks of every top-k entry over a model's scores: recommend_step_run and the three session wrappers (g4r_host_sessions.hpp)
 static int recommend_check(g4r_model* m, const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t* out_cols, float* out_scores) {
@@ -36,37 +36,39 @@ static TkRanges tk_ranges(const g4r_model* m, int mrows, int64_t n_cols, int til
     const int tpr = (int)((tiles + R0 - 1) / R0);
     return TkRanges{row_blocks, tpr, (int)((tiles + tpr - 1) / tpr)};
 }
+// *g = those ranges, with p_topk grown to the k entries per row and range they leave
+static int tk_reserve(g4r_model* m, int mrows, int64_t n_cols, int tile_cols, int64_t k, TkRanges* g) {
+    *g = tk_ranges(m, mrows, n_cols, tile_cols);
+    return m->p_topk.reserve(m, (int64_t)mrows * g->R * k);
+}
+
+// THE launch of k_topk_range: the form is <STORED, EXCL> and the type of the trailing argument x (none: the unfiltered forms).  The
+// grid is g's, the lists go to p_topk, the dynamic LDS is the form's (tk_smem).  scores / ldo: STORED only, NULL / 0 otherwise
+extern "C++" {      // (this file is included inside extern "C")
+template <bool STORED, bool EXCL, typename... X>
+static void tk_launch(g4r_model* m, hipStream_t s, const TkRanges& g, const float* hsrc, int mrows, const int* d_items, int64_t n_sel,
+                      const float* scores, int64_t ldo, int k, X... x) {
+    hipLaunchKernelGGL((k_topk_range<STORED, EXCL, X...>), dim3(g.R, g.row_blocks), dim3(256), (tk_smem<STORED, EXCL, X...>()), s,
+                       (const DevModel*)m->d_dm, hsrc, mrows, d_items, (long long)n_sel, scores, (long long)ldo, k, g.tpr, m->p_topk.p, x...);
+}
+}  // extern "C++"
 
 // selection of rows [0, mrows) of hsrc (the top layer's output) into p_tcols / p_tscores, enqueued only.  scores / ldo: the same
 // rows' materialised scores (softmax / softmax_logit), unused otherwise.  ex (device exclusions) NULL: the unfiltered kernels;
 // gx (g4r_continue_sessions, instead of ex): exclusions whose per-row lists grow on the device
 static int topk_select(g4r_model* m, const float* hsrc, int32_t mrows, const int* d_items, int64_t n_sel, int32_t k, const TkExcl* ex,
                        const float* scores, int64_t ldo, const TkGrow* gx = nullptr) {
-    const bool sm = is_softmax(m->dm);
-    const TkRanges g = tk_ranges(m, mrows, n_sel, TK_TN);
-    const int tpr = g.tpr, R = g.R;
+    TkRanges g;
     const int64_t nout = (int64_t)mrows * k;
-    if (m->p_topk.reserve(m, (int64_t)mrows * R * k) || m->p_tcols.reserve(m, nout) || m->p_tscores.reserve(m, nout)) return -1;
-    const dim3 grid(R, g.row_blocks);
-    if (gx && sm)
-        hipLaunchKernelGGL(k_topk_stored_g, grid, dim3(256), TK_SMEM_STORED_X, m->stream, (const DevModel*)m->d_dm, hsrc,
-                           (int)mrows, d_items, (long long)n_sel, scores, (long long)ldo, (int)k, tpr, m->p_topk.p, *gx);
-    else if (gx)
-        hipLaunchKernelGGL(k_topk_fused_g, grid, dim3(256), TK_SMEM_FUSED_X, m->stream, (const DevModel*)m->d_dm, hsrc,
-                           (int)mrows, d_items, (long long)n_sel, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk.p, *gx);
-    else if (sm && !ex)
-        hipLaunchKernelGGL(k_topk_stored, grid, dim3(256), TK_SMEM_STORED, m->stream, (const DevModel*)m->d_dm, hsrc,
-                           (int)mrows, d_items, (long long)n_sel, scores, (long long)ldo, (int)k, tpr, m->p_topk.p);
-    else if (sm)
-        hipLaunchKernelGGL(k_topk_stored_x, grid, dim3(256), TK_SMEM_STORED_X, m->stream, (const DevModel*)m->d_dm, hsrc,
-                           (int)mrows, d_items, (long long)n_sel, scores, (long long)ldo, (int)k, tpr, m->p_topk.p, *ex);
-    else if (!ex)
-        hipLaunchKernelGGL(k_topk_fused, grid, dim3(256), TK_SMEM_FUSED, m->stream, (const DevModel*)m->d_dm, hsrc,
-                           (int)mrows, d_items, (long long)n_sel, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk.p);
-    else
-        hipLaunchKernelGGL(k_topk_fused_x, grid, dim3(256), TK_SMEM_FUSED_X, m->stream, (const DevModel*)m->d_dm, hsrc,
-                           (int)mrows, d_items, (long long)n_sel, (const float*)nullptr, 0LL, (int)k, tpr, m->p_topk.p, *ex);
-    hipLaunchKernelGGL(k_topk_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->p_topk.p, R, (int)k, m->p_tcols.p, m->p_tscores.p);
+    if (tk_reserve(m, mrows, n_sel, TK_TN, k, &g) || m->p_tcols.reserve(m, nout) || m->p_tscores.reserve(m, nout)) return -1;
+    auto launch = [&](auto... x) {      // stored (softmax / softmax_logit) or fused, with the exclusions x or none
+        if (is_softmax(m->dm)) tk_launch<true, sizeof...(x) != 0>(m, m->stream, g, hsrc, mrows, d_items, n_sel, scores, ldo, k, x...);
+        else tk_launch<false, sizeof...(x) != 0>(m, m->stream, g, hsrc, mrows, d_items, n_sel, nullptr, 0, k, x...);
+    };
+    if (gx) launch(*gx);
+    else if (ex) launch(*ex);
+    else launch();
+    hipLaunchKernelGGL(k_topk_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->p_topk.p, g.R, (int)k, m->p_tcols.p, m->p_tscores.p);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -86,6 +88,15 @@ static int scan_check(g4r_model* m, const int32_t* item_idx, int64_t n_sel, int3
 
 // k-chunks of 64 columns of the padded top layer (the instantiations of k_scan_bf16: 2, 4, 8)
 static int scan_nch(const DevModel& d) { return d.Dtop <= 128 ? 2 : d.Dtop <= 256 ? 4 : 8; }
+// THE launch of k_scan_bf16 on the model's stream: the form is scan_nch's k-chunks and the type of the exclusions x (TkExcl or TkGrow)
+extern "C++" {
+template <typename E>
+static void scan_launch(g4r_model* m, const TkRanges& g, const float* hsrc, int mrows, const int* d_items, int64_t n_sel, int c, E x) {
+    const auto kern = scan_nch(m->dm) == 2 ? k_scan_bf16<2, E> : scan_nch(m->dm) == 4 ? k_scan_bf16<4, E> : k_scan_bf16<8, E>;
+    hipLaunchKernelGGL(kern, dim3(g.R, g.row_blocks), dim3(256), SCN_SMEM, m->stream, (const DevModel*)m->d_dm, hsrc, mrows, d_items,
+                       (long long)n_sel, (const uint4*)m->s_tab.p, c, g.tpr, m->p_topk.p, x);
+}
+}  // extern "C++"
 
 // the bf16 shadow table of Wy, (re)built on the stream when anything may have changed Wy since the last build
 static int scan_table_ensure(g4r_model* m) {
@@ -120,12 +131,11 @@ int g4r_scan_table_release(g4r_model* m) {
 static int topk_select_scan(g4r_model* m, const float* hsrc, int32_t mrows, const int* d_items, int64_t n_sel, int32_t k, int32_t c,
                             const TkExcl* ex, const TkGrow* gx = nullptr, bool work_ready = false) {
     if (scan_table_ensure(m)) return -1;
-    const TkRanges g = tk_ranges(m, mrows, n_sel, SCN_TN);
-    const int tpr = g.tpr, R = g.R;
+    TkRanges g;
     const int nl = (c + k - 1) / k, L = nl * k;
     const int64_t nout = (int64_t)mrows * k, P = (int64_t)mrows * c;
     if (mrows > 65535) return fail("the bf16 scan takes at most 65535 rows per call");
-    if (m->p_topk.reserve(m, (int64_t)mrows * R * c) || m->p_tcols.reserve(m, nout) || m->p_tscores.reserve(m, nout)) return -1;
+    if (tk_reserve(m, mrows, n_sel, SCN_TN, c, &g) || m->p_tcols.reserve(m, nout) || m->p_tscores.reserve(m, nout)) return -1;
     // k_score_cand's work items depend on c and the row count only: row r's list is positions [r c, (r + 1) c)
     if (!work_ready) {
         m->s_work.clear();
@@ -136,27 +146,9 @@ static int topk_select_scan(g4r_model* m, const float* hsrc, int32_t mrows, cons
         m->c_topk.reserve(m, (int64_t)mrows * L) || m->s_cols.reserve(m, P) || m->s_cnt.reserve(m, (int64_t)mrows))
         return -1;
     if (!work_ready) HIPCHK(hipMemcpyAsync(m->c_work.p, m->s_work.data(), m->s_work.size() * sizeof(int4), hipMemcpyHostToDevice, m->stream));
-    const dim3 grid(R, g.row_blocks);
-    const TkExcl x = ex ? *ex : TkExcl{nullptr, nullptr, nullptr};
-#define SCAN_LAUNCH(N) hipLaunchKernelGGL(k_scan_bf16<N>, grid, dim3(256), SCN_SMEM, m->stream, (const DevModel*)m->d_dm, hsrc, (int)mrows, d_items, \
-                                          (long long)n_sel, (const uint4*)m->s_tab.p, (int)c, tpr, m->p_topk.p, x)
-#define SCAN_LAUNCH_G(N) hipLaunchKernelGGL((k_scan_bf16<N, TkGrow>), grid, dim3(256), SCN_SMEM, m->stream, (const DevModel*)m->d_dm, hsrc, (int)mrows, \
-                                            d_items, (long long)n_sel, (const uint4*)m->s_tab.p, (int)c, tpr, m->p_topk.p, *gx)
-    if (gx)
-        switch (scan_nch(m->dm)) {
-            case 2: SCAN_LAUNCH_G(2); break;
-            case 4: SCAN_LAUNCH_G(4); break;
-            default: SCAN_LAUNCH_G(8); break;
-        }
-    else
-        switch (scan_nch(m->dm)) {
-            case 2: SCAN_LAUNCH(2); break;
-            case 4: SCAN_LAUNCH(4); break;
-            default: SCAN_LAUNCH(8); break;
-        }
-#undef SCAN_LAUNCH
-#undef SCAN_LAUNCH_G
-    hipLaunchKernelGGL(k_scan_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->p_topk.p, R, (int)c, d_items, m->s_cols.p, m->c_items.p,
+    if (gx) scan_launch(m, g, hsrc, mrows, d_items, n_sel, c, *gx);
+    else scan_launch(m, g, hsrc, mrows, d_items, n_sel, c, ex ? *ex : TkExcl{nullptr, nullptr, nullptr});
+    hipLaunchKernelGGL(k_scan_merge, dim3(mrows), dim3(256), 0, m->stream, (const uint2*)m->p_topk.p, g.R, (int)c, d_items, m->s_cols.p, m->c_items.p,
                        m->c_scores.p, m->s_cnt.p);
 #if !(defined(G4R_MUTATE) && G4R_MUTATE == 12)      // test build 12: stage 2 ranks by the approximate scores k_scan_merge left there
     hipLaunchKernelGGL(k_score_cand, dim3((unsigned)m->s_work.size()), dim3(256), 0, m->stream, (const DevModel*)m->d_dm, hsrc,

@@ -20,17 +20,8 @@
 #include "g4r_beam_kernels.cuh"
 #include "g4r_cand_kernels.cuh"
 
-// LDS of the sampling form of the range kernel: the EXCL fused kernel's (the row ids live in registers, 8 per lane)
-#define TK_SMEM_SAMPLE TK_SMEM_FUSED_X
-static_assert(TK_SMEM_SAMPLE <= TK_SMEM_FUSED_X + SC_BM * 4 && TK_SMEM_SAMPLE <= 156 * 1024,
-              "the sampling form of the range kernel may add at most a row-id column to the EXCL fused kernel's LDS");
-
-template __global__ void k_topk_range<false, true, TkSample>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkSample);
-
-// the two forms that also form the row normaliser Q in their scan (TkLse, g4r_topk_kernels.cuh): the draw + the sum; the exact
-// selection (launched with k = 1) + the sum
-template __global__ void k_topk_range<false, true, TkSampleLse>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkSampleLse);
-template __global__ void k_topk_range<false, true, TkGrowLse>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkGrowLse);
+// (The three forms of the range kernel are instantiated with the others, from TK_FORMS.  The sampling form's LDS is the EXCL fused
+// kernel's: the row ids live in registers, 8 per lane.)
 
 // One wave per draw row q = r S + j (grid = rows S, 64 threads): every layer's state of session row r -- in st.src (even history length)
 // or st.src1 (odd) -- is copied to row q of st.dst, the row's top-layer output hsrc[r] to hdst[q] (Dtop floats each)

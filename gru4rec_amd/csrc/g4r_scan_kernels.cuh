@@ -64,7 +64,8 @@ __device__ __forceinline__ float scan_thr_float(unsigned long long key) {
 template <int NCH, typename E = TkExcl>
 __global__ __launch_bounds__(256) void k_scan_bf16(const DevModel* __restrict__ mp, const float* h, int mrows, const int* item_idx,
                                                    long long n_sel, const uint4* tab, int c, int tpr, uint2* ws, E xarg) {
-    const TkExcl ex = tk_excl(xarg);
+    using F = TkForm<E>;
+    const TkExcl ex = F::excl(xarg);
     constexpr int KS = 4 * NCH;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const DevModel& m = *mp;
@@ -86,10 +87,10 @@ __global__ __launch_bounds__(256) void k_scan_bf16(const DevModel* __restrict__ 
     const int lrow = 32 * wid + r32, grow = rbase + lrow;      // this lane's row: local, global
     if (half == 0) {
         s_qn[lrow] = 0; s_ln[lrow] = 0; s_thr[lrow] = 0ull;
-        if constexpr (tk_is_grow<E>::value) {
+        if constexpr (F::GROW) {
             long long b;
             int n;
-            tk_row_list(xarg, grow, mrows, b, n);
+            F::row_list(F::grow(xarg), grow, mrows, b, n);
             s_xb[lrow] = b;
             s_xn[lrow] = n;
         } else {
@@ -266,9 +267,10 @@ __global__ __launch_bounds__(256) void k_scan_pack(const float* sc, const int* c
                                        : make_uint2(0u, 0xFFFFFFFFu);
 }
 
-template __global__ void k_scan_bf16<2>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkExcl);
-template __global__ void k_scan_bf16<4>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkExcl);
-template __global__ void k_scan_bf16<8>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkExcl);
-template __global__ void k_scan_bf16<2, TkGrow>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkGrow);
-template __global__ void k_scan_bf16<4, TkGrow>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkGrow);
-template __global__ void k_scan_bf16<8, TkGrow>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, TkGrow);
+// The six forms, once: F(k-chunks of 64 columns of the padded top layer, the type of the exclusions).  The instantiations here and
+// the LDS opt-in at create (g4r_host_create.hpp) are this list; scan_launch (g4r_host_topk.hpp) picks NCH by scan_nch.
+#define SCAN_FORMS(F) F(2, TkExcl) F(4, TkExcl) F(8, TkExcl) F(2, TkGrow) F(4, TkGrow) F(8, TkGrow)
+#define SCAN_INSTANTIATE(NCH, E) \
+    template __global__ void k_scan_bf16<NCH, E>(const DevModel*, const float*, int, const int*, long long, const uint4*, int, int, uint2*, E);
+SCAN_FORMS(SCAN_INSTANTIATE)
+#undef SCAN_INSTANTIATE

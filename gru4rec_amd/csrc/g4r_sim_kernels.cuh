@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void k_sim_gather(const float* __restrict__ T,
 // LDS: k_topk_fused's [queues | counts | lengths | thresholds | A tile | B tile | column items] + the rows' query items.  The merge
 // scratch aliases the B tile (rewritten for every tile of columns), so that a table of at most SC_KC floats per row keeps its A
 // tile -- the workgroup's 128 query rows -- for the whole range.
-#define SIM_SMEM (TK_SMEM_FUSED + SC_BM * 4)
+#define SIM_SMEM (tk_smem<false, false>() + SC_BM * 4)
 static_assert(4 * TK_SCRATCH_WAVE <= TK_TN * (SC_KC + 2) * 4, "the merge scratch must fit in the B tile");
 static_assert(SIM_SMEM <= 156 * 1024, "k_sim_range LDS over the 156 KiB the kernels may ask for");
 

@@ -1,14 +1,20 @@
 // Top-K next-item recommendation kernels (gfx950), behind g4r_recommend_step (not in the reference).
-//   k_topk_fused   scores of a column range (the k_score_all chain) -> the range's k best per row, nothing stored
-//   k_topk_stored  the same selection over a score matrix already in memory (softmax / softmax_logit final activations)
+//   k_topk_range   ONE kernel template, k_topk_range<STORED, EXCL, X...>: the k best of a column range per row.  Its thirteen
+//                  instantiations ("forms") are listed once, by name, in TK_FORMS below
 //   k_topk_merge   the ranges' lists of one row -> the row's k best (int32 column, float score)
-//   k_topk_rank    k_topk_fused for g4r_recommend_events: the same scan also counts, per row, the columns whose score is greater
-//                  than / equal to the row's target score (the counters of k_score_all<.., COUNT = true>, finished by k_rank_counts)
 //   k_events_merge k_topk_merge writing its row, the row's rank and target score at the event's place in the call's output
-// The TkGrow instantiations (g4r_continue_sessions) are the EXCL ones reading per-row lists that grow on the device between launches.
-// The EXCL = true instantiations of k_topk_range (behind g4r_recommend_step_filtered) drop excluded items where a survivor queue is
-// merged into its row's list (topk_merge_row): a global bit mask over item indices and a sorted per-row list (at most
-// G4R_EXCLUDE_MAX items).  The EXCL = false instantiations are the unfiltered kernels, instruction for instruction.
+// A form is three things.  STORED: the scores are read from a matrix already in memory (softmax / softmax_logit final activations)
+// instead of being computed tile by tile as k_score_all computes them (fused: nothing stored).  EXCL: excluded items are dropped where
+// a survivor queue is merged into its row's list (topk_merge_row): a global bit mask over item indices and a sorted per-row list (at
+// most G4R_EXCLUDE_MAX items); the EXCL = false forms without a trailing argument are the unfiltered kernels, instruction for
+// instruction.  X: the type of the ONE trailing kernel argument (none for the two unfiltered forms), which says what else the scan
+// does -- rank counters (TkEvents), lists that grow between launches (TkGrow), a draw (TkSample), the row normaliser (Tk...Lse).
+// What a trailing-argument type carries is stated once, in its description TkForm<X> next to the structs; the kernel reads its
+// constexpr flags and its views from there, and the dynamic LDS of a form (tk_smem) follows from the same flags.
+// To add a form: (1) a struct for the trailing argument with its TkForm specialisation (only what the type HAS; a type that pairs an
+// existing one with the row normaliser derives from TkFormLse), (2) one line in TK_FORMS -- the explicit instantiation, the host-side
+// name and the LDS opt-in at create all come from that line, (3) one tk_launch call (g4r_host_topk.hpp).  A launch of a form that
+// is not in TK_FORMS has no device code: the build refuses the library (build.py, kernels_without_device_code).
 //
 // Order (the contract of g4r_recommend_step): score descending, equal scores (float ==, so -0.0 == +0.0) by the lower column,
 // NaN below every number.  topk_key() maps (score, column) to one 64-bit key whose unsigned order IS that order; the keys of one
@@ -34,30 +40,12 @@ __device__ __forceinline__ unsigned long long topk_key(float v, unsigned col) {
 // (score bits, column) as stored in the lists; column 0xFFFFFFFF pads a list (columns are < 2^31) and keys 0
 __device__ __forceinline__ unsigned long long topk_key(uint2 e) { return e.y == 0xFFFFFFFFu ? 0ull : topk_key(__uint_as_float(e.x), e.y); }
 
-// LDS of the range kernels: [queues | queue counts | list lengths | thresholds | scratch (k_topk_stored) or score tile (k_topk_fused)]
-// The fused kernel's merge scratch aliases its A tile: a merge runs between the last read of one tile and the first write of the next.
-#define TK_SCRATCH_WAVE (TK_MAX * 8 + TK_Q * 8)          // bytes: a copy of the row's list + the sorted queue keys
-#define TK_SMEM_SEL (SC_BM * TK_Q * 8 + SC_BM * 4 * 2 + SC_BM * 8)
-#define TK_SCRATCH_WAVE_X (TK_SCRATCH_WAVE + G4R_EXCLUDE_MAX * 4)   // EXCL: + the row's sorted exclusion list
-#define TK_SMEM_STORED (TK_SMEM_SEL + 4 * TK_SCRATCH_WAVE)
-#define TK_SMEM_FUSED (TK_SMEM_SEL + ((SC_BM + TK_TN) * (SC_KC + 2) + TK_TN) * 4)
-#define TK_SEL_X (SC_BM * 12)           // EXCL: + every row's list start (8 B) and length (4 B), staged once per workgroup
-#define TK_SMEM_STORED_X (TK_SMEM_STORED + TK_SEL_X + 4 * (TK_SCRATCH_WAVE_X - TK_SCRATCH_WAVE))
-#define TK_SMEM_FUSED_X (TK_SMEM_FUSED + TK_SEL_X)
-#define TK_SEL_EV (SC_BM * 4)           // TkEvents with EXCL: + every row's position in its session
-// LDS budget (160 KiB per CU): k_topk_stored 77,824 B, 95,744 B with EXCL; k_topk_fused 150,912 B, 152,448 B with EXCL, the four
-// waves' merge scratch (4 x 2,560 B, 4 x 6,656 B = 26,624 B with EXCL) aliasing its 66,560 B A tile; 152,976 B for the forms with
-// the row normaliser (TK_SMEM_LSE, below)
-static_assert(4 * TK_SCRATCH_WAVE_X <= SC_BM * (SC_KC + 2) * 4, "the EXCL merge scratch must fit in the fused kernel's A tile");
-static_assert(TK_SMEM_STORED_X + TK_SEL_EV <= 156 * 1024 && TK_SMEM_FUSED_X + TK_SEL_EV <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
-
+// ---- the parts a trailing argument can carry: five plain structs of device pointers and scalars -------------------------------
 // Exclusions of one g4r_recommend_step_filtered call (device pointers, NULL = none): row r's sorted, duplicate-free item indices are
 // items[offs[r] .. offs[r + 1]), at most G4R_EXCLUDE_MAX of them; bit (i & 31) of mask[i >> 5] excludes item index i in every row.
 struct TkExcl { const long long* offs; const int* items; const unsigned* mask; };
-__device__ __forceinline__ TkExcl tk_excl() { return TkExcl{}; }
-__device__ __forceinline__ TkExcl tk_excl(TkExcl e) { return e; }
 
-// The trailing argument of the g4r_recommend_events instantiations (k_topk_range<.., .., TkEvents>), one evaluation step's rows.
+// The trailing argument of the g4r_recommend_events forms (k_topk_range<.., .., TkEvents>), one evaluation step's rows.
 // Rank counters (fused form only): tscore[r] is row r's target score (k_score_cand: g4r_predict_step's bit pattern); every column
 // of the range whose score is greater / equal adds to cnt[2 r] / cnt[2 r + 1] -- excluded columns too: exclusions shape the list,
 // never the rank.  tie_col != NULL ('tiebreaking'): score (r, n) is moved by tie_noise(r, n + col_off) and the target's by
@@ -70,57 +58,30 @@ struct TkEvents {
     const float* tscore; int* cnt; const int* tie_col; long long col_off; unsigned tie_ctr;
     const int4* seen; const int* s_items; const int* s_first; const unsigned* mask;
 };
-__device__ __forceinline__ TkExcl tk_excl(TkEvents e) { return TkExcl{nullptr, e.s_items, e.mask}; }
-__device__ __forceinline__ TkEvents tk_events() { return TkEvents{}; }
-__device__ __forceinline__ TkEvents tk_events(TkExcl) { return TkEvents{}; }
-__device__ __forceinline__ TkEvents tk_events(TkEvents e) { return e; }
-template <typename... X> struct tk_is_events { static constexpr bool value = false; };
-template <> struct tk_is_events<TkEvents> { static constexpr bool value = true; };
 
-// The trailing argument of the g4r_continue_sessions instantiations (k_topk_range<.., true, TkGrow>, k_scan_bf16<.., TkGrow>): TkExcl
-// whose per-row lists GROW on the device between launches.  Row r's sorted, duplicate-free list is items[beg[r] .. beg[r] + len[r]);
-// the host leaves slack behind every list, k_rollout_feed (g4r_rollout_kernels.cuh) inserts into it and bumps len[r].  A type of its
-// own, so that the TkExcl instantiations keep their kernel arguments and their code.
+// The trailing argument of the g4r_continue_sessions forms (k_topk_range<.., true, TkGrow>, k_scan_bf16<.., TkGrow>): TkExcl whose
+// per-row lists GROW on the device between launches.  Row r's sorted, duplicate-free list is items[beg[r] .. beg[r] + len[r]); the
+// host leaves slack behind every list, k_rollout_feed (g4r_rollout_kernels.cuh) inserts into it and bumps len[r].  A type of its
+// own -- as every one below -- so that the forms that exist keep their kernel arguments and their code.
 struct TkGrow { const long long* beg; const int* len; const int* items; const unsigned* mask; };
-__device__ __forceinline__ TkExcl tk_excl(TkGrow g) { return TkExcl{nullptr, g.items, g.mask}; }
-__device__ __forceinline__ TkEvents tk_events(TkGrow) { return TkEvents{}; }
-// row `row`'s list start and length (0, 0 for a row past the call's) as the range kernels stage them
-__device__ __forceinline__ void tk_row_list(const TkGrow& g, int row, int mrows, long long& b, int& n) {
-    const bool on = row < mrows;
-    b = on ? g.beg[row] : 0ll;
-    n = on ? g.len[row] : 0;
-}
-template <typename... X> struct tk_is_grow { static constexpr bool value = false; };
-template <> struct tk_is_grow<TkGrow> { static constexpr bool value = true; };
-__device__ __forceinline__ TkGrow tk_grow() { return TkGrow{}; }
-__device__ __forceinline__ TkGrow tk_grow(TkExcl) { return TkGrow{}; }
-__device__ __forceinline__ TkGrow tk_grow(TkEvents) { return TkGrow{}; }
-__device__ __forceinline__ TkGrow tk_grow(TkGrow g) { return g; }
 
-// The trailing argument of the g4r_sample_sessions instantiation (k_topk_range<false, true, TkSample>): TkGrow's fields, plus what turns
-// the selection into a draw.  Row r of the launch is the draw with row id row_id[r]; the value pushed to a row's queue, compared with
+// The trailing argument of the g4r_sample_sessions form (k_topk_range<false, true, TkSample>): TkGrow's fields, plus what turns the
+// selection into a draw.  Row r of the launch is the draw with row id row_id[r]; the value pushed to a row's queue, compared with
 // its threshold and kept in the lists is key = fl32(fl32(z * invT) + gumbel_noise(seed, row id, step, item)) in place of the score z:
 // the argmax of the keys over the eligible columns is a draw from softmax(z / T) over them (Gumbel-max), and the threshold, queue
-// and merge logic are the selection's own.  Again a type of its own: the other instantiations keep their arguments and their code.
+// and merge logic are the selection's own.
+// (Every score gets its noise.  Skipping the Philox call and the logarithms of a score whose key cannot beat its row's threshold
+// whatever the noise -- g < 17 -- gives the same results and was measured: it does not pay, profiles/sample_sessions.md.)
 struct TkSample {
     const long long* beg; const int* len; const int* items; const unsigned* mask;
     const unsigned* row_id; unsigned long long seed; unsigned step; float invT;
 };
-__device__ __forceinline__ TkExcl tk_excl(TkSample s) { return TkExcl{nullptr, s.items, s.mask}; }
-__device__ __forceinline__ TkEvents tk_events(TkSample) { return TkEvents{}; }
-__device__ __forceinline__ TkGrow tk_grow(TkSample s) { return TkGrow{s.beg, s.len, s.items, s.mask}; }
-template <> struct tk_is_grow<TkSample> { static constexpr bool value = true; };
-template <typename... X> struct tk_is_sample { static constexpr bool value = false; };
-template <> struct tk_is_sample<TkSample> { static constexpr bool value = true; };
-__device__ __forceinline__ TkSample tk_sample() { return TkSample{}; }
-__device__ __forceinline__ TkSample tk_sample(TkExcl) { return TkSample{}; }
-__device__ __forceinline__ TkSample tk_sample(TkEvents) { return TkSample{}; }
-__device__ __forceinline__ TkSample tk_sample(TkGrow) { return TkSample{}; }
-__device__ __forceinline__ TkSample tk_sample(TkSample s) { return s; }
+
 // The row normaliser of g4r_sample_sessions_lp / g4r_session_log_partition: Q[row] = the sum over the row's ELIGIBLE candidate positions
 // of q = lse_term(z, zeta[row * zs], invT), an exact 64-bit integer -- every term is a function of the term alone and integer adds
 // commute, so Q has the same bits however the columns are cut into ranges and whatever order the workgroups finish in.  zeta: the
 // largest eligible z of the row (the exact selection's top-1), so that every term is at most 2^39; Q is zeroed on the stream first.
+// Never a trailing argument itself: it rides with another one (TkSampleLse, TkGrowLse, TkEventsLse).
 struct TkLse { const float* zeta; int zs; unsigned long long* Q; float invT; };
 // q of one score: d = fl32(fl32(z - zeta) * invT) (two roundings, no FMA), q = rn(2^39 * expf(d)) (the library's expf; the product
 // with a power of two is exact); NaN gives 0
@@ -129,48 +90,122 @@ __device__ __forceinline__ unsigned long long lse_term(float z, float zeta, floa
     if (d != d) return 0ull;
     return __float2ull_rn(0x1p39f * expf(d));
 }
-// The trailing arguments of the two instantiations that form Q in their scan (k_topk_range<false, true, ...>), types of their own again:
-// TkSampleLse = TkSample's draw plus the sum, TkGrowLse = TkGrow's selection (launched with k = 1) plus the sum.
-struct TkSampleLse { TkSample s; TkLse l; };
-struct TkGrowLse { TkGrow g; TkLse l; };
-__device__ __forceinline__ TkExcl tk_excl(TkSampleLse x) { return tk_excl(x.s); }
-__device__ __forceinline__ TkExcl tk_excl(TkGrowLse x) { return tk_excl(x.g); }
-__device__ __forceinline__ TkEvents tk_events(TkSampleLse) { return TkEvents{}; }
-__device__ __forceinline__ TkEvents tk_events(TkGrowLse) { return TkEvents{}; }
-__device__ __forceinline__ TkGrow tk_grow(TkSampleLse x) { return tk_grow(x.s); }
-__device__ __forceinline__ TkGrow tk_grow(TkGrowLse x) { return x.g; }
-__device__ __forceinline__ TkSample tk_sample(TkSampleLse x) { return x.s; }
-__device__ __forceinline__ TkSample tk_sample(TkGrowLse) { return TkSample{}; }
-template <> struct tk_is_grow<TkSampleLse> { static constexpr bool value = true; };
-template <> struct tk_is_grow<TkGrowLse> { static constexpr bool value = true; };
-template <> struct tk_is_sample<TkSampleLse> { static constexpr bool value = true; };
-template <typename... X> struct tk_is_lse { static constexpr bool value = false; };
-template <> struct tk_is_lse<TkSampleLse> { static constexpr bool value = true; };
-template <> struct tk_is_lse<TkGrowLse> { static constexpr bool value = true; };
-__device__ __forceinline__ TkLse tk_lse() { return TkLse{}; }
-template <typename T> __device__ __forceinline__ TkLse tk_lse(T) { return TkLse{}; }
-__device__ __forceinline__ TkLse tk_lse(TkSampleLse x) { return x.l; }
-__device__ __forceinline__ TkLse tk_lse(TkGrowLse x) { return x.l; }
-// LDS of those two: the EXCL fused kernel's + per tile every row's 32-bit word of the columns its own list takes (SC_BM x 4 B) and the
-// word of the columns the global mask takes
-#define TK_SMEM_LSE (TK_SMEM_FUSED_X + (SC_BM + 4) * 4)
-static_assert(TK_SMEM_LSE <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
-// The trailing argument of the g4r_loglik_events instantiation (k_topk_range<false, true, TkEventsLse>): the row normaliser under
-// TkEvents' eligibility.  The rows' lists are the SESSION-level ones (e.seen / e.s_items / e.s_first), so the per-tile word of a row
-// marks a column only when its item is found in the session list with s_first <= the row's position; the mask as before.  No rank
-// counters (e.tscore / e.cnt / e.tie_col are not read); launched with k = 1, its lists unused.  A type of its own once more.
-struct TkEventsLse { TkEvents e; TkLse l; };
-__device__ __forceinline__ TkExcl tk_excl(TkEventsLse x) { return tk_excl(x.e); }
-__device__ __forceinline__ TkEvents tk_events(TkEventsLse x) { return x.e; }
-__device__ __forceinline__ TkSample tk_sample(TkEventsLse) { return TkSample{}; }
-__device__ __forceinline__ TkLse tk_lse(TkEventsLse x) { return x.l; }
-template <> struct tk_is_events<TkEventsLse> { static constexpr bool value = true; };
-template <> struct tk_is_lse<TkEventsLse> { static constexpr bool value = true; };
-// LDS: the forms' with the row normaliser + every row's position in its session (TK_SEL_EV): 153,488 B
-#define TK_SMEM_LSE_EV (TK_SMEM_LSE + TK_SEL_EV)
-static_assert(TK_SMEM_LSE_EV <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
-// (Every score gets its noise.  Skipping the Philox call and the logarithms of a score whose key cannot beat its row's threshold
-// whatever the noise -- g < 17 -- gives the same results and was measured: it does not pay, profiles/sample_sessions.md.)
+
+// ---- one description per trailing-argument pack: TkForm<X...> -----------------------------------------------------------------
+// k_topk_range, and k_scan_bf16 for its one argument, ask a pack four yes/no questions (constexpr flags) and five views:
+//   EV    TkEvents' rows: session-list exclusions with positions; rank counters in the fused form without LSE
+//   GROW  the rows' lists are (begin, length) pairs that may grow between launches, staged by row_list
+//   SMP   the value selected on is the draw's key
+//   LSE   the scan also forms the row normaliser Q
+//   excl(x) / events(x) / grow(x) / sample(x) / lse(x)   the part as its own struct
+// TkFormNone answers "no such part" to everything: every flag false, every view the all-NULL struct.  It is the whole description of
+// the empty pack (the unfiltered forms take no trailing argument) and the base of every other one, which states only what it has.
+template <typename... X> struct TkFormNone {
+    static constexpr bool EV = false, GROW = false, SMP = false, LSE = false;
+    static __device__ __forceinline__ TkExcl excl(X...) { return TkExcl{}; }
+    static __device__ __forceinline__ TkEvents events(X...) { return TkEvents{}; }
+    static __device__ __forceinline__ TkGrow grow(X...) { return TkGrow{}; }
+    static __device__ __forceinline__ TkSample sample(X...) { return TkSample{}; }
+    static __device__ __forceinline__ TkLse lse(X...) { return TkLse{}; }
+    // (GROW) row `row`'s list start and length, 0 and 0 for a row past the call's, as the range kernels stage them
+    static __device__ __forceinline__ void row_list(const TkGrow& g, int row, int mrows, long long& b, int& n) {
+        const bool on = row < mrows;
+        b = on ? g.beg[row] : 0ll;
+        n = on ? g.len[row] : 0;
+    }
+};
+template <typename... X> struct TkForm : TkFormNone<X...> {};
+template <> struct TkForm<TkExcl> : TkFormNone<TkExcl> {
+    static __device__ __forceinline__ TkExcl excl(TkExcl e) { return e; }
+};
+template <> struct TkForm<TkEvents> : TkFormNone<TkEvents> {
+    static constexpr bool EV = true;
+    static __device__ __forceinline__ TkExcl excl(TkEvents e) { return TkExcl{nullptr, e.s_items, e.mask}; }
+    static __device__ __forceinline__ TkEvents events(TkEvents e) { return e; }
+};
+template <> struct TkForm<TkGrow> : TkFormNone<TkGrow> {
+    static constexpr bool GROW = true;
+    static __device__ __forceinline__ TkExcl excl(TkGrow g) { return TkExcl{nullptr, g.items, g.mask}; }
+    static __device__ __forceinline__ TkGrow grow(TkGrow g) { return g; }
+};
+template <> struct TkForm<TkSample> : TkFormNone<TkSample> {
+    static constexpr bool GROW = true, SMP = true;
+    static __device__ __forceinline__ TkExcl excl(TkSample s) { return TkExcl{nullptr, s.items, s.mask}; }
+    static __device__ __forceinline__ TkGrow grow(TkSample s) { return TkGrow{s.beg, s.len, s.items, s.mask}; }
+    static __device__ __forceinline__ TkSample sample(TkSample s) { return s; }
+};
+// The description of a type C = { A a; TkLse l; } that pairs another trailing argument with the row normaliser: A's own, through a,
+// plus LSE.  (The fused EXCL forms only, as k_topk_range asserts.)
+template <typename C, typename A> struct TkFormLse : TkForm<A> {
+    static constexpr bool LSE = true;
+    static __device__ __forceinline__ TkExcl excl(const C& x) { return TkForm<A>::excl(x.a); }
+    static __device__ __forceinline__ TkEvents events(const C& x) { return TkForm<A>::events(x.a); }
+    static __device__ __forceinline__ TkGrow grow(const C& x) { return TkForm<A>::grow(x.a); }
+    static __device__ __forceinline__ TkSample sample(const C& x) { return TkForm<A>::sample(x.a); }
+    static __device__ __forceinline__ TkLse lse(const C& x) { return x.l; }
+};
+// TkSampleLse = TkSample's draw plus the sum (g4r_sample_sessions_lp).  TkGrowLse = TkGrow's selection (launched with k = 1) plus the
+// sum (top_p, g4r_session_log_partition).  Eligibility is decided per score: per tile every row's 32-bit word of the columns its own
+// list takes and the word of the columns the global mask takes.
+struct TkSampleLse { TkSample a; TkLse l; };
+template <> struct TkForm<TkSampleLse> : TkFormLse<TkSampleLse, TkSample> {};
+struct TkGrowLse { TkGrow a; TkLse l; };
+template <> struct TkForm<TkGrowLse> : TkFormLse<TkGrowLse, TkGrow> {};
+// TkEventsLse (g4r_loglik_events): the row normaliser under TkEvents' eligibility.  The rows' lists are the SESSION-level ones (seen /
+// s_items / s_first), so the per-tile word of a row marks a column only when its item is found in the session list with s_first <=
+// the row's position; the mask as before.  No rank counters (tscore / cnt / tie_col are not read); launched with k = 1, its lists unused.
+struct TkEventsLse { TkEvents a; TkLse l; };
+template <> struct TkForm<TkEventsLse> : TkFormLse<TkEventsLse, TkEvents> {};
+
+// ---- the forms, once -----------------------------------------------------------------------------------------------------------
+// F(host-side name, STORED, EXCL[, trailing-argument type]).  The explicit instantiations (TK_INSTANTIATE, after the kernel), the
+// host's names (g4r_host_model.hpp) and the LDS opt-in at create (g4r_host_create.hpp) are this list and nothing else.
+//   k_topk_fused / k_topk_stored       scores selected as they are produced (element-wise final activation) / out of p_scores (softmax)
+//   k_topk_fused_x / k_topk_stored_x   the same two with exclusions (g4r_recommend_step_filtered)
+//   k_topk_fused_g / k_topk_stored_g   the same two with lists that grow on the device (g4r_continue_sessions)
+//   k_topk_rank / k_topk_rank_x        g4r_recommend_events: k_topk_fused + the rank counters of k_score_count / + its exclusions
+//   k_topk_stored_ev                   softmax / softmax_logit with those exclusions (no counters)
+//   k_topk_events_q                    g4r_loglik_events: the row normaliser Q under those exclusions (k = 1)
+//   k_topk_sample                      selection on the Gumbel-perturbed key (g4r_sample_sessions)
+//   k_topk_sample_q / k_topk_fused_q   the same draw + Q (g4r_sample_sessions_lp) / k_topk_fused_g + Q (launched with k = 1)
+#define TK_FORMS(F)                                \
+    F(k_topk_fused, false, false)                  \
+    F(k_topk_stored, true, false)                  \
+    F(k_topk_fused_x, false, true, TkExcl)         \
+    F(k_topk_stored_x, true, true, TkExcl)         \
+    F(k_topk_fused_g, false, true, TkGrow)         \
+    F(k_topk_stored_g, true, true, TkGrow)         \
+    F(k_topk_rank, false, false, TkEvents)         \
+    F(k_topk_rank_x, false, true, TkEvents)        \
+    F(k_topk_stored_ev, true, true, TkEvents)      \
+    F(k_topk_events_q, false, true, TkEventsLse)   \
+    F(k_topk_sample, false, true, TkSample)        \
+    F(k_topk_sample_q, false, true, TkSampleLse)   \
+    F(k_topk_fused_q, false, true, TkGrowLse)
+
+// ---- LDS of a form, from the flags the kernel carves it by ---------------------------------------------------------------------
+// [queues | queue counts | list lengths | thresholds | (EXCL) list starts, lengths | (EXCL, EV) positions | tail]; the tail is the
+// four waves' merge scratch (STORED) or the score tile [A | B | the tile's items | (LSE) the rows' words, the mask's word] (fused),
+// whose A tile the merge scratch aliases: a merge runs between the last read of one tile and the first write of the next.
+#define TK_SCRATCH_WAVE (TK_MAX * 8 + TK_Q * 8)          // bytes: a copy of the row's list + the sorted queue keys
+#define TK_SCRATCH_WAVE_X (TK_SCRATCH_WAVE + G4R_EXCLUDE_MAX * 4)   // EXCL: + the row's sorted exclusion list
+#define TK_SMEM_SEL (SC_BM * TK_Q * 8 + SC_BM * 4 * 2 + SC_BM * 8)
+#define TK_SEL_X (SC_BM * 12)           // EXCL: + every row's list start (8 B) and length (4 B), staged once per workgroup
+#define TK_SEL_EV (SC_BM * 4)           // EXCL with EV: + every row's position in its session
+#define TK_TILE (((SC_BM + TK_TN) * (SC_KC + 2) + TK_TN) * 4)
+#define TK_TILE_LSE ((SC_BM + 4) * 4)   // LSE: + per tile every row's word of the columns its list takes, and the global mask's word
+static_assert(4 * TK_SCRATCH_WAVE_X <= SC_BM * (SC_KC + 2) * 4, "the EXCL merge scratch must fit in the fused kernel's A tile");
+// bytes in front of the tail (k_topk_range finds its tail here)
+constexpr size_t tk_smem_head(bool EXCL, bool EV) { return TK_SMEM_SEL + (EXCL ? TK_SEL_X + (EV ? TK_SEL_EV : 0) : 0); }
+// The dynamic LDS of k_topk_range<STORED, EXCL, X...>, of a 160 KiB CU: stored 77,824 B, 95,744 B with EXCL, 96,256 B with TkEvents'
+// positions; fused 150,912 B, 152,448 B with EXCL (the sampling form too: its row ids live in registers), 152,960 B with TkEvents'
+// positions; with the row normaliser 152,976 B, TkEventsLse 153,488 B
+template <bool STORED, bool EXCL, typename... X> constexpr size_t tk_smem() {
+    using F = TkForm<X...>;
+    constexpr size_t n = tk_smem_head(EXCL, F::EV) + (STORED ? 4 * (EXCL ? TK_SCRATCH_WAVE_X : TK_SCRATCH_WAVE) : TK_TILE + (F::LSE ? TK_TILE_LSE : 0));
+    static_assert(n <= 156 * 1024, "top-k LDS over the 156 KiB the kernels may ask for");
+    return n;
+}
 
 // One wave merges the survivor queue of local row r into the row's sorted list L (global, length n <= k): the queue is sorted in
 // registers (bitonic over the 64 lanes), then every element's place in the union is its own index plus the number of elements of
@@ -259,25 +294,27 @@ __device__ __forceinline__ void topk_merge_row(int r, uint2* L, int k, uint2* sq
 // k best of the row in key order, entries past the range's column count padded with column 0xFFFFFFFF (key 0).
 // STORED = false: the tile is computed as k_score_all computes it (one ascending-k fp32 MFMA chain from zero, + By, then the final
 // activation), so every score is bit-identical to g4r_predict_step's.  STORED = true: the tile is read from `sc` (ldo floats per row).
-// EXCL: the exclusions (one trailing TkExcl argument) apply at every merge (topk_merge_row), the per-wave scratch grows by the
-// row's list (TK_SCRATCH_WAVE_X).  EXCL = false takes no trailing argument, so its kernel arguments -- and with them its code --
-// are those of the unfiltered kernel.  TkSample (fused, EXCL): the value selected on is the draw's key, see the struct.
-// TkSampleLse / TkGrowLse (fused, EXCL): the scan also adds every ELIGIBLE score's lse_term to the row's Q, see TkLse.
-// TkEventsLse (fused, EXCL): that sum under TkEvents' session-list eligibility (g4r_loglik_events).
+// EXCL: the exclusions (the trailing argument's excl view and the rows' lists) apply at every merge (topk_merge_row), the per-wave
+// scratch grows by the row's list (TK_SCRATCH_WAVE_X).  The unfiltered forms take no trailing argument, so their kernel arguments --
+// and with them their code -- are those of the unfiltered kernel.  What else a form does is read from F = TkForm<X...>:
+// EV (with EXCL) the rows' lists are the session lists with positions, (fused, no LSE) the rank counters; GROW the lists are
+// (begin, length) pairs; SMP (fused, EXCL) the value selected on is the draw's key, see TkSample; LSE (fused, EXCL) the scan also adds
+// every ELIGIBLE score's lse_term to the row's Q, see TkLse -- under EV with the session lists' eligibility (g4r_loglik_events).
 template <bool STORED, bool EXCL, typename... X>
 __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__ mp, const float* h, int mrows, const int* item_idx,
                                                     long long n_sel, const float* sc, long long ldo, int k, int tpr, uint2* ws,
                                                     X... xs) {
-    constexpr bool EV = tk_is_events<X...>::value;      // g4r_recommend_events: rank counters, session-list exclusions
-    static_assert(sizeof...(X) == ((EXCL || EV) ? 1 : 0), "EXCL takes one TkExcl, the events form one TkEvents");
-    const TkExcl ex = tk_excl(xs...);
-    const TkEvents ev = tk_events(xs...);
-    constexpr bool SMP = tk_is_sample<X...>::value;      // g4r_sample_sessions: keys in place of scores
-    static_assert(!SMP || (EXCL && !STORED), "the sampling form is fused and takes its (possibly empty) lists");
-    const TkSample smp = tk_sample(xs...);
-    constexpr bool LSE = tk_is_lse<X...>::value;         // the row normaliser Q formed in the scan (TkLse)
-    static_assert(!LSE || (EXCL && !STORED), "the forms with the row normaliser are fused and take their (possibly empty) lists");
-    const TkLse lse = tk_lse(xs...);
+    using F = TkForm<X...>;
+    constexpr bool EV = F::EV;        // g4r_recommend_events: rank counters, session-list exclusions
+    static_assert(sizeof...(X) == ((EXCL || EV) ? 1 : 0), "EXCL takes one trailing argument (its lists), an EV form its TkEvents, the unfiltered forms none");
+    constexpr bool SMP = F::SMP;      // g4r_sample_sessions: keys in place of scores
+    static_assert(!SMP || (EXCL && !STORED), "an SMP form is fused and takes its (possibly empty) lists");
+    constexpr bool LSE = F::LSE;      // the row normaliser Q formed in the scan (TkLse)
+    static_assert(!LSE || (EXCL && !STORED), "an LSE form is fused and takes its (possibly empty) lists");
+    const TkExcl ex = F::excl(xs...);
+    const TkEvents ev = F::events(xs...);
+    const TkSample smp = F::sample(xs...);
+    const TkLse lse = F::lse(xs...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, lg = lane >> 4;
     uint2* s_q = reinterpret_cast<uint2*>(smem);
@@ -287,7 +324,7 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
     long long* s_xb = reinterpret_cast<long long*>(s_thr + SC_BM);      // (EXCL only)
     int* s_xn = reinterpret_cast<int*>(s_xb + SC_BM);
     int* s_xp = s_xn + SC_BM;                                           // (EXCL with TkEvents only)
-    char* tail = EXCL ? reinterpret_cast<char*>(s_xn + (EV ? 2 : 1) * SC_BM) : reinterpret_cast<char*>(s_thr + SC_BM);
+    char* tail = reinterpret_cast<char*>(smem) + tk_smem_head(EXCL, EV);
     float* sA = reinterpret_cast<float*>(tail);
     const int ldk = SC_KC + 2;
     float* sB = sA + SC_BM * ldk;
@@ -307,11 +344,11 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
             const int4 w = (ev.seen && rbase + tid < mrows) ? ev.seen[rbase + tid] : make_int4(0, 0, 0, 0);
             s_xb[tid] = w.x; s_xn[tid] = w.y; s_xp[tid] = w.z;
         }
-    } else if constexpr (EXCL && tk_is_grow<X...>::value) {
+    } else if constexpr (EXCL && F::GROW) {
         if (tid < SC_BM) {
             long long b;
             int n;
-            tk_row_list(tk_grow(xs...), rbase + tid, mrows, b, n);
+            F::row_list(F::grow(xs...), rbase + tid, mrows, b, n);
             s_xb[tid] = b;
             s_xn[tid] = n;
         }
@@ -652,16 +689,11 @@ __global__ __launch_bounds__(256) void k_events_tscore(const float* sc, long lon
     if (r < mrows) out[r] = sc[(size_t)r * ldo + tcol[r]];
 }
 
-template __global__ void k_topk_range<false, false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
-template __global__ void k_topk_range<true, false>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*);
-template __global__ void k_topk_range<false, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);
-template __global__ void k_topk_range<true, true, TkExcl>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkExcl);
-template __global__ void k_topk_range<false, true, TkGrow>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkGrow);
-template __global__ void k_topk_range<true, true, TkGrow>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkGrow);
-template __global__ void k_topk_range<false, false, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
-template __global__ void k_topk_range<false, true, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
-template __global__ void k_topk_range<true, true, TkEvents>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEvents);
-template __global__ void k_topk_range<false, true, TkEventsLse>(const DevModel*, const float*, int, const int*, long long, const float*, long long, int, int, uint2*, TkEventsLse);
+#define TK_INSTANTIATE(name, STORED, EXCL, ...)                                                                                       \
+    template __global__ void k_topk_range<STORED, EXCL, ##__VA_ARGS__>(const DevModel*, const float*, int, const int*, long long, \
+                                                                       const float*, long long, int, int, uint2*, ##__VA_ARGS__);
+TK_FORMS(TK_INSTANTIATE)
+#undef TK_INSTANTIATE
 // g4r_loglik_events: row r of one step is the event at place[r] (as k_events_merge places it): its target's z, the row's zeta and Q
 // go there.  Clears the rank counters the k = 1 selection (k_topk_range<false, true, TkEvents>) left behind, as k_rank_counts does.
 __global__ __launch_bounds__(256) void k_loglik_finish(const long long* place, const float* tz, const float* zeta, const unsigned long long* Q,
