@@ -15,6 +15,10 @@ G4R_MAX_LAYERS = 8
 G4R_TOPK_MAX = 256      # largest k of g4r_recommend_step
 G4R_BEAM_MAX = 32       # widest beam of g4r_beam_sessions
 G4R_SAMPLE_MAX = 64     # most draws per session of g4r_sample_sessions
+G4R_AUDIENCE_MAX = 65536           # largest k of g4r_audience_sessions,
+G4R_AUDIENCE_ITEMS_MAX = 4096      # most items of one call,
+G4R_AUDIENCE_ENTRIES_MAX = 2 ** 23 # and the most items x k
+AUDIENCE_BY = {'score': 0, 'logprob': 1}      # G4R_AUDIENCE_*
 G4R_STREAM_GUMBEL = 0x47554D42      # Philox stream id (counter word 3) of its noise
 BEAM_COMBINE = {'sum': 0, 'product': 1}      # G4R_BEAM_*
 G4R_EXCLUDE_MAX = 1024  # most distinct items one row of g4r_recommend_step_filtered may exclude
@@ -54,7 +58,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_set_item_groups', 'g4r_get_item_groups', 'g4r_recommend_sessions_capped', 'g4r_continue_sessions_capped', 'g4r_cap_lists', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_loglik_events', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_audience_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_set_item_groups', 'g4r_get_item_groups', 'g4r_recommend_sessions_capped', 'g4r_continue_sessions_capped', 'g4r_cap_lists', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_loglik_events', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_debug_gumbel', 'g4r_debug_lse_terms', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -141,6 +145,7 @@ def lib():
                                       i32p, f32p, f32pp]
     L.g4r_sample_sessions_lp.argtypes = L.g4r_sample_sessions.argtypes + [C.c_float, f32p]
     L.g4r_session_log_partition.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i64p, i32p, u32p, C.c_float, f32p, u64p]
+    L.g4r_audience_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i32, i32, i32, C.c_float, i32, i32p, f32p, i32p]
     L.g4r_scan_table_release.argtypes = [vp]
     L.g4r_similar_items.argtypes = [vp, i32, i32, i32p, i64, i32p, i64, i32, i32, u32p, i32p, f32p]
     L.g4r_diversify_lists.argtypes = [vp, i32, i32, i32p, f32p, i64, i32, i32, C.c_float, i32, i32p, f32p]
@@ -649,6 +654,24 @@ class Model:
         _chk(lib().g4r_session_log_partition(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), n_sel, _i64(xo), _i32(xi), _u32(mask),
                                              float(temperature), _f32(zeta), _u64(Q)))
         return zeta, Q
+
+    def audience_sessions(self, hist_offs, hist_items, items, k, by='logprob', temperature=1.0, exclude_history=False, hidden=None):
+        """For each of the M item indices `items` the k sessions with the largest value, after replaying whole session histories
+        (g4r_audience_sessions; histories and hidden as in recommend_sessions): (sessions int32[M, k] -- indices into the histories,
+        -1 behind a row's count --, values float32[M, k] -- NaN there --, counts int32[M]).  by: 'score' / 'logprob'."""
+        offs, hi, n = _hist(hist_offs, hist_items)
+        it = np.ascontiguousarray(items, dtype=np.int32).ravel()
+        M, k = len(it), int(k)
+        if not 1 <= M <= G4R_AUDIENCE_ITEMS_MAX:
+            raise ValueError('the number of items must be in [1, %d]' % G4R_AUDIENCE_ITEMS_MAX)
+        if not 1 <= k <= G4R_AUDIENCE_MAX or M * k > G4R_AUDIENCE_ENTRIES_MAX:
+            raise ValueError('k must be in [1, %d] and items x k at most %d' % (G4R_AUDIENCE_MAX, G4R_AUDIENCE_ENTRIES_MAX))
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        sessions, values = _topk_out((M, k))
+        counts = np.empty(M, dtype=np.int32)
+        _chk(lib().g4r_audience_sessions(self.h, _i64(offs), _i32(hi), n, h0p, _i32(it), M, k, AUDIENCE_BY[by], float(temperature),
+                                         1 if exclude_history else 0, _i32(sessions), _f32(values), _i32(counts)))
+        return sessions, values, counts
 
     def debug_lse_terms(self, z, zeta, inv_t):
         """The terms of the row normaliser for the logits z relative to zeta (an array like z, or one value) at the float32 reciprocal

@@ -68,11 +68,26 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            26: "k_group_cap (g4r_*_capped, g4r_cap_lists) counts a position's earlier same-group positions from the start of its OWN wave "
                "only: the positions of earlier waves are forgotten, so pools of more than 64 keep too many",
            27: "the row normaliser of g4r_loglik_events takes a session item as seen only when its first occurrence is BEFORE the input "
-               "event (s_first < position): the input event's own item, first shown there, stays in Q"}
+               "event (s_first < position): the input event's own item, first shown there, stays in Q",
+           28: "k_audience_keys (g4r_audience_sessions) files a session under its index WITHIN its chunk (c0 is not added): calls of one "
+               "chunk stay correct, from the second chunk on the lists name the wrong sessions"}
 
 
 def mutant_path(k):
     return os.path.join(HERE, '_variants', 'libgru4rec_hip_mut%d.so' % k)
+
+
+def _mutant_jobs():
+    """hipcc processes build_mutants runs at a time (each takes one core and peaks at ~2 GB): half the cores this process may use, at
+    least 2 and at most 4 -- every variant added makes the list longer, two at a time no longer keeps a clean build() short.
+    G4R_BUILD_JOBS overrides."""
+    if os.environ.get('G4R_BUILD_JOBS'):
+        return max(1, int(os.environ['G4R_BUILD_JOBS']))
+    try:
+        cores = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cores = os.cpu_count() or 2
+    return max(2, min(4, cores // 2))
 
 
 def build_mutants(force=False, verbose=False):
@@ -94,7 +109,7 @@ def build_mutants(force=False, verbose=False):
         todo = stale()
         if todo:
             _host_object(verbose)
-            with ThreadPoolExecutor(min(len(todo), 2)) as ex:      # two hipcc at a time (each peaks at ~2 GB)
+            with ThreadPoolExecutor(min(len(todo), _mutant_jobs())) as ex:
                 list(ex.map(lambda k: _device(mutant_path(k), ['G4R_MUTATE=%d' % k], verbose, audit=(k != 4)), todo))
     return [mutant_path(k) for k in MUTANTS]
 

@@ -19,6 +19,7 @@
 #include "g4r_beam_kernels.cuh"
 #include "g4r_cand_kernels.cuh"
 #include "g4r_sample_kernels.cuh"
+#include "g4r_audience_kernels.cuh"
 #include "g4r_scan_kernels.cuh"
 #include "g4r_sim_kernels.cuh"
 #include "g4r_mmr_kernels.cuh"
@@ -41,6 +42,7 @@ extern "C" {
 #include "g4r_host_sessions.hpp"
 #include "g4r_host_beam.hpp"
 #include "g4r_host_sample.hpp"
+#include "g4r_host_audience.hpp"
 #include "g4r_host_events.hpp"
 #include "g4r_host_loglik.hpp"
 #include "g4r_host_similar.hpp"

@@ -25,10 +25,10 @@ void g4r_set_error(const char* fmt, ...) {
     } while (0)
 
 enum { KN_GRU_P1 = 0, KN_GRU_P2, KN_SCORE_FWD, KN_LOSS, KN_SCORE_BWD, KN_BWD_PRE, KN_BWD_A, KN_BWD_B, KN_DENSE, KN_ALLREDUCE,
-       KN_DENSE_APPLY, KN_SPARSE, KN_UPDATE, KN_BWD_FUSED, KN_FWD_FUSED, KN_GATE, KN_FLUSH, KN_SCAN, KN_FINISH, KN_GRU_V, KN_GRU_H, KN_GRU_DA, KN_GRU_DY, KN_OWNER_WINDOW, KN_COUNT };
+       KN_DENSE_APPLY, KN_SPARSE, KN_UPDATE, KN_BWD_FUSED, KN_FWD_FUSED, KN_GATE, KN_FLUSH, KN_SCAN, KN_FINISH, KN_GRU_V, KN_GRU_H, KN_GRU_DA, KN_GRU_DY, KN_OWNER_WINDOW, KN_AUD_KEYS, KN_AUD_MERGE, KN_COUNT };
 static const char* KN_NAMES[KN_COUNT] = {"k_gru_p1", "k_gru_p2", "k_score_fwd", "k_loss_rows", "k_score_bwd", "k_gru_bwd_pre",
                                          "k_gru_bwd_a", "k_gru_bwd_b", "k_dense_grad", "rccl_allreduce", "k_dense_apply",
-                                         "k_sparse_update", "k_update", "k_gru_bwd", "k_gru_fwd", "k_gru_gate", "k_sparse_flush", "k_defer_scan", "k_finish_rows", "k_gru_v", "k_gru_h", "k_gru_da", "k_gru_dy", "k_owner_window"};
+                                         "k_sparse_update", "k_update", "k_gru_bwd", "k_gru_fwd", "k_gru_gate", "k_sparse_flush", "k_defer_scan", "k_finish_rows", "k_gru_v", "k_gru_h", "k_gru_da", "k_gru_dy", "k_owner_window", "k_audience_keys", "k_audience_merge"};
 
 struct EvRec { int kn; hipEvent_t a, b; };
 
@@ -230,6 +230,12 @@ struct g4r_model {
     DevBuf<int> gc_items, gc_cols, gc_pos, gc_kept, gc_plen, gc_prior;
     DevBuf<float> gc_scores;
     DevBuf<long long> gc_pbeg;
+    // audience selection (g4r_audience_sessions; k_audience_keys / k_audience_merge): the M items repeated for every row of a chunk, their
+    // work items and scores live in c_items / c_work / c_scores; a chunk's entries [M][rows]; the running lists' two sides [M][k] each;
+    // (side, len)[M] twice, read and written alternately; what the call downloads, [M][k] each
+    DevBuf<ulonglong2> au_ent, au_list[2];
+    DevBuf<int> au_state, au_sess;
+    DevBuf<float> au_val;
     unsigned tie_ctr = 0;                      // evaluation step counter of the 'tiebreaking' noise stream
     // the last g4r_recommend_events / g4r_loglik_events call (g4r_get_debug "events_launches"): its steps, the launches whose grid spans the candidate
     // columns, all its launches, the pieces its lists came back in

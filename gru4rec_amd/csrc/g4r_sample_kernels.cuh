@@ -147,8 +147,7 @@ __global__ __launch_bounds__(256) void k_sample_logprob(const float* z, const fl
                                                         int steps, int s, float* lp) {
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= rows) return;
-    const float d = __fmul_rn(__fsub_rn(z[row], zeta[row]), invT);
-    lp[(size_t)row * steps + s] = (float)((double)d - log((double)Q[row] * 0x1p-39));
+    lp[(size_t)row * steps + s] = lse_logprob(z[row], zeta[row], Q[row], invT);
 }
 
 // out[p] = lse_term(z[p], zeta[p], invT): the function the scan calls

@@ -90,6 +90,13 @@ __device__ __forceinline__ unsigned long long lse_term(float z, float zeta, floa
     if (d != d) return 0ull;
     return __float2ull_rn(0x1p39f * expf(d));
 }
+// The log-probability softmax(z * invT) over a row's eligible positions gives the position with logit z: fl32((double)d - log((double)Q
+// * 2^-39)), d = fl32(fl32(z - zeta) * invT) (two roundings, no FMA); zeta and the integer Q: the row's normaliser (TkLse).  The one
+// expression behind k_sample_logprob and k_audience_keys: the same (z, zeta, Q, invT) give the same bits in either.
+__device__ __forceinline__ float lse_logprob(float z, float zeta, unsigned long long Q, float invT) {
+    const float d = __fmul_rn(__fsub_rn(z, zeta), invT);
+    return (float)((double)d - log((double)Q * 0x1p-39));
+}
 
 // ---- one description per trailing-argument pack: TkForm<X...> -----------------------------------------------------------------
 // k_topk_range, and k_scan_bf16 for its one argument, ask a pack four yes/no questions (constexpr flags) and five views:

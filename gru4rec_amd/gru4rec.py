@@ -1296,6 +1296,68 @@ class GRU4Rec:
             return res['logprob'], out_offs, res
         return res['logprob'], out_offs
 
+    def audience_sessions(self, histories, item_ids, k, by='logprob', temperature=1.0, exclude_history=False, hidden=None):
+        """Which sessions for this item?  For each of M items the k sessions with the largest value, selected on the device in one
+        stateless call: (sessions int64[M, k], values float32[M, k], counts int32[M]).  Not in the reference.
+
+          histories, hidden  as in recommend_sessions: N >= 1 non-empty sequences of item ids, any N, and the optional initial state.
+          item_ids           M >= 1 item ids, at most G4R_AUDIENCE_ITEMS_MAX = 4096; duplicates are allowed, every position gets its
+                             own list.
+          k                  the audience size per item, 1 <= k <= G4R_AUDIENCE_MAX = 65536 with M * k <= 2^23.  It is not bounded by
+                             G4R_TOPK_MAX and may exceed N.
+          by='score'         the value is the item's full-catalogue predict_next_batch score after the session's history: the bits
+                             score_candidates_sessions returns for an element-wise final activation.  Scores of different sessions are
+                             on one scale only where the model's loss puts them there, and softmax / softmax_logit models raise
+                             NotImplementedError: use by='logprob'.
+          by='logprob'       the value is the log-probability that softmax(z / temperature) over the session's eligible items -- the
+                             whole catalogue, at most 2^24 items -- gives the item; z is the predict_next_batch score, for softmax
+                             models the pre-activation value, as in loglik_gpu.  It is session_log_likelihood's value for the history
+                             followed by the item: fl32((double)d - log((double)Q * 2^-39)), d = fl32(fl32(z - zeta) / temperature),
+                             zeta and the exact integer Q of session_log_partition.
+          temperature        as in sample_sessions; read with by='logprob' only.
+          exclude_history    a session whose history holds the item is not eligible for that item and is never listed; with
+                             by='logprob' the history's items also leave the session's normaliser (session_log_partition's
+                             exclude_history, loglik_gpu's exclude_seen; a history of at most G4R_EXCLUDE_MAX = 1024 distinct items).
+
+        Row j holds the counts[j] <= k eligible sessions with the largest value for item_ids[j], as indices into `histories`, ordered
+        by value descending, then by the lower index, NaN last; entries at and after counts[j] have session -1 and value NaN.  The
+        result depends on nothing else: not on how the call is chunked (G4R_SESSIONS_CHUNK) nor on the company a session keeps.  The
+        histories are replayed 512 a chunk and the running lists stay on the device, so M * k entries reach the host whatever N is.
+        The prediction state is neither read nor changed.  Everything is checked before any device work: the histories and `hidden`
+        as in recommend_sessions, an unknown item id raises KeyError.
+        Deliberately left out: predict_for_item_ids, exclude, exclude_per_row, scan='bf16', return_hidden; group-level affinity (a
+        segment per item group); per-session caps across items."""
+        if self.error_during_train:
+            raise Exception
+        if by not in _native.AUDIENCE_BY:
+            raise ValueError("by = %r: it must be 'score' or 'logprob'" % (by,))
+        softmax = self._final[0] in (_native.ACT_IDS['softmax'], _native.ACT_IDS['softmax_logit'])
+        if by == 'score' and softmax:
+            raise NotImplementedError("by='score' is not implemented for final_act=%r (a softmax score is normalised over its own row and "
+                                      "the pre-activation values of different sessions are not on one scale): use by='logprob'" % self.final_act)
+        t32 = _check_temperature(temperature) if by == 'logprob' else np.float32(1)
+        ids = np.ravel(item_ids) if isinstance(item_ids, np.ndarray) else list(item_ids)
+        M = len(ids)
+        if not 1 <= M <= _native.G4R_AUDIENCE_ITEMS_MAX:
+            raise ValueError('item_ids holds %d items: between 1 and G4R_AUDIENCE_ITEMS_MAX = %d are needed' % (M, _native.G4R_AUDIENCE_ITEMS_MAX))
+        try:
+            ok = not isinstance(k, bool) and int(k) == k and 1 <= k <= _native.G4R_AUDIENCE_MAX
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('k = %r: it must be an integer in [1, G4R_AUDIENCE_MAX = %d]' % (k, _native.G4R_AUDIENCE_MAX))
+        k = int(k)
+        if M * k >_native.G4R_AUDIENCE_ENTRIES_MAX:
+            raise ValueError('%d items x k = %d is more than G4R_AUDIENCE_ENTRIES_MAX = 2^23 list entries' % (M, k))
+        if by == 'logprob':
+            _check_lse_candidates(self.n_items)
+        N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
+        iidx = self.itemidmap[ids].values.astype(np.int32)
+        m = self._ensure_model()
+        sessions, values, counts = m.audience_sessions(offs, hidx, iidx, k, by=by, temperature=float(t32), exclude_history=bool(exclude_history),
+                                                       hidden=h0)
+        return np.asarray(sessions).astype(np.int64), np.asarray(values, dtype=np.float32), np.asarray(counts, dtype=np.int32)
+
     def sample_sessions(self, histories, steps, samples=1, temperature=1.0, top_k=None, seed=0, first_step=0, no_repeat=True,
                         predict_for_item_ids=None, exclude=None, exclude_per_row=None, hidden=None, return_hidden=False, top_p=None,
                         return_logprobs=False):

@@ -331,6 +331,35 @@ int g4r_session_log_partition(g4r_model* m, const int64_t* hist_offs, const int3
                               const int32_t* item_idx, int64_t n_sel, const int64_t* excl_offs, const int32_t* excl_items,
                               const uint32_t* excl_mask, float temperature, float* out_zeta, uint64_t* out_Q);
 
+/* not in the reference: audience selection, the transposed question -- for each of n_items items (item indices, duplicates allowed,
+ * every position gets its own list) the k sessions with the largest value, stateless: the replay of g4r_recommend_sessions (hist_*, n,
+ * h0 and their refusals), any n.  The value of (session i, item):
+ *   by = G4R_AUDIENCE_SCORE     the item's score for the session, g4r_predict_step's bit pattern (what g4r_score_candidates_sessions
+ *                               stores for an element-wise final activation); refused for softmax / softmax_logit
+ *   by = G4R_AUDIENCE_LOGPROB   fl32((double)d - log((double)Q * 2^-39)), d = fl32(fl32(z - zeta) * invT): the log-probability
+ *                               softmax(z / temperature) over the session's eligible items gives the item, zeta and Q of the session as
+ *                               g4r_session_log_partition returns them over the whole catalogue (at most 2^24 items), z the item's
+ *                               score (the pre-activation value for softmax / softmax_logit); temperature is read in this mode only
+ * exclude_history != 0: a session whose history holds the item is not eligible for it and is never listed, and with
+ * G4R_AUDIENCE_LOGPROB the session's history items leave its normaliser (g4r_session_log_partition with the history as the exclusion
+ * list: at most G4R_EXCLUDE_MAX distinct items per history).
+ * Output, [n_items][k] row-major and out_counts[n_items]: row j holds the out_counts[j] <= k eligible sessions with the largest value
+ * for items[j], as indices into the histories, in g4r_recommend_step's order with the session in the column's place -- value
+ * descending, equal values (float ==) to the lower index, NaN below every number; entries at and after out_counts[j] hold session -1
+ * and value NaN.  The result depends on nothing else: not on the chunking (G4R_SESSIONS_CHUNK) nor on the other sessions of the call.
+ * Limits: 1 <= k <= G4R_AUDIENCE_MAX = 65536 (not bounded by G4R_TOPK_MAX, it may exceed n), 1 <= n_items <= G4R_AUDIENCE_ITEMS_MAX =
+ * 4096, n_items * k <= G4R_AUDIENCE_ENTRIES_MAX = 2^23 (the running lists, 16 bytes an entry and two sides, then take 256 MiB of
+ * device memory and the unpacked result 64 MiB).  The lists stay on the device while the sessions stream past, 512 a chunk: one
+ * stream synchronisation per chunk, no download before the last one.  Every check happens before any launch. */
+#define G4R_AUDIENCE_MAX 65536
+#define G4R_AUDIENCE_ITEMS_MAX 4096
+#define G4R_AUDIENCE_ENTRIES_MAX (1LL << 23)
+#define G4R_AUDIENCE_SCORE 0
+#define G4R_AUDIENCE_LOGPROB 1
+int g4r_audience_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                          const int32_t* items, int32_t n_items, int32_t k, int32_t by, float temperature, int32_t exclude_history,
+                          int32_t* out_sessions, float* out_values, int32_t* out_counts);
+
 /* not in the reference: item-to-item neighbours in the model's own embedding space -- the k candidates most similar to each of n
  * query items.  Stateless: the prediction state and the training state are neither read nor changed.
  *   table T     space = G4R_SPACE_OUTPUT: Wy, rows of layers[n_layers - 1] floats.  G4R_SPACE_INPUT: E when embed_mode is

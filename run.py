@@ -60,11 +60,19 @@ LOGLIK_OPTIONS = [
     (None, '--loglik_temperature', dict(metavar='T', type=float, default=1.0, help='temperature T of --loglik (default 1.0)')),
 ]
 
+# audience selection (not in the reference): which sessions for this item?
+AUDIENCE_OPTIONS = [
+    (None, '--save_audience', dict(metavar='PATH', help='with -t (not in the reference): for every item of --audience_items the --audience_k test sessions most likely to continue with it -- the histories are the test sessions\' full sequences -- written to PATH as .npz: item_ids, session_ids (-1 behind a row\'s count), values, counts (GRU4Rec.audience_sessions; several test sets: PATH gets the set\'s number in front of its extension)')),
+    (None, '--audience_items', dict(metavar='FILE', help='the items of --save_audience: a text file with one item id per line')),
+    (None, '--audience_k', dict(metavar='K', type=int, default=100, help='sessions per item of --save_audience (default 100)')),
+    (None, '--audience_by', dict(metavar='BY', choices=['score', 'logprob'], default='logprob', help='the value --save_audience ranks the sessions by: the item\'s score, or its log-probability under the session\'s next-item distribution (default logprob)')),
+]
+
 
 def build_parser():
     ap = argparse.ArgumentParser(description='Train a GRU4Rec model on an MI355X (or load one) and report Recall@N / MRR@N.')
     ap.add_argument('path', metavar='PATH', help='training data (.tsv / .txt with TAB separators, or a pickled DataFrame) -- or the model file when -l is given')
-    for short, long_, kw in OPTIONS + NEIGHBOR_OPTIONS + GROUP_OPTIONS + LOGLIK_OPTIONS:
+    for short, long_, kw in OPTIONS + NEIGHBOR_OPTIONS + GROUP_OPTIONS + LOGLIK_OPTIONS + AUDIENCE_OPTIONS:
         ap.add_argument(*([short, long_] if short else [long_]), **kw)
     return ap
 
@@ -197,6 +205,43 @@ def evaluate(model, opts):
             out = opts.save_recs if len(opts.test) == 1 else '{}.{}{}'.format(root, opts.test.index(fname), ext or '.npz')
             np.savez(out, **recs)
             print('Saved the recommendations of {} events to: {}'.format(len(recs['rank']), out))
+        if opts.save_audience:
+            save_audience(model, events, opts, fname)
+
+
+def save_audience(model, events, opts, fname):
+    """--save_audience: the test sessions' full sequences (events of items the model does not know are dropped, as in the evaluation) are
+    the histories of GRU4Rec.audience_sessions; the indices it returns are written as the sessions' ids."""
+    import numpy as np
+    if not hasattr(model, 'audience_sessions'):
+        print('ERROR. The model class {} does not support --save_audience'.format(type(model).__module__))
+        sys.exit(1)
+    if not opts.audience_items:
+        print('ERROR. --save_audience needs --audience_items FILE (one item id per line)')
+        sys.exit(1)
+    ids = dict(zip(model.itemidmap.index.astype(str), model.itemidmap.index))      # (a pickled table may hold ids that are not strings)
+    with open(opts.audience_items, 'rt') as fh:
+        wanted = [line.strip() for line in fh if line.strip()]
+    unknown = [w for w in wanted if w not in ids]
+    if unknown or not wanted:
+        print('ERROR. --audience_items: {}'.format('the file is empty' if not wanted else 'the model does not know item {}'.format(unknown[0])))
+        sys.exit(1)
+    table = events[[opts.session_key, opts.item_key, opts.time_key]].copy()
+    table[opts.item_key] = table[opts.item_key].astype(str)
+    table = table[table[opts.item_key].isin(ids)].sort_values([opts.session_key, opts.time_key], kind='stable')
+    sess = table[opts.session_key].values
+    cuts = np.flatnonzero(sess[1:] != sess[:-1]) + 1
+    items = np.array([ids[i] for i in table[opts.item_key]])
+    histories = np.split(items, cuts)
+    session_ids = sess[np.concatenate([[0], cuts]).astype(np.int64)]
+    started = time.time()
+    idx, values, counts = model.audience_sessions(histories, [ids[w] for w in wanted], opts.audience_k, by=opts.audience_by)
+    root, ext = os.path.splitext(opts.save_audience)
+    out = opts.save_audience if len(opts.test) == 1 else '{}.{}{}'.format(root, opts.test.index(fname), ext or '.npz')
+    np.savez(out, item_ids=np.array([ids[w] for w in wanted]), session_ids=np.where(idx >= 0, session_ids[np.maximum(idx, 0)], -1), values=values,
+             counts=counts)
+    print('Saved the audiences ({}, k = {}) of {} items among {} sessions to: {} ({:.2f}s)'.format(opts.audience_by, opts.audience_k, len(wanted),
+                                                                                               len(histories), out, time.time() - started))
 
 
 def save_neighbors(model, opts):
