@@ -70,7 +70,11 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            27: "the row normaliser of g4r_loglik_events takes a session item as seen only when its first occurrence is BEFORE the input "
                "event (s_first < position): the input event's own item, first shown there, stays in Q",
            28: "k_audience_keys (g4r_audience_sessions) files a session under its index WITHIN its chunk (c0 is not added): calls of one "
-               "chunk stay correct, from the second chunk on the lists name the wrong sessions"}
+               "chunk stay correct, from the second chunk on the lists name the wrong sessions",
+           29: "finish_rows (k_finish_rows, the row-finishing workgroups of k_dense_grad2) leaves out the sixteenth K-slice plane of layer "
+               "0's dy: sums of up to 15 planes stay correct",
+           30: "k_gru_p1s keys its embedding-dropout mask by the k offset INSIDE the K slice (the slice's start is dropped from the Philox "
+               "counter): from the second input slice on, the forward's mask is not the one finish_rows regenerates"}
 
 
 def mutant_path(k):

@@ -79,6 +79,16 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #else
 #define G4R_MUT_WIN_G(g0, s) ((g0) + (s))
 #endif
+#if defined(G4R_MUTATE) && G4R_MUTATE == 29      // test build: finish_rows leaves out the sixteenth K-slice plane of dy
+#define G4R_MUT_PLANES(nsl) min((nsl), 15)
+#else
+#define G4R_MUT_PLANES(nsl) (nsl)
+#endif
+#if defined(G4R_MUTATE) && G4R_MUTATE == 30      // test build: k_gru_p1s keys its embedding-dropout mask by the k offset INSIDE the slice
+#define G4R_MUT_DROP_K(ks) 0
+#else
+#define G4R_MUT_DROP_K(ks) (ks)
+#endif
 
 // Philox stream ids (counter word 3); twin of oracle/philox.py
 #define G4R_STREAM_SAMPLE 0x53414D50u

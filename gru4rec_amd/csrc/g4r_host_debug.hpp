@@ -109,6 +109,19 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
         }
         return 0;
     }
+    else if (s == "wide_geo") {      // the K-slice geometry of the wide-layer kernels (WideGeo), 7 ML floats: per layer (ML = G4R_MAX_LAYERS slots of
+        // seven, 0 past n_layers) use (bits 1 k_gru_p1s + k_gru_gate, 8 k_gru_bwd_bw), ny, nh, kys, khs (phase 1: input / hidden slices and
+        // their lengths), bbn, bbk (dy: slices and their length).  A layer off the wide path reports WideGeo's defaults (use 0)
+        const int ML = G4R_MAX_LAYERS;
+        if (count < 7 * ML) return fail("count");
+        for (int i = 0; i < 7 * ML; ++i) host[i] = 0.f;
+        for (int l = 0; l < d.n_layers; ++l) {
+            const WideGeo& G = k.wg[l];
+            const int v[7] = {G.use, G.ny, G.nh, G.kys, G.khs, G.bbn, G.bbk};
+            for (int i = 0; i < 7; ++i) host[7 * l + i] = (float)v[i];
+        }
+        return 0;
+    }
     else if (s == "generic") { if (count < 1) return fail("count"); host[0] = (float)d.generic; return 0; }      // 1: the generic optimizer path (raw gradients -> opt_rule: k_sparse_update_generic, dense_apply_elem)
     else if (s == "score_b_split") { if (count < 1) return fail("count"); host[0] = (float)k.score_a_host; return 0; }      // 1: k_score_b's role A runs in the top layer's k_gru_dy launch (graph / eager steps; per-kernel profiling keeps it in k_score_b)
     else if (s == "n_cu") { if (count < 1) return fail("count"); host[0] = (float)m->n_cu; return 0; }      // the CU count the choice was made for

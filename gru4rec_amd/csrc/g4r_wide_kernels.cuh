@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256, 4) void k_gru_p1s(const DevModel* __restrict__
         const unsigned s0 = (unsigned)m.seed, s1 = (unsigned)(m.seed >> 32);
         const int nch = Klen >> 4;
         for (int i = 0; i < nch; ++i) {
-            const Philox4 p = philox4x32_10((unsigned)((ks + 16 * i + sc) >> 2), (unsigned)(m0 + sr), g, G4R_STREAM_DROP_EMBED, s0, s1);
+            const Philox4 p = philox4x32_10((unsigned)((G4R_MUT_DROP_K(ks) + 16 * i + sc) >> 2), (unsigned)(m0 + sr), g, G4R_STREAM_DROP_EMBED, s0, s1);
             const unsigned bits = (u32_to_unit(p.x) < retain ? 1u : 0u) | (u32_to_unit(p.y) < retain ? 2u : 0u) |
                                   (u32_to_unit(p.z) < retain ? 4u : 0u) | (u32_to_unit(p.w) < retain ? 8u : 0u);
             dm |= bits << (4 * i);
@@ -211,7 +211,7 @@ __device__ __forceinline__ void finish_rows(const DevModel& m, const StepCtx& c,
     float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int q = 0; q < 16; ++q)
-        if (q < nsl) { g.x += v[q].x; g.y += v[q].y; g.z += v[q].z; g.w += v[q].w; }
+        if (q < G4R_MUT_PLANES(nsl)) { g.x += v[q].x; g.y += v[q].y; g.z += v[q].z; g.w += v[q].w; }
     if (m.drop_e > 0.f) {
         const float4 mk = drop_mult4(m.seed, (unsigned)c.g, G4R_STREAM_DROP_EMBED, row, c4 >> 2, 1.0f - m.drop_e);
         g.x *= mk.x; g.y *= mk.y; g.z *= mk.z; g.w *= mk.w;

@@ -22,6 +22,10 @@ mutant; every one of those runs has to come back red, and the tensor it names ha
             not zero) and the one-step cases of every activation pass
   mutant 23 hidden_act_bwd's negative-branch slope of leaky / elu / selu x 1.01 -> dV0 (da) and dWx0 of their one-step cases, lean and
             wide; the tanh and relu rows pass
+  mutant 29 finish_rows leaves out the sixteenth K-slice plane of layer 0's dy -> dWy / acc_Wy (the input rows' update) of the 16-slice case
+            of test_gpu_wide_edges.py; the 12-slice case passes
+  mutant 30 k_gru_p1s keys its embedding-dropout mask by the k offset inside the K slice -> the two-input-slice case (embedding 144) of
+            test_gpu_wide_edges.py; the one-slice case (embedding 80, slice start 0) passes
 
 (Round 2's `atol = 1e-4` on every tensor let an accumulator that is wrong by 100 x pass.)  The same selection runs green on the
 product library in the ordinary suite."""
@@ -207,6 +211,30 @@ def test_mutant_23_turns_the_negative_slope_red(mutants, tmp_path):
             else:
                 assert state['ha dV0 da'] and state['ha dWx0'], (f, a, state)
                 assert not state['ha r0'] and not state['ha z0'] and not state['ha c0'] and not state['ha dV0 dzp'], (f, a, state)
+
+
+WIDE = 'tests/test_gpu_wide_edges.py::'
+
+
+def test_mutant_29_turns_the_sixteenth_dy_plane_red(mutants, tmp_path):
+    """finish_rows adds up min(nsl, 15) planes: the case with 16 dy slices (D = 512, slices of 96) must fail on the input rows' update --
+    dWy and, through g^2, acc_Wy (the embedding is constrained: the input rows are rows of Wy) --; the case with 12 slices must pass."""
+    r, state = _child(mutants[29], WIDE + 'test_dy_16_slices', str(tmp_path / 'm29a.txt'))
+    assert r.returncode == 1, 'mutant 29 passed the 16-slice case:\n%s' % (r.stdout + r.stderr)[-3000:]
+    assert state['dy16 dWy'] and state['dy16 acc_Wy'], state
+    r, state = _child(mutants[29], WIDE + 'test_two_stage_slices', str(tmp_path / 'm29b.txt'))
+    assert r.returncode == 0, 'mutant 29 on 12 slices: rc %d\n%s' % (r.returncode, (r.stdout + r.stderr)[-3000:])
+
+
+def test_mutant_30_turns_the_second_input_slice_red(mutants, tmp_path):
+    """k_gru_p1s draws the embedding-dropout mask of input slice s from the k offset inside the slice: with two input slices (embedding 144:
+    80 + 64) the second slice is masked by the first one's bits, which is neither the oracle's mask nor the one finish_rows regenerates: the
+    case must fail; with one slice (embedding 80, slice start 0) nothing changes and the case must pass."""
+    r, state = _child(mutants[30], WIDE + 'test_input_width[144]', str(tmp_path / 'm30a.txt'))
+    assert r.returncode == 1, 'mutant 30 passed the two-slice case:\n%s' % (r.stdout + r.stderr)[-3000:]
+    assert state['loss curve'] and state['in144 dE'], state
+    r, state = _child(mutants[30], WIDE + 'test_input_width[80]', str(tmp_path / 'm30b.txt'))
+    assert r.returncode == 0, 'mutant 30 on one input slice: rc %d\n%s' % (r.returncode, (r.stdout + r.stderr)[-3000:])
 
 
 def test_product_library_is_not_a_mutant():
