@@ -26,6 +26,9 @@ G4R_CAND_MAX = 2 ** 31 - 256  # most candidate positions of one g4r_score_candid
 G4R_DIVERSIFY_POOL_MAX = 128  # largest pool of g4r_diversify_lists / g4r_diversify_sessions
 G4R_GROUP_PRIOR_MAX = 1024  # most prior groups of one row of g4r_continue_sessions_capped / g4r_cap_lists
 G4R_SCAN_CAND_MAX = 1024  # most candidates per row (k * oversample) of g4r_recommend_step_scan / g4r_recommend_sessions_scan
+G4R_IVF_LISTS_MAX = 65536   # most lists of an item index (g4r_ivf_set)
+G4R_IVF_NPROBE_MAX = 256    # most lists one row of g4r_recommend_sessions_ivf probes
+G4R_IVF_WS_MAX = 65536      # largest nprobe * candidates per row of that entry (its stage-1 lists: rows * nprobe * c * 8 bytes)
 LOSS_IDS = {'cross-entropy': 0, 'bpr-max': 1, 'top1-max': 2, 'bpr': 3, 'top1': 4, 'xe_logit': 5}
 ACT_IDS = {'linear': 0, 'relu': 1, 'tanh': 2, 'leaky': 3, 'elu': 4, 'selu': 5, 'softmax': 6, 'softmax_logit': 7}
 ADAPT_IDS = {'adagrad': 0, 'rmsprop': 1, 'adadelta': 2, 'adam': 3, None: 4}
@@ -58,7 +61,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_audience_sessions', 'g4r_scan_table_release', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_set_item_groups', 'g4r_get_item_groups', 'g4r_recommend_sessions_capped', 'g4r_continue_sessions_capped', 'g4r_cap_lists', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_loglik_events', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_audience_sessions', 'g4r_scan_table_release', 'g4r_ivf_assign', 'g4r_ivf_set', 'g4r_ivf_release', 'g4r_recommend_sessions_ivf', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_set_item_groups', 'g4r_get_item_groups', 'g4r_recommend_sessions_capped', 'g4r_continue_sessions_capped', 'g4r_cap_lists', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_loglik_events', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_debug_gumbel', 'g4r_debug_lse_terms', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -147,6 +150,10 @@ def lib():
     L.g4r_session_log_partition.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i64p, i32p, u32p, C.c_float, f32p, u64p]
     L.g4r_audience_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i32, i32, i32, C.c_float, i32, i32p, f32p, i32p]
     L.g4r_scan_table_release.argtypes = [vp]
+    L.g4r_ivf_assign.argtypes = [vp, f32p, i32, i32p]
+    L.g4r_ivf_set.argtypes = [vp, f32p, i32, i64p, i32p]
+    L.g4r_ivf_release.argtypes = [vp]
+    L.g4r_recommend_sessions_ivf.argtypes = [vp, i64p, i32p, i32, f32pp, i32, i32, i32, i64p, i32p, u32p, i32p, f32p, i32p, f32pp, i32p]
     L.g4r_similar_items.argtypes = [vp, i32, i32, i32p, i64, i32p, i64, i32, i32, u32p, i32p, f32p]
     L.g4r_diversify_lists.argtypes = [vp, i32, i32, i32p, f32p, i64, i32, i32, C.c_float, i32, i32p, f32p]
     L.g4r_diversify_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i64p, i32p, u32p, i32, i32, C.c_float, i32,
@@ -565,6 +572,49 @@ class Model:
         else:
             _chk(lib().g4r_recommend_sessions_scan(*head, int(oversample), *tail))
         return (cols, scores, hout) if return_hidden else (cols, scores)
+
+    # -- item index (IVF)
+    def ivf_assign(self, centroids):
+        """The list of every item for float32 centroids [n_lists, layers[-1] + 1] (g4r_ivf_assign): int32[n_items]."""
+        cen = np.ascontiguousarray(centroids, dtype=np.float32)
+        if cen.ndim != 2 or cen.shape[1] != self.layers[-1] + 1:
+            raise ValueError('centroids must be a [n_lists, %d] matrix' % (self.layers[-1] + 1))
+        out = np.empty(self.cfg.n_items, dtype=np.int32)
+        _chk(lib().g4r_ivf_assign(self.h, _f32(cen), cen.shape[0], _i32(out)))
+        return out
+
+    def ivf_set(self, centroids, list_offs, list_items):
+        """Installs an item index and builds its device tables (g4r_ivf_set)."""
+        cen = np.ascontiguousarray(centroids, dtype=np.float32)
+        offs = np.ascontiguousarray(list_offs, dtype=np.int64)
+        items = np.ascontiguousarray(list_items, dtype=np.int32)
+        if cen.ndim != 2 or cen.shape[1] != self.layers[-1] + 1 or len(offs) != cen.shape[0] + 1 or len(items) != self.cfg.n_items:
+            raise ValueError('an item index is centroids [n_lists, %d], list_offs [n_lists + 1] and list_items [n_items]' % (self.layers[-1] + 1))
+        _chk(lib().g4r_ivf_set(self.h, _f32(cen), cen.shape[0], _i64(offs), _i32(items)))
+
+    def ivf_release(self):
+        _chk(lib().g4r_ivf_release(self.h))
+
+    def ivf_info(self):
+        """State of the item index: (lists, blocks of 32 positions, bytes its device tables hold, valid, builds so far)."""
+        a = self.get_debug('ivf_index', 5)
+        return int(a[0]), int(a[1]), int(a[2]), bool(a[3]), int(a[4])
+
+    def recommend_sessions_ivf(self, hist_offs, hist_items, k=20, oversample=8, nprobe=1, excl_offs=None, excl_items=None, excl_mask=None,
+                               hidden=None, return_hidden=False, return_probes=False):
+        """recommend_sessions over the nprobe best lists of the item index (g4r_recommend_sessions_ivf): (items int32[n, k], scores
+        float32[n, k], found int32[n]), + the hidden states with return_hidden=True, + the probed lists int32[n, nprobe] with
+        return_probes=True.  Entries at and after found[i] hold item 0 and score NaN."""
+        offs, hi, n = _hist(hist_offs, hist_items)
+        xo, xi, mask = _excl(n, excl_offs, excl_items, excl_mask, self.cfg.n_items, 'n')
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        hout, houtp = _hidden_out(n, self.layers, return_hidden)
+        cols, scores = _topk_out((n, k))
+        found = np.empty(n, dtype=np.int32)
+        probes = np.empty((n, max(int(nprobe), 1)), dtype=np.int32) if return_probes else None
+        _chk(lib().g4r_recommend_sessions_ivf(self.h, _i64(offs), _i32(hi), n, h0p, k, int(oversample), int(nprobe), _i64(xo), _i32(xi), _u32(mask),
+                                              _i32(cols), _f32(scores), _i32(found), houtp, _i32(probes)))
+        return (cols, scores, found) + ((hout,) if return_hidden else ()) + ((probes,) if return_probes else ())
 
     def continue_sessions(self, hist_offs, hist_items, item_idx=None, k=1, steps=1, no_repeat=True, excl_offs=None, excl_items=None,
                           excl_mask=None, hidden=None, return_hidden=False, oversample=None):

@@ -74,7 +74,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            29: "finish_rows (k_finish_rows, the row-finishing workgroups of k_dense_grad2) leaves out the sixteenth K-slice plane of layer "
                "0's dy: sums of up to 15 planes stay correct",
            30: "k_gru_p1s keys its embedding-dropout mask by the k offset INSIDE the K slice (the slice's start is dropped from the Philox "
-               "counter): from the second input slice on, the forward's mask is not the one finish_rows regenerates"}
+               "counter): from the second input slice on, the forward's mask is not the one finish_rows regenerates",
+           31: "k_ivf_scan (g4r_recommend_sessions_ivf) does not scan the last block of a list whose length is not a multiple of 32: "
+               "the items of that block never become candidates"}
 
 
 def mutant_path(k):

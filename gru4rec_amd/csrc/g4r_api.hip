@@ -21,6 +21,7 @@
 #include "g4r_sample_kernels.cuh"
 #include "g4r_audience_kernels.cuh"
 #include "g4r_scan_kernels.cuh"
+#include "g4r_ivf_kernels.cuh"
 #include "g4r_sim_kernels.cuh"
 #include "g4r_mmr_kernels.cuh"
 #include "g4r_group_kernels.cuh"
@@ -40,6 +41,7 @@ extern "C" {
 #include "g4r_host_topk.hpp"
 #include "g4r_host_predict.hpp"
 #include "g4r_host_sessions.hpp"
+#include "g4r_host_ivf.hpp"
 #include "g4r_host_beam.hpp"
 #include "g4r_host_sample.hpp"
 #include "g4r_host_audience.hpp"

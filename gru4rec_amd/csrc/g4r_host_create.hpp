@@ -324,12 +324,14 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
         (const void*)k_score_bwd_n, (const void*)k_gru_bwd_fused, (const void*)k_gru_fwd_fused, (const void*)k_score_bwd_w, (const void*)k_score_bwd2,
         (const void*)k_gru_bwd_a_w4, (const void*)k_gru_bwd_a_w8d, (const void*)k_gru_bwd_b, (const void*)k_dense_grad<32>,
         (const void*)k_score_store, (const void*)k_score_count, (const void*)k_sim_range<false>, (const void*)k_sim_range<true>,
-        (const void*)k_mmr_rerank<false>, (const void*)k_mmr_rerank<true>,
+        (const void*)k_mmr_rerank<false>, (const void*)k_mmr_rerank<true>, (const void*)k_ivf_assign,
 #define TK_PTR(name, ...) (const void*)name,
 #define SCAN_PTR(NCH, E) (const void*)k_scan_bf16<NCH, E>,
-        TK_FORMS(TK_PTR) SCAN_FORMS(SCAN_PTR)      // every form of the two range kernels: the lists themselves
+#define IVF_PTR(NCH) (const void*)k_ivf_scan<NCH>,
+        TK_FORMS(TK_PTR) SCAN_FORMS(SCAN_PTR) IVF_FORMS(IVF_PTR)      // every form of the range kernels: the lists themselves
 #undef TK_PTR
 #undef SCAN_PTR
+#undef IVF_PTR
     };
     auto opt_in = [&](const void* kern) { return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, big); };
     for (const void* kern : lds_kernels) HIPCHK(opt_in(kern));

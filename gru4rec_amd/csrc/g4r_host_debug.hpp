@@ -34,6 +34,14 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
         host[0] = (float)((double)m->s_tab.cap * 16.0); host[1] = m->s_tab_valid ? 1.f : 0.f; host[2] = (float)m->s_tab_builds;
         return 0;
     }
+    else if (s == "ivf_index") {      // the item index: (lists, blocks of 32 positions, bytes its device tables hold, 1 if they are valid, builds so far); all 0 without one
+        if (count < 5) return fail("count");
+        const IvfIndex& iv = m->iv;
+        host[0] = (float)iv.nl; host[1] = (float)iv.nblk;
+        host[2] = (float)((double)iv.tab.cap * 16.0 + (double)(iv.pos_by.cap + iv.pos_item.cap + iv.blk.cap + iv.doffs.cap + iv.cwt.cap + iv.cb.cap) * 4.0);
+        host[3] = iv.valid ? 1.f : 0.f; host[4] = (float)iv.builds;
+        return 0;
+    }
     else if (s == "sim_norms") {      // (bytes the inverse norms of g4r_similar_items hold, 1 if a table's are valid, builds so far)
         if (count < 3) return fail("count");
         host[0] = (float)(((m->sim_inv[0] ? 1.0 : 0.0) + (m->sim_inv[1] ? 1.0 : 0.0)) * (double)d.n_items * 4.0);

@@ -86,6 +86,27 @@ struct DevBuf {
     int reserve(g4r_model* m, int64_t n);
 };
 
+// The item index of g4r_recommend_sessions_ivf (g4r_host_ivf.hpp).  Host: what g4r_ivf_set was given -- centroids [nl][Dtop + 1], the
+// lists' offsets and their items (ascending within a list).  Device, owned by the index, grow only, rebuilt from the host copy and the
+// current Wy / By after weights_changed: the bf16 table in list order (every list padded to whole blocks of 32 positions), By and the
+// item of every position, the lists' block ranges and lengths, the centroids (weights transposed [Dtop][nl], biases).  Per chunk: a
+// row's centroid entries, its probes and their scores, the (list, row) bitmap, the lists' first triples, the work items, the sorted
+// triples and the number of work items.
+struct IvfIndex {
+    bool set = false, valid = false;
+    int nl = 0;
+    int64_t nblk = 0, builds = 0;
+    std::vector<float> cen;
+    std::vector<int64_t> offs;
+    std::vector<int32_t> items;
+    DevBuf<uint4> tab;
+    DevBuf<float> pos_by, cwt, cb, pscores;
+    DevBuf<int> pos_item, blk, doffs, probes, toff, trip, n_work;
+    DevBuf<uint2> ent;
+    DevBuf<unsigned> member;
+    DevBuf<int4> work;
+};
+
 struct g4r_model {
     g4r_config cfg;
     DevModel dm;                 // host master copy of the device-resident model descriptor
@@ -209,6 +230,7 @@ struct g4r_model {
     DevBuf<int> s_cols;
     DevBuf<int> s_cnt;
     std::vector<int4> s_work;
+    IvfIndex iv;                                 // the item index (g4r_ivf_set / g4r_recommend_sessions_ivf)
     // item neighbours (g4r_similar_items): the inverse row norms of the item tables (0: Wy, 1: E), built on the first cosine call and
     // again after anything that may have changed the tables (weights_changed); the query items of one chunk and their rows
     float* sim_inv[2] = {nullptr, nullptr};
@@ -290,9 +312,9 @@ struct CapStage {
     int32_t* out_pos; int32_t* out_kept;                         // host: [n][k] (NULL: not wanted), [n][max(steps, 1)]
 };
 
-// every entry that may rewrite Wy / E calls this: the bf16 shadow table of the two-stage top-k and the inverse norms of
-// g4r_similar_items are rebuilt on their next use
-static inline void weights_changed(g4r_model* m) { m->s_tab_valid = false; m->sim_valid[0] = m->sim_valid[1] = false; }
+// every entry that may rewrite Wy / E calls this: the bf16 shadow table of the two-stage top-k, the inverse norms of
+// g4r_similar_items and the device tables of the item index are rebuilt on their next use
+static inline void weights_changed(g4r_model* m) { m->s_tab_valid = false; m->sim_valid[0] = m->sim_valid[1] = false; m->iv.valid = false; }
 // the captured step graphs, stale with what they captured (the kernel choice, the collective); the next step that wants one captures
 // it again.  also_head: the head graph (one step's kernels up to the dense gradients) too
 static inline void drop_step_graphs(g4r_model* m, bool also_head) {

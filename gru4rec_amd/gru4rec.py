@@ -572,6 +572,7 @@ class GRU4Rec:
                                       'order on NumPy\'s global random stream; only the device store (store_type="gpu") resumes')
         self.predict = None
         self.error_during_train = False
+        self.drop_item_index()      # the item map may change
         item_col = data[self.item_key]
         if eventio.is_categorical(item_col):
             # table from eventio.read_events: the category codes already are the indices (no hash join over the events)
@@ -775,6 +776,7 @@ class GRU4Rec:
         if self._model is not None:
             self._model.close()
             self._model = None
+        self._item_index_on = None      # (the index itself stays on this object: the next device model receives it again)
         self.predict = None
 
     # ------------------------------------------------------------------ prediction (gru4rec.py:665-728)
@@ -1047,6 +1049,185 @@ class GRU4Rec:
             cols, scores = m.recommend_step(in_idxs, iidx, k)      # (the unfiltered exact selection is an entry of its own)
         return cand[cols], scores
 
+    # ------------------------------------------------------------------ item index (IVF) of recommend_sessions(nprobe=)
+    @staticmethod
+    def _index_n_lists(n_lists, n_items):
+        """The checked number of lists of an item index over n_items items; None: round(4 * sqrt(n_items))."""
+        if n_lists is None:
+            n_lists = min(max(int(round(4.0 * np.sqrt(n_items))), 1), n_items, _native.G4R_IVF_LISTS_MAX)
+        if isinstance(n_lists, bool) or int(n_lists) != n_lists or not 1 <= n_lists <= min(_native.G4R_IVF_LISTS_MAX, n_items):
+            raise ValueError('n_lists = %r: it must be an integer in [1, min(%d, n_items = %d)]' % (n_lists, _native.G4R_IVF_LISTS_MAX, n_items))
+        return int(n_lists)
+
+    def _index_checked(self, index):
+        """index= of build_item_index (a dict as item_index() returns it), validated: (centroids float32[n_lists, D + 1], list_offs
+        int64[n_lists + 1], list_items as item INDICES int32, every list ascending)."""
+        n_items, W = len(self.itemidmap), self.layers[-1] + 1
+        if not isinstance(index, dict) or not all(key in index for key in ('centroids', 'list_offs', 'list_items')):
+            raise ValueError("index must be a dict with 'centroids', 'list_offs' and 'list_items', as item_index() returns it")
+        cen = np.asarray(index['centroids'])
+        if cen.ndim != 2 or cen.shape[1] != W or cen.dtype != np.float32:
+            raise ValueError('index: centroids must be a float32 array [n_lists, %d], not %s %s' % (W, cen.dtype, cen.shape))
+        n_lists = self._index_n_lists(cen.shape[0], n_items)
+        if not np.isfinite(cen).all():
+            raise ValueError('index: centroids must be finite')
+        offs = np.asarray(index['list_offs'])
+        if offs.ndim != 1 or len(offs) != n_lists + 1 or not np.issubdtype(offs.dtype, np.integer):
+            raise ValueError('index: list_offs must hold n_lists + 1 = %d integers' % (n_lists + 1))
+        offs = offs.astype(np.int64)
+        if offs[0] != 0 or offs[-1] != n_items or (np.diff(offs) < 0).any():
+            raise ValueError('index: list_offs must rise monotonically from 0 to n_items = %d' % n_items)
+        ids = np.ravel(index['list_items'])
+        if len(ids) != n_items:
+            raise ValueError('index: list_items must be a permutation of all %d items, it holds %d' % (n_items, len(ids)))
+        idx = self.itemidmap[ids].values.astype(np.int64)
+        if (np.bincount(idx, minlength=n_items) != 1).any():
+            raise ValueError('index: list_items must be a permutation of all %d items (an item is listed twice)' % n_items)
+        lst = np.repeat(np.arange(n_lists), np.diff(offs))
+        idx = idx[np.lexsort((idx, lst))]      # every list in ascending item index: the order within a list carries nothing
+        return np.ascontiguousarray(cen), offs, idx.astype(np.int32)
+
+    def _kmeans(self, n_lists, iters, sample_per_list, seed):
+        """Plain Lloyd k-means on the host over a deterministic sample of at most sample_per_list * n_lists item vectors [Wy[i], By[i]]
+        (float32); assignment maximises v.c - |c|^2 / 2, equal objectives to the lower list; empty clusters keep their centroid."""
+        n = len(self.itemidmap)
+        rng = np.random.RandomState(seed)
+        S = min(n, int(sample_per_list) * n_lists)
+        rows = np.sort(rng.choice(n, S, replace=False)) if S < n else np.arange(n)
+        X = np.concatenate([np.asarray(self.Wy, dtype=np.float32)[rows], np.asarray(self.By, dtype=np.float32).reshape(-1, 1)[rows]], axis=1)
+        cen = X[np.sort(rng.choice(S, n_lists, replace=False))].copy()
+        for _ in range(int(iters)):
+            half = 0.5 * (cen.astype(np.float64) ** 2).sum(axis=1).astype(np.float32)
+            a = np.empty(S, dtype=np.int64)
+            for r0 in range(0, S, 16384):
+                a[r0:r0 + 16384] = np.argmax(X[r0:r0 + 16384] @ cen.T - half, axis=1)
+            cnt = np.bincount(a, minlength=n_lists)
+            sums = np.stack([np.bincount(a, weights=X[:, j], minlength=n_lists) for j in range(X.shape[1])], axis=1)
+            full = cnt > 0
+            cen[full] = (sums[full] / cnt[full, None]).astype(np.float32)
+        return cen
+
+    def build_item_index(self, n_lists=None, iters=10, sample_per_list=64, seed=0, centroids=None, index=None):
+        """Builds the item index (an inverted file over the item table) that recommend_sessions(nprobe=) probes.  Not in the reference.
+        It needs a fitted or loaded model.  Item i is indexed by v_i = [Wy[i], By[i]] (dimension D + 1): its inner product with [h, 1]
+        is the item's logit.  The items are clustered into n_lists lists (None: round(4 * sqrt(n_items)); an integer in [1, 65536], at
+        most n_items) by plain Lloyd k-means on the host -- `iters` rounds over a deterministic sample (`seed`) of at most
+        sample_per_list * n_lists items, assignment by the largest v.c - |c|^2 / 2, empty clusters keep their centroid -- and every
+        item is then assigned to its best list on the device (equal objectives to the lower list).  A list holds its items in
+        ascending item index.
+
+          centroids   a float32 array [n_lists, D + 1]: k-means is skipped, only the device assignment runs.
+          index       a dict as item_index() returns it: both are skipped.  It is validated (ValueError): list_items must be a
+                      permutation of all items, list_offs must hold n_lists + 1 monotone offsets from 0 to n_items, centroids must
+                      have the right shape and be finite.  The order of the items within a list carries nothing.
+
+        Returns the statistics of the build: n_lists, list_len_min / list_len_mean / list_len_max, empty_lists, and the seconds spent
+        on k-means, on the assignment and on the upload (seconds_kmeans, seconds_assign, seconds_upload).  A work item of the scan
+        walks a whole list, so list_len_max against list_len_mean is the skew a probe of the longest list pays for.
+
+        The index lives until fit / prepare (the item map may change), drop_item_index or the end of this object; savemodel does not
+        pickle it: keep item_index() and pass it back as index= after loadmodel.  When Wy / By change on the device afterwards
+        (further training steps), the index's device tables are rebuilt from the current weights on the next call while the centroids
+        and the partition stay as they were built.  That costs recall, never correctness: every returned score stays exact."""
+        import time
+        if getattr(self, 'error_during_train', False):
+            raise Exception
+        if getattr(self, 'itemidmap', None) is None or getattr(self, 'Wy', None) is None:
+            raise ValueError('build_item_index needs a fitted or loaded model')
+        n_items, W = len(self.itemidmap), self.layers[-1] + 1
+        t = dict(seconds_kmeans=0.0, seconds_assign=0.0, seconds_upload=0.0)
+        if index is not None:
+            cen, offs, items = self._index_checked(index)
+            m = self._ensure_model()
+        else:
+            if centroids is not None:
+                cen = np.asarray(centroids)
+                if cen.ndim != 2 or cen.shape[1] != W or cen.dtype != np.float32 or not np.isfinite(cen).all():
+                    raise ValueError('centroids must be a finite float32 array [n_lists, %d]' % W)
+                self._index_n_lists(cen.shape[0], n_items)
+                cen = np.ascontiguousarray(cen)
+                m = self._ensure_model()
+            else:
+                n_lists = self._index_n_lists(n_lists, n_items)
+                if isinstance(iters, bool) or int(iters) != iters or iters < 0:
+                    raise ValueError('iters = %r: it must be an integer >= 0' % (iters,))
+                if isinstance(sample_per_list, bool) or int(sample_per_list) != sample_per_list or sample_per_list < 1:
+                    raise ValueError('sample_per_list = %r: it must be an integer >= 1' % (sample_per_list,))
+                m = self._ensure_model()
+                t0 = time.perf_counter()
+                cen = self._kmeans(n_lists, iters, sample_per_list, seed)
+                t['seconds_kmeans'] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            lst = m.ivf_assign(cen)
+            items = np.argsort(lst, kind='stable').astype(np.int32)      # stable: every list in ascending item index
+            offs = np.concatenate([[0], np.cumsum(np.bincount(lst, minlength=len(cen)))]).astype(np.int64)
+            t['seconds_assign'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        m.ivf_set(cen, offs, items)
+        t['seconds_upload'] = time.perf_counter() - t0
+        self._item_index = dict(centroids=cen, list_offs=offs, list_items=items)
+        self._item_index_on = m
+        lens = np.diff(offs)
+        return dict(n_lists=len(cen), list_len_min=int(lens.min()), list_len_mean=float(lens.mean()), list_len_max=int(lens.max()),
+                    empty_lists=int((lens == 0).sum()), **t)
+
+    def item_index(self):
+        """The item index as dict(centroids float32[n_lists, D + 1], list_offs int64[n_lists + 1], list_items: item ids in list
+        order), or None without one.  Passed back as build_item_index(index=...) it re-creates the index without training it again."""
+        ix = getattr(self, '_item_index', None)
+        if ix is None:
+            return None
+        return dict(centroids=ix['centroids'].copy(), list_offs=ix['list_offs'].copy(),
+                    list_items=self.itemidmap.index.values[ix['list_items']])
+
+    def drop_item_index(self):
+        """Frees the host and device copies of the item index; recommend_sessions(nprobe=) then raises until one is built again."""
+        m = getattr(self, '_item_index_on', None)
+        if m is not None and m is getattr(self, '_model', None) and getattr(m, 'h', None):
+            m.ivf_release()
+        self._item_index = None
+        self._item_index_on = None
+
+    def _index_model(self):
+        """The device model, holding the item index (a model created since the index was built receives it here)."""
+        m = self._ensure_model()
+        if getattr(self, '_item_index_on', None) is not m:
+            ix = self._item_index
+            m.ivf_set(ix['centroids'], ix['list_offs'], ix['list_items'])
+            self._item_index_on = m
+        return m
+
+    def _check_nprobe(self, nprobe, return_probes, k, oversample, scan, predict_for_item_ids, max_per_group):
+        """The refusals of recommend_sessions(nprobe=), after the k check and before any device work: (nprobe, oversample) checked."""
+        if nprobe is None:
+            if return_probes:
+                raise ValueError('return_probes=True needs nprobe: without it no list is probed')
+            return None
+        ix = getattr(self, '_item_index', None)
+        if ix is None:
+            raise ValueError('nprobe needs an item index: call build_item_index first')
+        n_lists = len(ix['list_offs']) - 1
+        if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or not 1 <= nprobe <= n_lists:
+            raise ValueError('nprobe = %r: it must be an integer in [1, n_lists = %d]' % (nprobe, n_lists))
+        if nprobe > _native.G4R_IVF_NPROBE_MAX:
+            raise ValueError('nprobe = %d: a row probes at most G4R_IVF_NPROBE_MAX = %d lists' % (nprobe, _native.G4R_IVF_NPROBE_MAX))
+        if scan != 'fp32':
+            self._scan_oversample(scan, oversample, k)      # (an unknown name is refused as ever)
+            raise ValueError("nprobe and scan='bf16' exclude each other: the index is a first stage of its own (its scan is the bf16 one)")
+        if predict_for_item_ids is not None:
+            raise ValueError('nprobe and predict_for_item_ids exclude each other: the index holds all items')
+        if max_per_group is not None:
+            raise ValueError('nprobe and max_per_group exclude each other')
+        self._scan_oversample('fp32', oversample, k)
+        if self.final_act.startswith('softmax'):
+            raise NotImplementedError("nprobe is not implemented for final_act=%r, as scan='bf16' is not: a softmax value needs the whole "
+                                      "row's maximum and sum" % self.final_act)
+        c = min(int(k) * int(oversample), _native.G4R_SCAN_CAND_MAX)
+        if int(nprobe) * c > _native.G4R_IVF_WS_MAX:
+            raise ValueError('nprobe * min(k * oversample, %d) = %d * %d: it must be at most G4R_IVF_WS_MAX = %d (the first stage keeps that '
+                             'many entries per row)' % (_native.G4R_SCAN_CAND_MAX, nprobe, c, _native.G4R_IVF_WS_MAX))
+        return int(nprobe), int(oversample)
+
     def _session_inputs(self, histories, hidden):
         """Checks and packs the histories and the initial hidden state of a stateless call (recommend_sessions,
         score_candidates_sessions): (N, lengths, offsets int64[N + 1], item indices int32, per-layer padded states or None)."""
@@ -1072,9 +1253,25 @@ class GRU4Rec:
         return N, lens, offs, hidx, h0
 
     def recommend_sessions(self, histories, k=20, predict_for_item_ids=None, exclude_history=False, exclude=None, exclude_per_row=None,
-                           hidden=None, return_hidden=False, scan='fp32', oversample=8, max_per_group=None, pool=None, exclude_groups=None):
+                           hidden=None, return_hidden=False, scan='fp32', oversample=8, max_per_group=None, pool=None, exclude_groups=None,
+                           nprobe=None, return_probes=False):
         """Top-k next items of N whole sessions in one stateless call: (item_ids[N, k], scores[N, k] float32), plus the new hidden
         state with return_hidden=True.  Not in the reference.
+
+          nprobe           None: nothing changes.  An integer in [1, n_lists] (at most 256; it needs build_item_index): approximate
+                           top-k over the item index.  Row i probes the nprobe lists whose centroids score best against its final
+                           hidden state (equal values to the lower list) and only their items are considered: a bf16 scan (as
+                           scan='bf16', exclusions applied) keeps c = min(k * oversample, 1024) of them, those are scored again in fp32
+                           and the k best returned.  Every returned score is predict_next_batch's bit for bit, the order and the tie
+                           rule (the lower item first) are the exact call's; only WHICH items are considered is approximate.  The call
+                           returns (item_ids[N, k], scores[N, k], n_found[N] int32), then the hidden state with return_hidden=True,
+                           then with return_probes=True an int32 array [N, nprobe] of list numbers, best first.  n_found[i] < k only
+                           when row i's probed lists hold fewer than k eligible items; entries at and after it have score NaN and
+                           an unspecified id.  A row's result does not depend on the other rows of the call; with nprobe = n_lists it
+                           is scan='bf16''s with the same oversample; when c covers the eligible items of the probed lists it is the
+                           exact top-k over them.  Refused (ValueError) together with scan='bf16', predict_for_item_ids or
+                           max_per_group, without an index, out of range, or with nprobe * c over G4R_IVF_WS_MAX = 65536; softmax /
+                           softmax_logit raise NotImplementedError.  The exclusions, hidden and return_hidden work as without it.
 
           histories        N >= 1 non-empty sequences of item ids; row i belongs to histories[i].  Any N, independent of batch_size.
           hidden           None: every session starts from zero (a new session).  Otherwise a list with one float32 array
@@ -1109,6 +1306,16 @@ class GRU4Rec:
         if self.error_during_train:
             raise Exception
         k = _check_k(k, self._n_candidates(predict_for_item_ids), bools=True)
+        probe = self._check_nprobe(nprobe, return_probes, k, oversample, scan, predict_for_item_ids, max_per_group)
+        if probe is not None:
+            N, lens, offs, hidx, h0 = self._session_inputs(histories, hidden)
+            excl = self._session_exclusions(N, lens, hidx, k, None, exclude_history, exclude, exclude_per_row, exclude_groups=exclude_groups)
+            out = self._index_model().recommend_sessions_ivf(offs, hidx, k, probe[1], probe[0], *excl, hidden=h0, return_hidden=return_hidden,
+                                                             return_probes=return_probes)
+            res = (self.itemidmap.index.values[out[0]], out[1], out[2])
+            if return_hidden:
+                res += (self._unpad_hidden(out[3]),)
+            return res + (out[-1],) if return_probes else res
         cap, pool = self._cap_args(max_per_group, pool, k, self._n_candidates(predict_for_item_ids))
         ksel = k if cap is None else pool      # what the selection returns per row
         over = self._scan_oversample(scan, oversample, ksel)
@@ -1878,7 +2085,7 @@ class GRU4Rec:
 
     def __getstate__(self):
         st = dict(self.__dict__)
-        for k in ('_model', '_plan', '_plan_key', '_data_items', '_offsets', '_base_order', '_dist', '_loss_id', '_final', '_hidden', '_pop64', '_cpu_store', '_seen', '_seen_n', '_seen_over'):
+        for k in ('_model', '_plan', '_plan_key', '_data_items', '_offsets', '_base_order', '_dist', '_loss_id', '_final', '_hidden', '_pop64', '_cpu_store', '_seen', '_seen_n', '_seen_over', '_item_index', '_item_index_on'):
             st.pop(k, None)
         st['predict'] = None
         return st

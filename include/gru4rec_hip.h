@@ -230,6 +230,44 @@ int g4r_recommend_sessions_scan(g4r_model* m, const int64_t* hist_offs, const in
                                 float* const* out_hidden);
 int g4r_scan_table_release(g4r_model* m);
 
+/* not in the reference: approximate top-k over an item index (IVF).  The items are partitioned into n_lists lists, each with a
+ * centroid of dimension Dtop + 1; item i is indexed by v_i = [Wy[i], By[i]], whose inner product with [h, 1] is the item's logit.
+ *   g4r_ivf_assign   out_list[i] = the list of item i for the given centroids [n_lists][Dtop + 1] (finite): the list that maximises
+ *                    v_i . c - |c|^2 / 2 in fp32, equal objectives to the lower list.  Computed on the device from the current Wy / By.
+ *   g4r_ivf_set      installs an index: the centroids, list_offs[n_lists + 1] (from 0 to n_items, monotone) and list_items[n_items], a
+ *                    permutation of all items that holds every list in ascending item index.  Everything is checked; the device
+ *                    tables are built before it returns: a bf16 copy of Wy in list order (every list padded to whole blocks of 32
+ *                    positions; n_items x the padded top layer x 2 bytes, plus the pads) -- the shadow table of the bf16 scan is not
+ *                    needed and not built by this path.  They are rebuilt from the current weights on the first call after anything
+ *                    that may have changed Wy (the entries listed above); the centroids and the partition stay as set, which costs
+ *                    recall, never correctness.
+ *   g4r_ivf_release  frees the host and device copies; g4r_destroy does too.  g4r_get_debug "ivf_index" -> (lists, blocks of 32
+ *                    positions, bytes the device tables hold, 1 if they are valid, builds so far).
+ * g4r_recommend_sessions_ivf takes the histories, h0, k, the exclusions and out_hidden of g4r_recommend_sessions_scan (all items
+ * are the candidates), oversample >= 1 and nprobe in [1, min(n_lists, G4R_IVF_NPROBE_MAX)].  A row's result:
+ *   probes      the nprobe lists with the largest fl32(h . c_w + c_b), equal values to the lower list; a function of the row's final
+ *               hidden state only.  out_probes[n * nprobe] (NULL: not wanted) receives them, best first.
+ *   candidates  over the eligible items of the probed lists, the c = min(k * oversample, G4R_SCAN_CAND_MAX) best approximate scores
+ *               (the bf16 scan's, bit for bit) in the order (score descending, lower ITEM INDEX first, NaN last); exclusions apply here.
+ *   result      the candidates scored as g4r_predict_step scores them and the k best by (exact score, lower item index first)
+ *               returned as item indices.  out_found[i] = min(k, the candidates of row i): a row is short only when its probed
+ *               lists hold fewer than k eligible items; the entries at and after out_found[i] hold item 0 and score NaN.
+ * So a row's result does not depend on the rows it is called with or on the chunking, with nprobe = n_lists it is
+ * g4r_recommend_sessions_scan's with the same oversample, and when c covers the eligible items of the probed lists it is the exact
+ * top-k over their union.  The stage-1 lists take rows * nprobe * c * 8 bytes per chunk: nprobe * c <= G4R_IVF_WS_MAX.  Refused
+ * before any launch: no index, softmax / softmax_logit, a top layer wider than 512, k, oversample, nprobe or nprobe * c out of range,
+ * and what g4r_recommend_sessions refuses.  The prediction state is neither read nor changed. */
+#define G4R_IVF_LISTS_MAX 65536
+#define G4R_IVF_NPROBE_MAX 256
+#define G4R_IVF_WS_MAX 65536
+int g4r_ivf_assign(g4r_model* m, const float* centroids, int32_t n_lists, int32_t* out_list);
+int g4r_ivf_set(g4r_model* m, const float* centroids, int32_t n_lists, const int64_t* list_offs, const int32_t* list_items);
+int g4r_ivf_release(g4r_model* m);
+int g4r_recommend_sessions_ivf(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, const float* const* h0,
+                               int32_t k, int32_t oversample, int32_t nprobe, const int64_t* excl_offs, const int32_t* excl_items,
+                               const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, int32_t* out_found,
+                               float* const* out_hidden, int32_t* out_probes);
+
 /* not in the reference: multi-step continuation of n whole sessions, stateless.  The arguments of g4r_recommend_sessions_scan
  * (oversample = 0: the exact selection of g4r_recommend_sessions) plus steps >= 1 and no_repeat; out_cols / out_scores hold
  * n * steps * k entries, [session][step][rank].  Step 0 is g4r_recommend_sessions(_scan) of the histories.  For s >= 1 the item of
