@@ -76,7 +76,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            30: "k_gru_p1s keys its embedding-dropout mask by the k offset INSIDE the K slice (the slice's start is dropped from the Philox "
                "counter): from the second input slice on, the forward's mask is not the one finish_rows regenerates",
            31: "k_ivf_scan (g4r_recommend_sessions_ivf) does not scan the last block of a list whose length is not a multiple of 32: "
-               "the items of that block never become candidates"}
+               "the items of that block never become candidates",
+           32: "k_owner_window's per-position entries count a repeated item whose occurrences are all sampled negatives one too low: "
+               "its owner adds one step row too few"}
 
 
 def mutant_path(k):

@@ -13,7 +13,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define G4R_OWN_INLINE 15      /* earlier occurrences an owner-table row holds (DevModel::own_pos) */
 #define G4R_OWN_SLOTS 16       /* owner tables in the ring: the steps of a window (= G4R_GRAPH_STEPS, k_owner_window) */
 #define G4R_OWN_WINDOW_MAXR 12288      /* longest occurrence list k_owner_window stages in its LDS (48 KB of ids) */
-#define G4R_OWN_WINDOW_MINWG 4         /* pre-scan workgroups of k_loss_rows (16 occurrences each) up to which the pre-scan stays: a window launch would cost more */
+#define G4R_POS_ENT_MAXHS 8192          /* most hash slots (16 bytes each) of k_owner_window's per-position entries: the ids, the waves' position rows and the hash share 156 KB of LDS */
+#define G4R_OWN_WINDOW_MINWG 4        /* pre-scan workgroups of k_loss_rows (16 occurrences each) up to which the pre-scan stays: a window launch would cost more */
 
 // Mutation builds for the parity suite's self-test (tests/test_gpu_mutation.py builds them as variant libraries next to the product
 // one and expects the parity tests to turn red): G4R_MUTATE=1 inflates every per-occurrence sparse accumulator increment by
@@ -78,6 +79,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define G4R_MUT_WIN_G(g0, s) (g0)
 #else
 #define G4R_MUT_WIN_G(g0, s) ((g0) + (s))
+#endif
+#if defined(G4R_MUTATE) && G4R_MUTATE == 32      // test build: k_owner_window's per-position entries count a repeated item whose occurrences
+// are all sampled negatives one too low
+#define G4R_MUT_ENT_CNT(cnt, allsmp) (((allsmp) && (cnt) > 1) ? (cnt) - 1 : (cnt))
+#else
+#define G4R_MUT_ENT_CNT(cnt, allsmp) (cnt)
 #endif
 #if defined(G4R_MUTATE) && G4R_MUTATE == 29      // test build: finish_rows leaves out the sixteenth K-slice plane of dy
 #define G4R_MUT_PLANES(nsl) min((nsl), 15)
@@ -244,6 +251,11 @@ struct DevModel {
     // step (g4r_loss_kernel.cuh).  The ring sits behind k_update_l's dense-tile table.  Null: no owner table (G4R_OWNER_SCAN=1, or no
     // k_update_l): every owner scans occ_idx itself.
     GP(int) own_pos;
+    // per-position entries of the window form: a second ring of G4R_OWN_SLOTS tables of [(R + 3) & ~3] int4 next to own_pos, slot s,
+    // position k = (last + 1, R - first, count, 0) of the item at position k over its table -- the value occ_fl[table][item] has once
+    // the forward kernels of that step have published it; zeros where the position holds no item.  k_owner_window writes it; the
+    // step's kernels then take the entry by position and nobody touches occ_fl.  Null: the entries are built inside every step.
+    GP(int) pos_ent;
 };
 // step plane of global step g
 #define G4R_SLOT(m, g) ((size_t)((g) & (long long)(m).defer_mask))

@@ -99,6 +99,20 @@ static int build_lean_args(g4r_model* m) {
         // workgroups; G4R_OWNER_WINDOW=1 asks for it at any length the LDS holds
         const bool pays = cdiv(d.R, LOSS_NW) > G4R_OWN_WINDOW_MINWG;
         m->own_window = d.own_pos && d.R <= G4R_OWN_WINDOW_MAXR && (m->sw.owner_window > 0 || (m->sw.owner_window < 0 && pays));
+        // The window launch also writes every step's (last + 1, R - first, count) entries by position (DevModel::pos_ent; the ring sits
+        // next to the owner ring), where every kernel that publishes or reads them is a lean one and the hash of k_owner_window -- a power of
+        // two of slots >= 1.5 R, 16 bytes each -- fits its LDS next to the ids (R <= 5461).  Else, and with G4R_POS_ENTRIES=0, the
+        // entries are built inside every step as before (debug key `pos_entries`).
+        int hs = 64;
+        while (hs < d.R + d.R / 2) hs *= 2;
+        const bool all_lean = k.fwd[0] == FWD_LEAN && k.bwd[0] == BWD_LEAN && k.score_fwd == SF_LEAN && k.score_bwd == SB_LEAN;
+        m->pos_entries = m->own_window && m->sw.pos_entries && all_lean && d.xmode == 0 && hs <= G4R_POS_ENT_MAXHS;
+        if (m->pos_entries) {
+            m->pos_hs = hs;
+            int4* ring = nullptr;
+            if (dalloc(m, &ring, (size_t)G4R_OWN_SLOTS * (size_t)((d.R + 3) & ~3))) return -1;
+            d.pos_ent = (int*)ring;
+        }
         HIPCHK(hipMemcpyAsync(m->d_tiles16, tiles.data(), tiles.size() * sizeof(DenseTile), hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipStreamSynchronize(m->stream));      // (before `tiles` goes out of scope)
     }
@@ -111,7 +125,7 @@ static KernelSwitches read_switches(const g4r_config& cfg) {
     KernelSwitches w;
     w.no_lean = getenv("G4R_NO_LEAN") != nullptr; w.no_mt = getenv("G4R_NO_MT") != nullptr; w.no_bmt = getenv("G4R_NO_BMT") != nullptr;
     w.no_merge = getenv("G4R_NO_MERGE") != nullptr; w.owner_scan_in_update = env_int("G4R_OWNER_SCAN", 0) != 0;
-    w.owner_window = env_int("G4R_OWNER_WINDOW", -1);
+    w.owner_window = env_int("G4R_OWNER_WINDOW", -1); w.pos_entries = env_int("G4R_POS_ENTRIES", 1) != 0;
     w.score_b_split = env_int("G4R_SCORE_B_SPLIT", 1) != 0;
     w.allow_lean_update = env_int("G4R_LEAN_UPDATE", 1) != 0; w.defer = env_int("G4R_DEFER", cfg.defer_updates) != 0;
     w.p2_geo = env_int("G4R_P2_GEO", -1); w.ba_geo = env_int("G4R_BA_GEO", -1);
@@ -324,7 +338,7 @@ int g4r_create(const g4r_config* cfg, g4r_model** out) {
         (const void*)k_score_bwd_n, (const void*)k_gru_bwd_fused, (const void*)k_gru_fwd_fused, (const void*)k_score_bwd_w, (const void*)k_score_bwd2,
         (const void*)k_gru_bwd_a_w4, (const void*)k_gru_bwd_a_w8d, (const void*)k_gru_bwd_b, (const void*)k_dense_grad<32>,
         (const void*)k_score_store, (const void*)k_score_count, (const void*)k_sim_range<false>, (const void*)k_sim_range<true>,
-        (const void*)k_mmr_rerank<false>, (const void*)k_mmr_rerank<true>, (const void*)k_ivf_assign,
+        (const void*)k_mmr_rerank<false>, (const void*)k_mmr_rerank<true>, (const void*)k_ivf_assign, (const void*)k_owner_window,
 #define TK_PTR(name, ...) (const void*)name,
 #define SCAN_PTR(NCH, E) (const void*)k_scan_bf16<NCH, E>,
 #define IVF_PTR(NCH) (const void*)k_ivf_scan<NCH>,

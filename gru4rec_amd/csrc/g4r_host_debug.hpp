@@ -77,6 +77,11 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
     // every table of the owner ring ([G4R_OWN_SLOTS][R][16]): slot i = step i of the last window (k_owner_window); without it only slot 0 is written
     else if (s == "own_pos_ring") { if (!d.own_pos) return fail("no owner table (k_update_l not chosen, or G4R_OWNER_SCAN=1)"); p = (const float*)d.own_pos; n = (int64_t)G4R_OWN_SLOTS * 16 * d.R; }
     else if (s == "owner_window") { if (count < 1) return fail("count"); host[0] = (m->own_window && k.update == UP_LEAN) ? 1.f : 0.f; return 0; }      // 1: k_owner_window writes the owner tables of a window of steps ahead of them; 0: the pre-scan in k_loss_rows (G4R_OWNER_WINDOW=0, R > G4R_OWN_WINDOW_MAXR, R <= 16 G4R_OWN_WINDOW_MINWG), or no table
+    // 1: k_owner_window also writes every step's (last + 1, R - first, count) entries by position and the step's kernels take them from there;
+    // 0: the entries are built inside every step (G4R_POS_ENTRIES=0, no window launch, a kernel of the step that is not a lean one, R > 5461)
+    else if (s == "pos_entries") { if (count < 1) return fail("count"); host[0] = m->pos_entries ? 1.f : 0.f; return 0; }
+    // the entry ring (ints, [G4R_OWN_SLOTS][(R + 3) & ~3][4]): slot i = step i of the last window
+    else if (s == "pos_entries_ring") { if (!d.pos_ent) return fail("no per-position entries (debug key pos_entries)"); p = (const float*)d.pos_ent; n = (int64_t)G4R_OWN_SLOTS * 4 * ((d.R + 3) & ~3); }
 #if !defined(G4R_CLK_TRACE)
     else if (s == "dbgclk" || s == "dbgtile") return fail("in-kernel traces need a library built with G4R_BUILD_CLK=1 (python -m gru4rec_amd.build --force) and G4R_CLK=1 at run time");
 #endif

@@ -42,6 +42,7 @@ struct KernelSwitches {
     bool score_b_split = true;            // G4R_SCORE_B_SPLIT=0: k_score_b keeps its role A (the item-gradient tiles), no hosting in k_gru_dy
     bool owner_scan_in_update = false;    // G4R_OWNER_SCAN=1: k_update_l's owners of repeated items scan occ_idx themselves (no pre-scan in k_loss_rows)
     int owner_window = -1;                // G4R_OWNER_WINDOW=0: the owner tables come from the pre-scan in k_loss_rows, every step, not from k_owner_window once per window; 1: from k_owner_window wherever its LDS holds the list; unset: where that pays (g4r_host_create.hpp)
+    bool pos_entries = true;              // G4R_POS_ENTRIES=0: the (last, first, count) entries are built inside every step (atomics in k_gru_v / k_score_s, occ_fl), also where k_owner_window could write them per position
     bool defer = false;                   // G4R_DEFER (default: g4r_config::defer_updates)
     int p2_geo = -1, ba_geo = -1;         // G4R_P2_GEO / G4R_BA_GEO = 0 / 1: the 4-wave / 8-wave geometry of k_gru_p2 / k_gru_bwd_a (-1: the policy)
     int wide2 = -1, p1_ks = 128, bb_ks = 0;      // G4R_WIDE2 (wide-layer kernel mask, -1: the policy), G4R_P1_KS / G4R_BB_KS (their K slices)
@@ -148,6 +149,8 @@ struct g4r_model {
     DenseTile* d_tiles16 = nullptr; int ntiles16 = 0;
     bool own_window = false;     // k_owner_window writes the owner tables of a window of steps ahead of them (debug key `owner_window`)
     int own_last = 0;            // ring slot of the last step run (debug key `own_pos`)
+    bool pos_entries = false;    // k_owner_window also writes the steps' per-position entries (DevModel::pos_ent; debug key `pos_entries`)
+    int pos_hs = 0;              // hash slots of that form in k_owner_window's LDS
     hipEvent_t ev_ow[2] = {nullptr, nullptr};      // profiling: the window launch
     LeanV* d_leanV = nullptr; LeanH* d_leanH = nullptr; LeanDa* d_leanDa = nullptr; LeanDy* d_leanDy = nullptr;      // [layers] argument blocks (g4r_lean_kernels.cuh)
     hipGraphExec_t gexec = nullptr;
@@ -342,6 +345,16 @@ static inline bool dist_graph_wanted(const g4r_model* m) {
 static inline StepMode step_mode(const g4r_model* m) {
     if (!m->cfg.use_graph || m->profiling || m->sw.trace) return STEP_EAGER;
     return (m->dm.apply_dense_inplace || dist_graph_wanted(m)) ? STEP_GRAPH : STEP_HEAD_GRAPH;
+}
+// The one place that says whether a step's owner tables came from a window launch (k_owner_window in front of the step's window:
+// StepWindow::open) -- and whether its per-position entries did: StepWindow and every launch of the step ask here.  False (per-kernel
+// profiling with the split update, G4R_OWNER_WINDOW=0 / G4R_POS_ENTRIES=0, lists past the caps): every kernel gets the null slot and
+// the entries are built and taken back inside the step, through occ_fl.
+static inline bool window_tables(const g4r_model* m) { return m->own_window && m->kern.update == UP_LEAN && !(m->profiling && m->profile_split); }
+static inline bool window_entries(const g4r_model* m) { return m->pos_entries && window_tables(m); }
+// slot `slot` of the entry ring (the step's index in its window), or null
+static inline const int4* step_entries(const g4r_model* m, int slot) {
+    return window_entries(m) ? (const int4*)m->dm.pos_ent + (size_t)slot * (size_t)((m->dm.R + 3) & ~3) : nullptr;
 }
 // the steps a run leaves behind its replays (fewer than the shortest graph holds): on the staged dense path the head graph + eager
 // tail, else eager launches

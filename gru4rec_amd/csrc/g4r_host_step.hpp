@@ -53,7 +53,8 @@ static void launch_loss_rows(StepLauncher& lk, dim3 grid) {
 static inline bool update_merged(const g4r_model* m, const StepLauncher& lk) { return m->kern.update != UP_SPLIT && !(lk.recs && m->profile_split); }
 
 // ---- the phases of the head, each a straight sequence over m->kern (choose_kernels)
-static void gru_forward(g4r_model* m, StepLauncher& lk, int l) {
+// ent: the step's slot of the entry ring where its per-position entries came from the window launch, else null (step_entries)
+static void gru_forward(g4r_model* m, StepLauncher& lk, int l, const int4* ent) {
     const DevModel& d = m->dm;
     const StepKernels& k = m->kern;
     const int B = d.B, first = l == 0 ? 1 : 0;
@@ -66,7 +67,7 @@ static void gru_forward(g4r_model* m, StepLauncher& lk, int l) {
         const LeanH& h = m->h_leanH[l];
         const auto kv = l > 0 ? k_gru_v<false, false> : (d.drop_e > 0.f ? k_gru_v<true, true> : k_gru_v<true, false>);
         lk.open(KN_GRU_V);
-        lk.launch(kv, dim3(g.x, g.y, 3), dim3(512), 0, m->d_leanV + l, v.st, v.cur_in, v.Wx, v.Wrz, v.H0, v.H1, (unsigned)d.D[l] | ((unsigned)d.IN[l] << 16), B);
+        lk.launch(kv, dim3(g.x, g.y, 3), dim3(512), 0, m->d_leanV + l, v.st, v.cur_in, v.Wx, v.Wrz, v.H0, v.H1, (unsigned)d.D[l] | ((unsigned)d.IN[l] << 16), B, l == 0 ? ent : nullptr);
         lk.close();
         lk.open(KN_GRU_H);
         lk.launch(k_gru_h, g, dim3(512), 0, m->d_leanH + l, h.Wh, h.Hr, h.Vc, h.z, h.cur_rst, h.H0, h.H1, d.D[l], B);
@@ -96,7 +97,7 @@ static void gru_forward(g4r_model* m, StepLauncher& lk, int l) {
     lk.close();
 }
 
-static void score_forward_and_loss(g4r_model* m, StepLauncher& lk) {
+static void score_forward_and_loss(g4r_model* m, StepLauncher& lk, const int4* ent) {
     const DevModel& d = m->dm;
     const StepKernels& k = m->kern;
     const int L = d.n_layers, B = d.B;
@@ -107,7 +108,7 @@ static void score_forward_and_loss(g4r_model* m, StepLauncher& lk) {
     switch (k.score_fwd) {
     case SF_LEAN:
         lk.launch(d.logq != 0.f ? k_score_s<true> : k_score_s<false>, dim3(cdiv(d.ldSc, 32), cdiv(B, 32)), dim3(256), 0, m->d_leanS, meta, d.cur_col, d.hd[L - 1], d.Wy,
-                  d.By, d.Sc, (unsigned)d.Dtop | ((unsigned)B << 16), (unsigned)d.N | ((unsigned)d.ldSc << 16));
+                  d.By, d.Sc, (unsigned)d.Dtop | ((unsigned)B << 16), (unsigned)d.N | ((unsigned)d.ldSc << 16), ent);
         break;
     case SF_MT:
         lk.launch(k_score_mt_4s, dim3(cdiv(B, 64) * cdiv(d.ldSc, 272)), dim3(256), SMEM_MT_4S, d.cur_col, meta, d.hd[L - 1], d.Wy, d.zrow, dmp,
@@ -123,7 +124,7 @@ static void score_forward_and_loss(g4r_model* m, StepLauncher& lk) {
     // a step that ends in k_update_l and whose owner table no window launch has written: up to one more workgroup per idle CU, the
     // owner pre-scan of its repeated items (g4r_loss_kernel.cuh)
     const int nown = std::min(cdiv(d.R, LOSS_NW), std::max(2 * m->n_cu - B, 32));
-    launch_loss_rows(lk, dim3(B + (update_merged(m, lk) && k.update == UP_LEAN && d.own_pos && !m->own_window ? nown : 0)));
+    launch_loss_rows(lk, dim3(B + (k.update == UP_LEAN && d.own_pos && !window_tables(m) ? nown : 0)));
     lk.close();
 }
 
@@ -131,7 +132,7 @@ static void score_forward_and_loss(g4r_model* m, StepLauncher& lk) {
 // the update in two launches: the moved form (role A in the top layer's k_gru_dy launch) is what graph replay and plain eager steps run
 static inline bool score_a_hosted(const g4r_model* m, const StepLauncher& lk) { return m->kern.score_a_host && !lk.recs; }
 
-static void score_backward(g4r_model* m, StepLauncher& lk) {
+static void score_backward(g4r_model* m, StepLauncher& lk, const int4* ent) {
     const DevModel& d = m->dm;
     const StepKernels& k = m->kern;
     const int L = d.n_layers, B = d.B;
@@ -145,7 +146,7 @@ static void score_backward(g4r_model* m, StepLauncher& lk) {
         const LeanB& q = m->h_leanB;
         const bool hosted = score_a_hosted(m, lk);      // role B alone: role A rides in the top layer's k_gru_dy launch (gru_backward)
         lk.launch(hosted ? k_score_b<false> : k_score_b<true>, dim3((hosted ? 0 : q.nA) + d.ksplit * q.nrb * q.ndb), dim3(512), 0, m->d_leanB, meta, d.cur_col, d.Sc,
-                  d.hd[L - 1], d.Wy, d.accWy, (unsigned)d.Dtop | ((unsigned)B << 16), dimsN);
+                  d.hd[L - 1], d.Wy, d.accWy, (unsigned)d.Dtop | ((unsigned)B << 16), dimsN, ent);
         break;
     }
     case SB_BMT:
@@ -164,7 +165,7 @@ static void score_backward(g4r_model* m, StepLauncher& lk) {
     lk.close();
 }
 
-static void gru_backward(g4r_model* m, StepLauncher& lk, int l) {
+static void gru_backward(g4r_model* m, StepLauncher& lk, int l, const int4* ent) {
     const DevModel& d = m->dm;
     const StepKernels& k = m->kern;
     const int L = d.n_layers, B = d.B;
@@ -185,8 +186,8 @@ static void gru_backward(g4r_model* m, StepLauncher& lk, int l) {
             // independent -- single-occurrence accumulator rows, no buffer one writes and the other reads -- is written there)
             const LeanB& b = m->h_leanB;
             lk.launch(k_gru_dy_a, dim3(gx, nrb + cdiv(cdiv(b.nA, 2), gx)), dim3(1024), 0, m->d_leanDy + l, meta, y.occ_idx, y.dV, y.drp, y.Wx, y.r, dims, B, m->d_leanB, d.cur_col,
-                      d.Sc, d.hd[L - 1], d.accWy, (unsigned)d.Dtop | ((unsigned)B << 16), (unsigned)d.N | ((unsigned)d.ldSc << 16), (unsigned)b.nA | ((unsigned)b.ndh << 16));
-        } else lk.launch(k_gru_dy, dim3(gx, nrb), dim3(1024), 0, m->d_leanDy + l, meta, y.occ_idx, y.dV, y.drp, y.Wx, y.r, dims, B);
+                      d.Sc, d.hd[L - 1], d.accWy, (unsigned)d.Dtop | ((unsigned)B << 16), (unsigned)d.N | ((unsigned)d.ldSc << 16), (unsigned)b.nA | ((unsigned)b.ndh << 16), ent, l == 0 ? ent : nullptr);
+        } else lk.launch(k_gru_dy, dim3(gx, nrb), dim3(1024), 0, m->d_leanDy + l, meta, y.occ_idx, y.dV, y.drp, y.Wx, y.r, dims, B, l == 0 ? ent : nullptr);
         lk.close();
         return;
     }
@@ -221,6 +222,20 @@ static void gru_backward(g4r_model* m, StepLauncher& lk, int l) {
 // (step_tail).  Else a launch of their own.
 // (the dense-gradient tiles on a BRANCH of the step graph next to the sparse rows -- they share nothing -- were measured: the
 // fork / join costs more than running them side by side gives, 126.6 -> 139.8 us per step at configs[2]; profiles/r05_experiments.md #8)
+// k_update_l.  roles 0: the whole launch (bookkeeping, dense tiles, row workgroups); under g4r_profile(m, 2) its two halves as launches of
+// their own -- 1: the dense tiles, 2: bookkeeping + row workgroups -- the same workgroups running the same code on the same operands, so
+// a profiled step leaves the bits of an unprofiled one (the grid's block ranges are arguments: a half passes 0 for the ranges it leaves out).
+// The step's owner table: its slot of the ring where a window launch wrote it, else slot 0 (the pre-scan in k_loss_rows).
+static void launch_update_l(g4r_model* m, StepLauncher& lk, int slot, int roles) {
+    const DevModel& d = m->dm;
+    const int nb8 = cdiv(d.R, 8);
+    const unsigned nbk = roles == 1 ? 0u : 1u + (unsigned)cdiv(d.ldSc, 512);
+    const unsigned ntiles = roles == 2 ? 0u : (unsigned)m->ntiles16, nrow = roles == 1 ? 0u : (unsigned)nb8;
+    const int* opos = (const int*)(m->d_tiles16 + m->ntiles16) + (window_tables(m) ? (size_t)slot * d.R * 16 : (size_t)0);
+    lk.launch(d.mom > 0.f ? k_update_l<true> : k_update_l<false>, dim3(nbk + ntiles + nrow), dim3(512), 0, m->d_leanU, m->d_tiles16, d.occ_idx, d.occ_fl, d.dSx, d.dSy, d.dSBy,
+              opos, ntiles | ((unsigned)nb8 << 16), (unsigned)d.R | ((unsigned)d.B << 16), nbk, step_entries(m, slot));
+}
+
 static void dense_gradients(g4r_model* m, StepLauncher& lk, int slot) {
     const DevModel& d = m->dm;
     const StepKernels& k = m->kern;
@@ -231,7 +246,8 @@ static void dense_gradients(g4r_model* m, StepLauncher& lk, int slot) {
     const bool mo = d.mom > 0.f;
     if (!update_merged(m, lk)) {
         lk.open(KN_DENSE);
-        if (k.wide_dense) lk.launch(k_dense_grad2, dim3(m->ntiles64 + (d.bbn[0] > 0 ? gfin.x : 0)), dim3(256), SMEM_T2K, dmp, stp, m->d_tiles64, m->ntiles64);
+        if (k.update == UP_LEAN) launch_update_l(m, lk, slot, 1);      // (its other half: step_tail)
+        else if (k.wide_dense) lk.launch(k_dense_grad2, dim3(m->ntiles64 + (d.bbn[0] > 0 ? gfin.x : 0)), dim3(256), SMEM_T2K, dmp, stp, m->d_tiles64, m->ntiles64);
         else {
             if (k.finish_rows) lk.launch(k_finish_rows, gfin, dim3(256), 0, dmp, stp);
             lk.launch(k_dense_grad<32>, dim3(m->ntiles), dim3(GT_NTH_FEW), SMEM_TN, dmp, stp, m->d_tiles);
@@ -245,14 +261,8 @@ static void dense_gradients(g4r_model* m, StepLauncher& lk, int slot) {
         lk.close();
     }
     lk.open(KN_UPDATE);
-    if (k.update == UP_LEAN) {
-        const int nb8 = cdiv(d.R, 8);
-        const unsigned nbk = 1u + (unsigned)cdiv(d.ldSc, 512);
-        // this step's table of the owner ring (behind the dense tiles; slot 0 without a window launch, the ring's base when there is no table)
-        const int* opos = (const int*)(m->d_tiles16 + m->ntiles16) + (m->own_window ? (size_t)slot * d.R * 16 : (size_t)0);
-        lk.launch(mo ? k_update_l<true> : k_update_l<false>, dim3(nbk + m->ntiles16 + nb8), dim3(512), 0, m->d_leanU, m->d_tiles16, d.occ_idx, d.occ_fl, d.dSx, d.dSy, d.dSBy,
-                  opos, (unsigned)m->ntiles16 | ((unsigned)nb8 << 16), (unsigned)d.R | ((unsigned)B << 16), nbk);
-    } else
+    if (k.update == UP_LEAN) launch_update_l(m, lk, slot, 0);
+    else
         lk.launch(K_UPDATE[k.chunks == 1 ? 0 : 1][mo], dim3(m->ntiles + m->nblk_occ + 1), dim3(SP_WAVES * 64), std::max(SMEM_TN, m->smem_sparse), dmp, stp, m->d_tiles,
                   m->ntiles, m->nblk_occ);
     lk.close();
@@ -264,10 +274,11 @@ static void dense_gradients(g4r_model* m, StepLauncher& lk, int slot) {
 // of the owner ring k_owner_window wrote for it (g4r_update_kernels.cuh); 0 where the pre-scan in k_loss_rows writes the table
 static int step_head(g4r_model* m, StepLauncher& lk, int slot) {
     const int L = m->dm.n_layers;
-    for (int l = 0; l < L; ++l) gru_forward(m, lk, l);
-    score_forward_and_loss(m, lk);
-    score_backward(m, lk);
-    for (int l = L - 1; l >= 0; --l) gru_backward(m, lk, l);
+    const int4* ent = step_entries(m, slot);
+    for (int l = 0; l < L; ++l) gru_forward(m, lk, l, ent);
+    score_forward_and_loss(m, lk, ent);
+    score_backward(m, lk, ent);
+    for (int l = L - 1; l >= 0; --l) gru_backward(m, lk, l, ent);
     dense_gradients(m, lk, slot);
     HIPCHK(hipGetLastError());
     return 0;
@@ -333,7 +344,8 @@ static int step_tail(g4r_model* m, StepLauncher& lk) {
         lk.close();
     } else if (!update_merged(m, lk)) {
         lk.open(KN_SPARSE);
-        lk.launch(K_SPARSE_UPDATE[chunk_index(k.chunks)][d.mom > 0.f], dim3(m->nblk_occ + 1), dim3(SP_WAVES * 64), m->smem_sparse, dmp, stp, m->nblk_occ);
+        if (k.update == UP_LEAN) launch_update_l(m, lk, 0, 2);      // (no window launch in front of such a step: slot 0, the null entry slot)
+        else lk.launch(K_SPARSE_UPDATE[chunk_index(k.chunks)][d.mom > 0.f], dim3(m->nblk_occ + 1), dim3(SP_WAVES * 64), m->smem_sparse, dmp, stp, m->nblk_occ);
         lk.close();
     }
     HIPCHK(hipGetLastError());
@@ -441,7 +453,7 @@ struct StepWindow {
     g4r_model* m;
     const bool own_win;
     bool scanned = false;
-    explicit StepWindow(g4r_model* m_) : m(m_), own_win(m_->own_window && m_->kern.update == UP_LEAN && !(m_->profiling && m_->profile_split)) {}
+    explicit StepWindow(g4r_model* m_) : m(m_), own_win(window_tables(m_)) {}
     ~StepWindow() { if (scanned) m->defer_broken = true; }
     bool on() const { return m->defer_on || own_win; }
     // t, g: plan step and global step of the window's first step
@@ -452,7 +464,8 @@ struct StepWindow {
             StepLauncher lk(m, nullptr);      // (G4R_SKIP_KN, tools/kn_cost.py: what the window launch costs a step)
             if (m->profiling) for (auto& e : m->ev_ow) if (!e) (void)hipEventCreate(&e);
             lk.use(KN_OWNER_WINDOW, m->profiling ? m->ev_ow[0] : nullptr, m->profiling ? m->ev_ow[1] : nullptr);
-            lk.launch(k_owner_window, dim3((unsigned)(nw * cdiv(2 * d.B, OW_NW))), dim3(OW_T), (size_t)(((d.R + 3) & ~3) + 16 * OW_NW) * sizeof(int), dmp, t, g, nw);
+            const int hs = window_entries(m) ? m->pos_hs : 0;      // the steps' per-position entries with their owner tables
+            lk.launch(k_owner_window, dim3((unsigned)(nw * cdiv(2 * d.B, OW_NW))), dim3(OW_T), (size_t)(((d.R + 3) & ~3) + 16 * OW_NW + 4 * hs) * sizeof(int), dmp, t, g, nw, hs);
             HIPCHK(hipGetLastError());      // (a refused launch would leave the steps the tables of an older window)
         }
         if (!m->defer_on) return 0;

@@ -177,7 +177,7 @@ __device__ __forceinline__ LeanState lean_state(int4 mt) {
 // back) and the X part of occ_idx / occ_fl; workgroup (0, 0, 0) republishes the step state for the kernels that read StepState::*_b.
 template <bool L0, bool DROPE>
 __global__ __launch_bounds__(512) void k_gru_v(const LeanV* __restrict__ ap, StepState* st_, const int* cur_in_, const float* Wx_, const float* Wrz_,
-                                               const float* H0_, const float* H1_, unsigned dims, unsigned B) {
+                                               const float* H0_, const float* H1_, unsigned dims, unsigned B, const int4* ent_) {
     __shared__ float sJ[4 * 8 * 64];
     const unsigned tid = threadIdx.x, lane = tid & 63, li = lane & 15, lg = lane >> 4;
     const unsigned wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -221,16 +221,24 @@ __global__ __launch_bounds__(512) void k_gru_v(const LeanV* __restrict__ ap, Ste
     // ---- the state is needed from here
     const LeanState sx = lean_state(mt);
     const int M = sx.M;
-    if (a.first && blockIdx.x == 0 && blockIdx.y == 0 && part == 0 && tid == 0) {
-        GAS StepState* sw = (GAS StepState*)st_;
-        sw->t_b = (long long)(((unsigned long long)(unsigned)mt.w) | ((unsigned long long)(unsigned)cur_in[2 * B + 4] << 32));
-        sw->g_b = (long long)(((unsigned long long)(unsigned)mt.x) | ((unsigned long long)(unsigned)mt.y << 32));
-        sw->M_b = M;
-    }
+    // ent_ != null: the step's entries came with the window launch (k_owner_window) -- nothing to publish with atomics, and the plain
+    // stores (the state, occ_idx) go out behind the wave's last use of loaded data (`publish`), where nothing waits for them any more
+    const bool late = ent_ != nullptr;
+    const int th_hi = (a.first && blockIdx.x == 0 && blockIdx.y == 0 && part == 0 && tid == 0) ? cur_in[2 * B + 4] : 0;
+    auto put_state = [&]() {
+        if (a.first && blockIdx.x == 0 && blockIdx.y == 0 && part == 0 && tid == 0) {
+            GAS StepState* sw = (GAS StepState*)st_;
+            sw->t_b = (long long)(((unsigned long long)(unsigned)mt.w) | ((unsigned long long)(unsigned)th_hi << 32));
+            sw->g_b = (long long)(((unsigned long long)(unsigned)mt.x) | ((unsigned long long)(unsigned)mt.y << 32));
+            sw->M_b = M;
+        }
+    };
+    if (!late) put_state();
     const bool rowok = (int)rowA < M, odd = (sx.g & 1u) != 0;
+    const bool pubrow = L0 && blockIdx.x == 0 && part == 0 && wid == 0 && lg == 0 && rowA < B;
     if (L0) {
         if (!rowok) item = -1;
-        if (blockIdx.x == 0 && part == 0 && wid == 0 && lg == 0 && rowA < B) {
+        if (pubrow && !late) {
             a.occ_idx[rowA] = item;
             if (item >= 0 && a.pub_fl) {      // first / last occurrence of the item in this step's gathered-row list (k_update)
                 int* fl = (int*)a.occ_fl + 4 * (size_t)item;
@@ -240,7 +248,12 @@ __global__ __launch_bounds__(512) void k_gru_v(const LeanV* __restrict__ ap, Ste
             }
         }
     }
-    if ((int)m0 >= M) return;
+    auto publish = [&]() {
+        if (!late) return;
+        if (pubrow) a.occ_idx[rowA] = item;
+        put_state();
+    };
+    if ((int)m0 >= M) { publish(); return; }
     LCLK(3);
     float4 ah = odd ? ah1 : ah0;
     const float hep = odd ? he1 : he0;
@@ -273,17 +286,19 @@ __global__ __launch_bounds__(512) void k_gru_v(const LeanV* __restrict__ ap, Ste
     float v = bias;
 #pragma unroll
     for (int w = 0; w < 8; ++w) v += sJ[(wid * 8 + w) * 64 + lane];      // K slices in wave order
-    if (ncol >= D || (int)rowe >= M) return;
-    const unsigned o = 4 * (rowe * D + ncol);
-    if (part == 0) stu(a.Vc, o, v);
-    else if (part == 1) { const float rr = sigmoidf_(v); stu(a.r, o, rr); stu(a.Hr, o, hep * rr); }
-    else stu(a.z, o, sigmoidf_(v));
+    if (ncol < D && (int)rowe < M) {
+        const unsigned o = 4 * (rowe * D + ncol);
+        if (part == 0) stu(a.Vc, o, v);
+        else if (part == 1) { const float rr = sigmoidf_(v); stu(a.r, o, rr); stu(a.Hr, o, hep * rr); }
+        else stu(a.z, o, sigmoidf_(v));
+    }
+    publish();
     LCLK(7);
     LSPAN_END();
 }
 
 // (hipcc emits the device code of a __global__ template only for explicit instantiations)
-#define G4R_LEAN_V_ARGS const LeanV*, StepState*, const int*, const float*, const float*, const float*, const float*, unsigned, unsigned
+#define G4R_LEAN_V_ARGS const LeanV*, StepState*, const int*, const float*, const float*, const float*, const float*, unsigned, unsigned, const int4*
 template __global__ void k_gru_v<true, false>(G4R_LEAN_V_ARGS);
 template __global__ void k_gru_v<true, true>(G4R_LEAN_V_ARGS);
 template __global__ void k_gru_v<false, false>(G4R_LEAN_V_ARGS);
@@ -468,7 +483,7 @@ __global__ __launch_bounds__(128) void k_gru_da(const LeanDa* __restrict__ ap, c
 // Adagrad pieces dSx / dAx (or the accumulator in place for a single-occurrence item), else the lower layer's dh.
 #define LN_PL 8        // partial planes (= ceil(D / 16) <= 8)
 __device__ __forceinline__ void gru_dy_tile(const LeanDy* __restrict__ ap, const int* meta_, const int* occ_idx_, const float* dV_, const float* drp_,
-                                            const float* Wx_, const float* r_, const unsigned dims, const unsigned B, float* sJ) {
+                                            const float* Wx_, const float* r_, const unsigned dims, const unsigned B, float* sJ, const int4* ent_) {
     const unsigned tid = threadIdx.x, lane = tid & 63, li = lane & 15, lg = lane >> 4;
     const unsigned wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned D = dims & 0xFFFFu, IN = dims >> 16, Dq = D >> 2;
@@ -509,7 +524,9 @@ __device__ __forceinline__ void gru_dy_tile(const LeanDy* __restrict__ ap, const
         if (a.layer0 && wid < 4) {      // -> the item's accumulator element, its occurrence count
             const unsigned ic = min((unsigned)max(itm, 0), (unsigned)a.n_items - 1);      // (rows past M hold an old id: clamped, unused)
             a2 = a.accT[(size_t)ic * IN + nc];
-            cnt2 = a.occ_fl[4 * (size_t)ic + 2];
+            // (ent_: the step's entries came with the window launch -- the count sits at the row's position; one load either way)
+            const GAS int* cntp = ent_ ? (const GAS int*)ent_ + 4 * (size_t)min(rowe, B - 1) + 2 : a.occ_fl + 4 * (size_t)ic + 2;
+            cnt2 = *cntp;
         }
         DYCK(2);
         sx = lean_state(mt);
@@ -605,9 +622,9 @@ __device__ __forceinline__ void gru_dy_tile(const LeanDy* __restrict__ ap, const
     LSPAN_END();
 }
 __global__ __launch_bounds__(1024) void k_gru_dy(const LeanDy* __restrict__ ap, const int* meta_, const int* occ_idx_, const float* dV_, const float* drp_,
-                                                 const float* Wx_, const float* r_, unsigned dims, unsigned B) {
+                                                 const float* Wx_, const float* r_, unsigned dims, unsigned B, const int4* ent_) {
     __shared__ float sJ[4 * 16 * 64];
-    gru_dy_tile(ap, meta_, occ_idx_, dV_, drp_, Wx_, r_, dims, B, sJ);
+    gru_dy_tile(ap, meta_, occ_idx_, dV_, drp_, Wx_, r_, dims, B, sJ, ent_);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -619,7 +636,7 @@ __global__ __launch_bounds__(1024) void k_gru_dy(const LeanDy* __restrict__ ap, 
 // Y | samples part of occ_idx / occ_fl.  Replaces k_score_fwd's 64 x 32 LDS-staged tiles there (5.0 -> ~2 us in the step, tools/kn_cost.py).
 template <bool LOGQ>
 __global__ __launch_bounds__(256) void k_score_s(const LeanS* __restrict__ ap, const int* meta_, const int* cur_col_, const float* hd_, const float* Wy_,
-                                                 const float* By_, float* Sc_, unsigned dimsA, unsigned dimsB) {
+                                                 const float* By_, float* Sc_, unsigned dimsA, unsigned dimsB, const int4* ent_) {
     __shared__ f32x4 sJ[4 * 4 * 64];
     const unsigned tid = threadIdx.x, lane = tid & 63, li = lane & 15, lg = lane >> 4;
     const unsigned wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -658,23 +675,27 @@ __global__ __launch_bounds__(256) void k_score_s(const LeanS* __restrict__ ap, c
     LCLK(1);
     const LeanState sx = lean_state(mt);
     const int M = sx.M;
-    if (blockIdx.y == 0 && wid == 0 && lg < 2) {      // lanes (li, 0): column n0 + li; lanes (li, 1): column n0 + 16 + li
+    // ent_ != null: the step's entries came with the window launch (k_owner_window) -- no atomics, and col_item / occ_idx are stored
+    // behind the wave's last use of loaded data (`publish`), where nothing waits for them any more
+    const bool late = ent_ != nullptr;
+    const bool pubcol = blockIdx.y == 0 && wid == 0 && lg < 2 && (lg ? nB : nA) < ldSc;      // lanes (li, 0): column n0 + li; lanes (li, 1): column n0 + 16 + li
+    auto publish = [&](bool fl_too) {
+        if (!pubcol) return;
         const unsigned n = lg ? nB : nA;
         const int item = lg ? it1 : it0;
-        if (n < ldSc) {
-            a.col_item[n] = item;
-            if (n < N) {
-                a.occ_idx[n] = item;
-                if (item >= 0 && a.pub_fl) {
-                    int* fl = (int*)a.occ_fl + 4 * (size_t)item;
-                    atomicMax(fl, (int)(B + n) + 1);
-                    atomicMax(fl + 1, a.R - (int)(B + n));
-                    atomicAdd(fl + 2, 1);
-                }
+        a.col_item[n] = item;
+        if (n < N) {
+            a.occ_idx[n] = item;
+            if (fl_too && item >= 0 && a.pub_fl) {
+                int* fl = (int*)a.occ_fl + 4 * (size_t)item;
+                atomicMax(fl, (int)(B + n) + 1);
+                atomicMax(fl + 1, a.R - (int)(B + n));
+                atomicAdd(fl + 2, 1);
             }
         }
-    }
-    if ((int)m0 >= M) return;
+    };
+    if (!late) publish(true);
+    if ((int)m0 >= M) { if (late) publish(false); return; }
     LCLK(2);
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!(ok0 && (int)(m0 + li) < M)) a00 = z4;
@@ -699,7 +720,6 @@ __global__ __launch_bounds__(256) void k_score_s(const LeanS* __restrict__ ap, c
     LCLK(4);
     f32x4 v = sJ[(wid * 4 + 0) * 64 + lane];      // K quarters in wave order
     v += sJ[(wid * 4 + 1) * 64 + lane]; v += sJ[(wid * 4 + 2) * 64 + lane]; v += sJ[(wid * 4 + 3) * 64 + lane];
-    if (ne >= N) return;
     const unsigned r0 = m0 + 16 * (wid >> 1) + 4 * lg;
     GAS float* Sc = (GAS float*)Sc_;
     float o[4];
@@ -707,12 +727,13 @@ __global__ __launch_bounds__(256) void k_score_s(const LeanS* __restrict__ ap, c
     for (int rg = 0; rg < 4; ++rg) { o[rg] = v[rg] + bias; lean_keep(o[rg]); }      // (complete before the conditional stores: lean_keep)
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg)
-        if ((int)(r0 + rg) < M) stu(Sc, 4 * ((r0 + rg) * ldSc + ne), o[rg]);
+        if (ne < N && (int)(r0 + rg) < M) stu(Sc, 4 * ((r0 + rg) * ldSc + ne), o[rg]);
+    if (late) publish(false);
     LCLK(5);
     LSPAN_END();
 }
-template __global__ void k_score_s<false>(const LeanS*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned);
-template __global__ void k_score_s<true>(const LeanS*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned);
+template __global__ void k_score_s<false>(const LeanS*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned, const int4*);
+template __global__ void k_score_s<true>(const LeanS*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned, const int4*);
 
 // ---------------------------------------------------------------------------------------------
 // Scoring backward of a narrow top layer at RSC15-like sizes (B <= 128, D <= 128), two roles in one launch (block ranges), both on the same
@@ -731,7 +752,7 @@ template __global__ void k_score_s<true>(const LeanS*, const int*, const int*, c
 // computes and leaves without a store.  `lead`: the thread that stamps the tile's row of the span table (trace builds).
 __device__ __forceinline__ void score_b_role_a(const LeanB& a, const int4 mt, const GAS int* cur_col, const GAS float* Sc, const GAS float* hd, float* accWy_,
                                                const unsigned D, const unsigned B, const unsigned N, const unsigned ldSc, const unsigned t, const unsigned ndh,
-                                               const unsigned wid, const unsigned lane, f32x4* sJ, const bool live, const bool lead) {
+                                               const unsigned wid, const unsigned lane, f32x4* sJ, const bool live, const bool lead, const int4* ent_) {
     const unsigned li = lane & 15, lg = lane >> 4;
     LSPAN_BEGIN_AT(a.dbgtile, 2048 + t, lead && live);
     f32x4 acc[4];
@@ -761,7 +782,9 @@ __device__ __forceinline__ void score_b_role_a(const LeanB& a, const int4 mt, co
     // at its join -- the accumulator gather's round trip then sits in front of the MFMAs instead of under them)
     float4 acc4 = ld4((const GAS float*)accWy_ + (size_t)ic * D + min(d4, D - 4));
     const float accb = a.accBy[ic];
-    const int cnt = a.occ_fl[4 * (size_t)ic + 2];
+    // (ent_: the step's entries came with the window launch -- the count sits at the column's position B + n; one load either way, no branch)
+    const GAS int* cntp = ent_ ? (const GAS int*)ent_ + 4 * (size_t)min(B + nc, B + N - 1) + 2 : a.occ_fl + 4 * (size_t)ic + 2;
+    const int cnt = *cntp;
     if (d4 >= D) acc4 = make_float4(accb, 0.f, 0.f, 0.f);
     __builtin_amdgcn_sched_barrier(0);      // (all loads out before the first MFMA)
     const LeanState sx = lean_state(mt);
@@ -866,7 +889,7 @@ __device__ __forceinline__ void score_b_role_b(const LeanB& a, const int4 mt, co
 // the top layer's k_gru_dy launch (k_gru_dy_a below), off the chain k_score_b -> k_gru_da -> k_gru_dy -> k_update_l.
 template <bool ROLE_A>
 __global__ __launch_bounds__(512) void k_score_b(const LeanB* __restrict__ ap, const int* meta_, const int* cur_col_, const float* Sc_, const float* hd_,
-                                                 const float* Wy_, float* accWy_, unsigned dimsA, unsigned dimsB) {
+                                                 const float* Wy_, float* accWy_, unsigned dimsA, unsigned dimsB, const int4* ent_) {
     __shared__ f32x4 sJ[4 * 8 * 64];
     const unsigned tid = threadIdx.x, lane = tid & 63;
     const unsigned wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -876,14 +899,14 @@ __global__ __launch_bounds__(512) void k_score_b(const LeanB* __restrict__ ap, c
     const int4 mt = ldi4((const GAS int*)meta_);
     const LeanB a = *ap;      // (its role-dependent fields are used far below: the compiler's lazy loads cost nothing there)
     if (ROLE_A) {
-        if (blockIdx.x < (unsigned)a.nA) { score_b_role_a(a, mt, cur_col, Sc, hd, accWy_, D, B, N, ldSc, blockIdx.x, (unsigned)a.ndh, wid, lane, sJ, true, tid == 0); return; }
+        if (blockIdx.x < (unsigned)a.nA) { score_b_role_a(a, mt, cur_col, Sc, hd, accWy_, D, B, N, ldSc, blockIdx.x, (unsigned)a.ndh, wid, lane, sJ, true, tid == 0, ent_); return; }
         score_b_role_b(a, mt, cur_col, Sc, Wy_, D, B, ldSc, blockIdx.x - (unsigned)a.nA, wid, lane, sJ);
     } else {
         score_b_role_b(a, mt, cur_col, Sc, Wy_, D, B, ldSc, blockIdx.x, wid, lane, sJ);
     }
 }
-template __global__ void k_score_b<true>(const LeanB*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned);
-template __global__ void k_score_b<false>(const LeanB*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned);
+template __global__ void k_score_b<true>(const LeanB*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned, const int4*);
+template __global__ void k_score_b<false>(const LeanB*, const int*, const int*, const float*, const float*, const float*, float*, unsigned, unsigned, const int4*);
 
 // The top layer's k_gru_dy launch with k_score_b's role A behind it: rows [0, ceil(B / 16)) of the grid are k_gru_dy's own workgroups
 // (dispatched first), the rows behind them carry TWO role-A tiles each (waves 0 .. 7 tile 2 h, waves 8 .. 15 tile 2 h + 1, 32 KB of LDS per
@@ -900,10 +923,11 @@ template __global__ void k_score_b<false>(const LeanB*, const int*, const int*, 
 // Two GRU layers: the host is the top layer's launch (the first k_gru_dy of the step); the lower layers' launches are plain k_gru_dy.
 __global__ __launch_bounds__(1024) void k_gru_dy_a(const LeanDy* __restrict__ ap, const int* meta_, const int* occ_idx_, const float* dV_, const float* drp_,
                                                    const float* Wx_, const float* r_, unsigned dims, unsigned B, const LeanB* __restrict__ bp,
-                                                   const int* cur_col_, const float* Sc_, const float* hd_, float* accWy_, unsigned dimsA, unsigned dimsB, unsigned tilesA) {
+                                                   const int* cur_col_, const float* Sc_, const float* hd_, float* accWy_, unsigned dimsA, unsigned dimsB, unsigned tilesA,
+                                                   const int4* ent_, const int4* ent0_) {      // ent_: the step's entries (role A); ent0_: the same where this launch is layer 0's, else null
     __shared__ f32x4 sJ[2 * 4 * 8 * 64];
     const unsigned nrb = (B + 15) >> 4;
-    if (blockIdx.y < nrb) { gru_dy_tile(ap, meta_, occ_idx_, dV_, drp_, Wx_, r_, dims, B, (float*)sJ); return; }
+    if (blockIdx.y < nrb) { gru_dy_tile(ap, meta_, occ_idx_, dV_, drp_, Wx_, r_, dims, B, (float*)sJ, ent0_); return; }
     const unsigned tid = threadIdx.x, lane = tid & 63;
     const unsigned wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned nA = tilesA & 0xFFFFu, half = wid >> 3;
@@ -913,7 +937,7 @@ __global__ __launch_bounds__(1024) void k_gru_dy_a(const LeanDy* __restrict__ ap
     const LeanB a = *bp;
     const bool live = t < nA;
     score_b_role_a(a, mt, (const GAS int*)cur_col_, (const GAS float*)Sc_, (const GAS float*)hd_, accWy_, dimsA & 0xFFFFu, dimsA >> 16, dimsB & 0xFFFFu,
-                   dimsB >> 16, live ? t : nA - 1, tilesA >> 16, wid & 7, lane, sJ + half * (4 * 8 * 64), live, (tid & 511) == 0);
+                   dimsB >> 16, live ? t : nA - 1, tilesA >> 16, wid & 7, lane, sJ + half * (4 * 8 * 64), live, (tid & 511) == 0, ent_);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -936,7 +960,7 @@ __global__ __launch_bounds__(1024) void k_gru_dy_a(const LeanDy* __restrict__ ap
 //     occurrence's value).  Items whose occurrences are all sampled negatives take the (count - 1) x own row shortcut as there.
 template <bool MOM>
 __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* occ_idx, GAS int* occ_fl, const GAS float* dSx, const GAS float* dSy,
-                                                 const GAS float* dSBy, const GAS int* opos_t, unsigned k, unsigned R, unsigned B) {
+                                                 const GAS float* dSBy, const GAS int* opos_t, const GAS int* ent, unsigned k, unsigned R, unsigned B) {
     const unsigned lane = threadIdx.x & 63;
     const bool tableE = k < B && !a.constrained;
     const unsigned W = tableE ? (unsigned)a.wE : (unsigned)a.wY, nc4 = W >> 2;
@@ -946,6 +970,10 @@ __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* 
     // first loads: the occurrence's item, its row of the owner table (lane l < 16: entry l), its step row, its bias step
     int item = ldu_i(occ_idx, 4 * kc);
     const int opos = ldu_i(opos_t, 4 * (16 * kc + min(lane, 15u)));
+    // ent != null: the step's entries came with the window launch (k_owner_window) -- the entry of position k is a first load, a
+    // non-owner ends before the second level, and nobody takes the entry back (occ_fl is not used at all)
+    int4 fl = make_int4(0, 0, 0, 0);
+    if (ent) fl = ldi4(ent + 4 * kc);
     const GAS float* srow = (kc < B) ? dSx + (size_t)kc * W : dSy + (size_t)(kc - B) * W;
     const float4 sk = ld4(srow + 4 * c4);
     const bool bias = k >= B;
@@ -958,7 +986,8 @@ __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* 
     const unsigned ic = (unsigned)max(item, 0);
     // second level: the item's entry, its parameter (velocity) row, its bias state
     GAS int* flp = occ_fl + 4 * ((tableE ? (size_t)a.n_items : 0) + ic);
-    const int4 fl = ldi4(flp);
+    if (ent) { if (!(item >= 0 && fl.x == (int)k + 1)) return; }      // wave-uniform
+    else fl = ldi4(flp);
     const float4 pz = ld4(P + (size_t)ic * W + 4 * c4);
     float4 vz = make_float4(0.f, 0.f, 0.f, 0.f);
     if (MOM) vz = ld4(V + (size_t)ic * W + 4 * c4);
@@ -977,7 +1006,7 @@ __device__ __forceinline__ void lean_rows_update(const LeanU& a, const GAS int* 
         ak = ld4(arow + 4 * c4);
         if (bias) bak = a.dABy[k - B];
     }
-    if (lane == 0) *(GAS int4*)flp = make_int4(0, 0, 0, 0);      // the entry is taken back for the next step
+    if (!ent && lane == 0) *(GAS int4*)flp = make_int4(0, 0, 0, 0);      // the entry is taken back for the next step
     const float lr = a.lr, momc = a.mom, lmbd = a.lmbd;
     const int lo = (a.constrained || k < B) ? 0 : (int)B;
     const int first_j = max(lo, (int)R - fl.y);
@@ -1229,7 +1258,7 @@ __device__ __forceinline__ void lean_bookkeep(const LeanU& a, unsigned part, uns
 template <bool MOM>
 __global__ __launch_bounds__(512) void k_update_l(const LeanU* __restrict__ ap, const DenseTile* __restrict__ tiles_, const int* occ_idx_, int* occ_fl_,
                                                   const float* dSx_, const float* dSy_, const float* dSBy_, const int* opos_, unsigned packA, unsigned packB,
-                                                  unsigned nbk) {
+                                                  unsigned nbk, const int4* ent_) {
     const unsigned ntiles = packA & 0xFFFFu, nblk = packA >> 16, R = packB & 0xFFFFu, B = packB >> 16;
     const LeanU a = *ap;
     LSPAN_BEGIN(a.dbgtile, 2700);
@@ -1241,8 +1270,8 @@ __global__ __launch_bounds__(512) void k_update_l(const LeanU* __restrict__ ap, 
     // (opos_: this step's table of the owner ring, an argument: its rows are requested with the first loads)
     const unsigned q = b - ntiles, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     lean_rows_update<MOM>(a, (const GAS int*)occ_idx_, (GAS int*)occ_fl_, (const GAS float*)dSx_, (const GAS float*)dSy_, (const GAS float*)dSBy_,
-                          (const GAS int*)opos_, wid * nblk + q, R, B);
+                          (const GAS int*)opos_, (const GAS int*)ent_, wid * nblk + q, R, B);
     LSPAN_END();
 }
-template __global__ void k_update_l<false>(const LeanU*, const DenseTile*, const int*, int*, const float*, const float*, const float*, const int*, unsigned, unsigned, unsigned);
-template __global__ void k_update_l<true>(const LeanU*, const DenseTile*, const int*, int*, const float*, const float*, const float*, const int*, unsigned, unsigned, unsigned);
+template __global__ void k_update_l<false>(const LeanU*, const DenseTile*, const int*, int*, const float*, const float*, const float*, const int*, unsigned, unsigned, unsigned, const int4*);
+template __global__ void k_update_l<true>(const LeanU*, const DenseTile*, const int*, int*, const float*, const float*, const float*, const int*, unsigned, unsigned, unsigned, const int4*);

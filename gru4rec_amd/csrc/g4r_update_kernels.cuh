@@ -678,9 +678,14 @@ __global__ __launch_bounds__(256) void k_defer_scan(const DevModel* __restrict__
 #define OW_NW (OW_T / 64)
 static_assert(G4R_OWN_INLINE + 1 == 16, "an owner-table row is 16 ints: the count and G4R_OWN_INLINE positions");
 static_assert(((size_t)G4R_OWN_WINDOW_MAXR + 16 * OW_NW) * sizeof(int) <= 65536, "k_owner_window: the longest list and the waves' position rows share one workgroup's 64 KB of LDS");
-__global__ __launch_bounds__(OW_T) void k_owner_window(const DevModel* __restrict__ mp, long long t0, long long g0, int nw) {
+// Per-position entries (hs > 0: hash slots, a power of two >= 1.5 R; DevModel::pos_ent): the same list gives, for EVERY item of the step --
+// those that occur only among the negatives too --, the (last + 1, R - first, count) the forward kernels would publish to occ_fl with
+// three global atomics per occurrence.  Every workgroup of the step files all R ids in an LDS hash table (key = the id, or -2 - id in
+// the E table of a separate embedding; compare-and-swap on the key, linear probing, then LDS max / max / add: the three results do
+// not depend on the order) and writes the entries of its share of the positions.  No global atomics, no item-indexed table.
+__global__ __launch_bounds__(OW_T) void k_owner_window(const DevModel* __restrict__ mp, long long t0, long long g0, int nw, int hs) {
     const DevModel& m = *mp;
-    extern __shared__ __attribute__((aligned(16))) int sid[];      // [Rp] the step's ids, [OW_NW][16] the waves' first positions
+    extern __shared__ __attribute__((aligned(16))) int sid[];      // [Rp] the step's ids, [OW_NW][16] the waves' first positions, [4][hs] the hash (key | last + 1 | R - first | count)
     const int R = m.R, B = m.B, Rp = (R + 3) & ~3;
     const int gps = (2 * B + OW_NW - 1) / OW_NW;      // workgroups per step
     const int s = (int)blockIdx.x / gps, q = (int)blockIdx.x - s * gps;
@@ -693,7 +698,43 @@ __global__ __launch_bounds__(OW_T) void k_owner_window(const DevModel* __restric
         int table;
         sid[k] = k < R ? defer_item(m, t0 + s, G4R_MUT_WIN_G(g0, s), k, table) : -1;
     }
+    int* hkey = sid + Rp + 16 * OW_NW;
+    for (int i = threadIdx.x; i < 4 * hs; i += OW_T) hkey[i] = i < hs ? -1 : 0;
     __syncthreads();
+    if (hs > 0) {      // (uniform over the launch)
+        const bool one_table = m.embed_mode == G4R_EMBED_CONSTRAINED;
+        int *hlast = hkey + hs, *hfirst = hlast + hs, *hcnt = hfirst + hs;
+        // slot of a key that is in the table, or the free slot it takes (`take`)
+        auto slot_of = [&](int key, bool take) {
+            int h = (int)(((unsigned)key * 2654435761u) >> 8) & (hs - 1);
+            for (int n = 0; n < hs; ++n) {      // (at most R < hs keys: a free slot always ends the walk)
+                const int old = take ? atomicCAS(hkey + h, -1, key) : hkey[h];
+                if (old == key || (take && old == -1)) break;
+                h = (h + 1) & (hs - 1);
+            }
+            return h;
+        };
+        for (int k = threadIdx.x; k < R; k += OW_T) {
+            const int item = sid[k];
+            if (item < 0) continue;
+            const int h = slot_of((one_table || k >= B) ? item : -2 - item, true);
+            atomicMax(hlast + h, k + 1);
+            atomicMax(hfirst + h, R - k);
+            atomicAdd(hcnt + h, 1);
+        }
+        __syncthreads();
+        const int per = (Rp + gps - 1) / gps;      // positions of this workgroup: [q per, (q + 1) per)
+        GAS int4* ent = (GAS int4*)m.pos_ent + (size_t)s * (size_t)Rp;
+        for (int k = q * per + (int)threadIdx.x; k < min((q + 1) * per, Rp); k += OW_T) {
+            const int item = k < R ? sid[k] : -1;
+            int4 e = make_int4(0, 0, 0, 0);
+            if (item >= 0) {
+                const int h = slot_of((one_table || k >= B) ? item : -2 - item, false);
+                e = make_int4(hlast[h], hfirst[h], G4R_MUT_ENT_CNT(hcnt[h], R - hfirst[h] >= 2 * B), 0);
+            }
+            ent[k] = e;
+        }
+    }
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int p = q * OW_NW + wid;
     if (p >= 2 * B) return;
