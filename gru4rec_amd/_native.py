@@ -61,7 +61,7 @@ SYMBOLS = [
     'g4r_get_param', 'g4r_set_popularity', 'g4r_set_sample_store', 'g4r_get_sample_store',
     'g4r_sample_store_rows', 'g4r_build_plan', 'g4r_set_plan', 'g4r_train_steps', 'g4r_get_losses',
     'g4r_synchronize', 'g4r_global_step', 'g4r_refills', 'g4r_set_step_counters', 'g4r_kernel_time', 'g4r_profile', 'g4r_reset_hidden',
-    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_audience_sessions', 'g4r_scan_table_release', 'g4r_ivf_assign', 'g4r_ivf_set', 'g4r_ivf_release', 'g4r_recommend_sessions_ivf', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_set_item_groups', 'g4r_get_item_groups', 'g4r_recommend_sessions_capped', 'g4r_continue_sessions_capped', 'g4r_cap_lists', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_loglik_events', 'g4r_comm_unique_id',
+    'g4r_predict_begin', 'g4r_predict_hidden', 'g4r_predict_step', 'g4r_recommend_step', 'g4r_recommend_step_filtered', 'g4r_recommend_sessions', 'g4r_recommend_step_scan', 'g4r_recommend_sessions_scan', 'g4r_continue_sessions', 'g4r_store_open', 'g4r_store_close', 'g4r_store_push', 'g4r_store_peek', 'g4r_store_read', 'g4r_store_write', 'g4r_beam_sessions', 'g4r_sample_sessions', 'g4r_sample_sessions_lp', 'g4r_session_log_partition', 'g4r_audience_sessions', 'g4r_scan_table_release', 'g4r_ivf_assign', 'g4r_ivf_set', 'g4r_ivf_release', 'g4r_recommend_sessions_ivf', 'g4r_similar_items', 'g4r_diversify_lists', 'g4r_diversify_sessions', 'g4r_set_item_groups', 'g4r_get_item_groups', 'g4r_recommend_sessions_capped', 'g4r_continue_sessions_capped', 'g4r_cap_lists', 'g4r_score_candidates', 'g4r_score_candidates_sessions', 'g4r_rank_targets', 'g4r_evaluate', 'g4r_recommend_events', 'g4r_loglik_events', 'g4r_comm_unique_id',
     'g4r_comm_init', 'g4r_virtual_train_steps', 'g4r_virtual_sync_dense', 'g4r_comm_sync_sparse', 'g4r_sync_set_rule', 'g4r_set_sync_every', 'g4r_comm_min_i64', 'g4r_comm_max_i64', 'g4r_comm_nranks', 'g4r_p2p_enable', 'g4r_p2p_export', 'g4r_p2p_attach', 'g4r_p2p_active', 'g4r_sync_enable', 'g4r_sync_row_floats', 'g4r_sync_export', 'g4r_sync_import', 'g4r_get_debug', 'g4r_debug_loss_rows', 'g4r_debug_gumbel', 'g4r_debug_lse_terms', 'g4r_stress_start', 'g4r_stress_stop', 'g4r_selftest_mfma', 'g4r_bench_rows',
     'g4r_events_load', 'g4r_events_rows', 'g4r_events_items', 'g4r_events_item_bytes', 'g4r_events_time_kind',
     'g4r_events_copy', 'g4r_events_free',
@@ -142,6 +142,12 @@ def lib():
     L.g4r_recommend_sessions_scan.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i64p, i32p, u32p, i32p, f32p,
                                               f32pp]
     L.g4r_continue_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i32, i64p, i32p, u32p, i32p, f32p, f32pp]
+    L.g4r_store_open.argtypes = [vp, i64, i32]
+    L.g4r_store_close.argtypes = [vp]
+    L.g4r_store_push.argtypes = [vp, i64p, i32p, i32p, i32p, i32, i32p, i64, i32, i32, i32, u32p, i32p, f32p, i32p]
+    L.g4r_store_peek.argtypes = [vp, i32p, i32, i32p, i64, i32, i32, i32, u32p, i32p, f32p, i32p]
+    L.g4r_store_read.argtypes = [vp, i32p, i32, f32pp, i32p, i32p, i32p]
+    L.g4r_store_write.argtypes = [vp, i32p, i32, f32pp, i32p, i32p, i32p]
     L.g4r_beam_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i32, i32, i32, i64p, i32p, u32p, i32p, i32p,
                                     f32p, f32p, i32p]
     L.g4r_sample_sessions.argtypes = [vp, i64p, i32p, i32, f32pp, i32p, i64, i32, i32, i64p, i32p, u32p, i32, i32, C.c_float, C.c_uint64, i32,
@@ -572,6 +578,65 @@ class Model:
         else:
             _chk(lib().g4r_recommend_sessions_scan(*head, int(oversample), *tail))
         return (cols, scores, hout) if return_hidden else (cols, scores)
+
+    # -- session store (slot-level; the id map lives in gru4rec_amd/session_store.py)
+    def store_open(self, capacity, seen_cap):
+        _chk(lib().g4r_store_open(self.h, int(capacity), int(seen_cap)))
+
+    def store_close(self):
+        _chk(lib().g4r_store_close(self.h))
+
+    def store_info(self):
+        """(capacity, seen_cap, bytes the slots hold) of the open session store; zeros without one."""
+        a = self.get_debug('session_store', 3)
+        return int(a[0]), int(a[1]), int(a[2])
+
+    def store_push(self, ev_offs, ev_items, slots, fresh, item_idx=None, k=0, exclude_seen=False, excl_mask=None, oversample=None):
+        """The events of n rows through the slots of the session store (g4r_store_push): row r is ev_items[ev_offs[r]:ev_offs[r + 1]]
+        (item indices) of the session in slot slots[r], started from zero with an empty list where fresh[r].  k = 0: returns None;
+        otherwise (cols int32[n, k], scores float32[n, k], overflow int32[n]) after every row's last event, the slot's seen list
+        excluded with exclude_seen.  oversample: as in recommend_step_filtered."""
+        offs, ev, n = _hist(ev_offs, ev_items)
+        sl, fr = np.ascontiguousarray(slots, dtype=np.int32), np.ascontiguousarray(fresh, dtype=np.int32)
+        if len(sl) != n or len(fr) != n:
+            raise ValueError('slots and fresh must hold one entry per row (n)')
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        mask = _mask(excl_mask, self.cfg.n_items)
+        cols, scores = _topk_out((n, k))
+        over = np.zeros(n, dtype=np.int32)
+        _chk(lib().g4r_store_push(self.h, _i64(offs), _i32(ev), _i32(sl), _i32(fr), n, _i32(it), n_sel, int(k), int(oversample or 0),
+                                  int(bool(exclude_seen)), _u32(mask), _i32(cols), _f32(scores), _i32(over)))
+        return (cols, scores, over) if k else None
+
+    def store_peek(self, slots, item_idx=None, k=20, exclude_seen=False, excl_mask=None, oversample=None):
+        """store_push's selection from what the slots hold (g4r_store_peek): nothing is stepped or written."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        it, n_sel = _cand(item_idx, self.cfg.n_items)
+        mask = _mask(excl_mask, self.cfg.n_items)
+        cols, scores = _topk_out((len(sl), k))
+        over = np.zeros(len(sl), dtype=np.int32)
+        _chk(lib().g4r_store_peek(self.h, _i32(sl), len(sl), _i32(it), n_sel, int(k), int(oversample or 0), int(bool(exclude_seen)), _u32(mask),
+                                  _i32(cols), _f32(scores), _i32(over)))
+        return cols, scores, over
+
+    def store_read(self, slots, seen_cap):
+        """The slots' rows (g4r_store_read): (hidden: float32[n, layers[l]] per layer, seen int32[n, seen_cap], len int32[n], flag int32[n])."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(sl)
+        hout, houtp = _hidden_out(n, self.layers, True)
+        seen, ln, fl = np.zeros((n, seen_cap), dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        _chk(lib().g4r_store_read(self.h, _i32(sl), n, houtp, _i32(seen), _i32(ln), _i32(fl)))
+        return hout, seen, ln, fl
+
+    def store_write(self, slots, hidden, seen, ln, flag):
+        """The reverse of store_read (g4r_store_write); seen: int32[n, seen_cap], every row strictly ascending up to its length."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(sl)
+        h0, h0p = _hidden_in(hidden, n, self.layers)
+        seen, ln, fl = (np.ascontiguousarray(a, dtype=np.int32) for a in (seen, ln, flag))
+        if seen.ndim != 2 or seen.shape[0] != n or len(ln) != n or len(fl) != n:
+            raise ValueError('seen must be [n, seen_cap], len and flag [n]')
+        _chk(lib().g4r_store_write(self.h, _i32(sl), n, h0p, _i32(seen), _i32(ln), _i32(fl)))
 
     # -- item index (IVF)
     def ivf_assign(self, centroids):

@@ -78,7 +78,9 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            31: "k_ivf_scan (g4r_recommend_sessions_ivf) does not scan the last block of a list whose length is not a multiple of 32: "
                "the items of that block never become candidates",
            32: "k_owner_window's per-position entries count a repeated item whose occurrences are all sampled negatives one too low: "
-               "its owner adds one step row too few"}
+               "its owner adds one step row too few",
+           33: "k_store_save (g4r_store_push) reads every row's final state from the half the chunk's LONGEST row selects: in a call that "
+               "mixes odd and even event counts, the rows of the other parity store the state BEFORE their last event"}
 
 
 def mutant_path(k):

@@ -16,6 +16,7 @@
 #include "g4r_eval_kernels.cuh"
 #include "g4r_topk_kernels.cuh"
 #include "g4r_rollout_kernels.cuh"
+#include "g4r_store_kernels.cuh"
 #include "g4r_beam_kernels.cuh"
 #include "g4r_cand_kernels.cuh"
 #include "g4r_sample_kernels.cuh"
@@ -41,6 +42,7 @@ extern "C" {
 #include "g4r_host_topk.hpp"
 #include "g4r_host_predict.hpp"
 #include "g4r_host_sessions.hpp"
+#include "g4r_host_store.hpp"
 #include "g4r_host_ivf.hpp"
 #include "g4r_host_beam.hpp"
 #include "g4r_host_sample.hpp"

@@ -48,6 +48,11 @@ int g4r_get_debug(g4r_model* m, const char* name, float* host, int64_t count) {
         host[1] = (m->sim_valid[0] || m->sim_valid[1]) ? 1.f : 0.f; host[2] = (float)m->sim_builds;
         return 0;
     }
+    else if (s == "session_store") {      // the session store: (capacity, seen_cap, bytes its slots hold); all 0 without an open one
+        if (count < 3) return fail("count");
+        host[0] = (float)m->st.capacity; host[1] = (float)m->st.seen_cap; host[2] = (float)m->st.bytes;
+        return 0;
+    }
     else if (s == "continue_steps") {      // g4r_continue_sessions so far: (calls that passed every check, (chunk, step) chains enqueued); a refused call moves neither
         if (count < 2) return fail("count");
         host[0] = (float)m->ro_calls; host[1] = (float)m->ro_steps;

@@ -261,6 +261,19 @@ struct g4r_model {
     DevBuf<ulonglong2> au_ent, au_list[2];
     DevBuf<int> au_state, au_sess;
     DevBuf<float> au_val;
+    // session store (g4r_store_*; g4r_host_store.hpp, g4r_store_kernels.cuh): per layer the slots' hidden rows [capacity][D[l]], the seen
+    // lists [capacity][seen_cap] with their lengths and overflow flags [capacity]; per chunk the rows' slots and fresh marks (chunk
+    // order), the (begin, length) of their lists for TkGrow, their flags, and the staging of g4r_store_read / _write
+    struct SessionStore {
+        bool open = false;
+        int64_t capacity = 0;
+        int seen_cap = 0;
+        size_t bytes = 0;
+        float* H[G4R_MAX_LAYERS] = {nullptr};
+        int *items = nullptr, *len = nullptr, *flag = nullptr;
+        DevBuf<int> slot, fresh, xlen, oflag, io;
+        DevBuf<long long> xbeg;
+    } st;
     unsigned tie_ctr = 0;                      // evaluation step counter of the 'tiebreaking' noise stream
     // the last g4r_recommend_events / g4r_loglik_events call (g4r_get_debug "events_launches"): its steps, the launches whose grid spans the candidate
     // columns, all its launches, the pieces its lists came back in

@@ -59,10 +59,15 @@ static int replay_chunk_rows(int32_t n) {
 // and done(c0, Cc, perm) runs on the host.  Shared by g4r_recommend_sessions, g4r_score_candidates_sessions and g4r_continue_sessions.
 // final_half (g4r_continue_sessions): score() leaves there the ping-pong half that holds EVERY row's final state after its rollout
 // (-1: the replay's own rule, each row's in H[len & 1]).
+// store (g4r_store_push, g4r_host_store.hpp; h0 and out_hidden NULL): the two edges go to the session store instead of the host.  Row i
+// of the call starts from the store row of slot store->slots[i], or from zeros where store->fresh[i] is set (k_store_load), and its
+// final state goes back to that row (k_store_save, k_replay_final's rule).  A chunk's slots and fresh marks lie in st.slot / st.fresh
+// (chunk order) from its begin on, so score() may read them.
+struct StoreEdge { const int32_t* slots; const int32_t* fresh; };
 extern "C++" {      // (this file is included inside extern "C")
 template <class S, class F>
 static int replay_chunks(g4r_model* m, const int64_t* hist_offs, const int32_t* hist_items, int32_t n, int C, const float* const* h0,
-                         float* const* out_hidden, S score, F done, const int* final_half = nullptr) {
+                         float* const* out_hidden, S score, F done, const int* final_half = nullptr, const StoreEdge* store = nullptr) {
     const DevModel& d = m->dm;
     const int L = d.n_layers;
     const GruBufs rb = replay_bufs(m);
@@ -88,7 +93,17 @@ static int replay_chunks(g4r_model* m, const int64_t* hist_offs, const int32_t* 
         HIPCHK(hipMemcpyAsync(m->r_in.p, steps.data(), steps.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipMemcpyAsync(m->r_perm, perm.data(), Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipMemcpyAsync(m->r_len, len.data(), Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
+        if (store) {
+            if (m->st.slot.reserve(m, Cc) || m->st.fresh.reserve(m, Cc)) return -1;
+            HIPCHK(hipMemcpyAsync(m->st.slot.p, store->slots + c0, Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(m->st.fresh.p, store->fresh + c0, Cc * sizeof(int), hipMemcpyHostToDevice, m->stream));
+        }
         for (int l = 0; l < L; ++l) {
+            if (store) {
+                hipLaunchKernelGGL(k_store_load, dim3(cdiv((long long)Cc * d.D[l], 256)), dim3(256), 0, m->stream, m->rH[l][0],
+                                   (const float*)m->st.H[l], (const int*)m->st.slot.p, (const int*)m->st.fresh.p, (const int*)m->r_perm, Cc, d.D[l]);
+                continue;
+            }
             if (h0) HIPCHK(hipMemcpyAsync(m->rio[l], h0[l] + (size_t)c0 * d.D[l], (size_t)Cc * d.D[l] * sizeof(float), hipMemcpyHostToDevice, m->stream));
             hipLaunchKernelGGL(k_replay_begin, dim3(cdiv((long long)Cc * d.D[l], 256)), dim3(256), 0, m->stream, m->rH[l][0],
                                h0 ? (const float*)m->rio[l] : (const float*)nullptr, (const int*)m->r_perm, Cc, d.D[l]);
@@ -101,6 +116,11 @@ static int replay_chunks(g4r_model* m, const int64_t* hist_offs, const int32_t* 
             gru_step(m, rb, t & 1, (const int*)m->r_in.p + (size_t)t * Cc, Mt);
         }
         if (score(c0, Cc, (const std::vector<int>&)perm, (const float*)m->rhout[L - 1])) return -1;
+        if (store)
+            for (int l = 0; l < L; ++l)
+                hipLaunchKernelGGL(k_store_save, dim3(cdiv((long long)Cc * d.D[l], 256)), dim3(256), 0, m->stream, m->st.H[l],
+                                   (const float*)m->rH[l][0], (const float*)m->rH[l][1], (const int*)m->st.slot.p, (const int*)m->r_perm,
+                                   (const int*)m->r_len, Cc, d.D[l], T);
         if (out_hidden)
             for (int l = 0; l < L; ++l) {
                 const int fh = final_half ? *final_half : -1;

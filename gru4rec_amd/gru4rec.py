@@ -205,6 +205,7 @@ class GRU4Rec:
         self.item_groups = None
         self.group_labels = None
         self._model = None
+        self._store = None      # the open session store (open_session_store)
         self._dist = None
         self._cpu_store = False
         self.loss_history = []
@@ -572,6 +573,7 @@ class GRU4Rec:
                                       'order on NumPy\'s global random stream; only the device store (store_type="gpu") resumes')
         self.predict = None
         self.error_during_train = False
+        self._drop_session_store()      # the model is replaced
         self.drop_item_index()      # the item map may change
         item_col = data[self.item_key]
         if eventio.is_categorical(item_col):
@@ -704,6 +706,7 @@ class GRU4Rec:
     def run_epoch(self, epoch, max_steps=None):
         """One pass of the reference's epoch body (gru4rec.py:587-661).  Returns (costs, M per step) or None on NaN."""
         m = self._model
+        self._drop_session_store()      # the weights change
         t0 = time.time()
         plan = self._epoch_plan()
         m.reset_hidden()
@@ -773,6 +776,7 @@ class GRU4Rec:
 
     def close(self):
         """Releases the device model (parameters stay on the host object); the next predict / fit creates a new one."""
+        self._drop_session_store()
         if self._model is not None:
             self._model.close()
             self._model = None
@@ -1331,6 +1335,41 @@ class GRU4Rec:
         if not return_hidden:
             return cand[out[0]], out[1]
         return cand[out[0]], out[1], self._unpad_hidden(out[2])
+
+    # ------------------------------------------------------------------ session store (gru4rec_amd/session_store.py)
+    def _drop_session_store(self):
+        """Every path that drops, replaces or retrains the device model comes through here (prepare -- so fit --, run_epoch, close):
+        an open session store is closed, its states belong to the old weights."""
+        st = getattr(self, '_store', None)
+        if st is not None:
+            st._invalidate()
+        self._store = None
+
+    def open_session_store(self, capacity, seen_cap=64):
+        """Opens the device-resident session store of this model and returns it (a session_store.SessionStore).  Not in the reference.
+        It holds `capacity` sessions: every session's hidden state and its sorted list of seen items (at most seen_cap, an integer in
+        [0, G4R_EXCLUDE_MAX = 1024]; 0: no lists are kept, and exclude_seen=True is refused) stay on the device between calls, so a
+        service pushes a click and receives the next top-k without replaying a history or carrying a state: store.push /
+        store.recommend / store.export / store.load / store.end.  One open store per device model: a second open raises
+        RuntimeError until the first is closed.  The store is bound to the device model: fit, prepare, run_epoch and close close
+        it (its calls then raise RuntimeError), and it is not pickled.  It needs a fitted or loaded model."""
+        from .session_store import SessionStore
+        if getattr(self, 'error_during_train', False):
+            raise Exception
+        if getattr(self, 'itemidmap', None) is None:
+            raise ValueError('open_session_store needs a fitted or loaded model')
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity < 2 ** 31:
+            raise ValueError('capacity = %r: it must be an integer in [1, 2^31 - 1]' % (capacity,))
+        if isinstance(seen_cap, bool) or not isinstance(seen_cap, (int, np.integer)) or not 0 <= seen_cap <= _native.G4R_EXCLUDE_MAX:
+            raise ValueError('seen_cap = %r: it must be an integer in [0, G4R_EXCLUDE_MAX = %d]' % (seen_cap, _native.G4R_EXCLUDE_MAX))
+        st = getattr(self, '_store', None)
+        if st is not None and not st.closed:
+            raise RuntimeError('a session store is open on this model already (one per device model): close it first')
+        m = self._ensure_model()
+        m.store_open(int(capacity), int(seen_cap))
+        self._store = SessionStore(self, m, capacity, seen_cap)
+        self._store._bytes = m.store_info()[2]
+        return self._store
 
     def continue_sessions(self, histories, steps, k=1, no_repeat=True, predict_for_item_ids=None, exclude=None, exclude_per_row=None,
                           hidden=None, return_hidden=False, scan='fp32', oversample=8, max_per_group=None, pool=None, count_history=False,
@@ -2085,7 +2124,7 @@ class GRU4Rec:
 
     def __getstate__(self):
         st = dict(self.__dict__)
-        for k in ('_model', '_plan', '_plan_key', '_data_items', '_offsets', '_base_order', '_dist', '_loss_id', '_final', '_hidden', '_pop64', '_cpu_store', '_seen', '_seen_n', '_seen_over', '_item_index', '_item_index_on'):
+        for k in ('_model', '_plan', '_plan_key', '_data_items', '_offsets', '_base_order', '_dist', '_loss_id', '_final', '_hidden', '_pop64', '_cpu_store', '_seen', '_seen_n', '_seen_over', '_item_index', '_item_index_on', '_store'):
             st.pop(k, None)
         st['predict'] = None
         return st

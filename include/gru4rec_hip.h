@@ -285,6 +285,49 @@ int g4r_continue_sessions(g4r_model* m, const int64_t* hist_offs, const int32_t*
                           const int64_t* excl_offs, const int32_t* excl_items, const uint32_t* excl_mask, int32_t* out_cols,
                           float* out_scores, float* const* out_hidden);
 
+/* not in the reference: a device-resident session store, so that a serving process neither replays a session's history nor carries its
+ * state and seen items between calls.  One store per model.  It holds `capacity` slots; slot s holds one session's hidden state (every
+ * layer; per layer float[capacity][layers[l] padded to 4]), its seen list (at most seen_cap item indices, sorted, duplicate-free), the
+ * list's length and an overflow flag.  The entries are slot-level: which session owns which slot, and which slot is given up when none
+ * is free, is the caller's map (GRU4Rec.open_session_store keeps one in Python).  The store does not watch the weights: a caller that
+ * changes them (g4r_train_steps, g4r_set_param, ...) closes the store, or serves states of the old weights.
+ *   g4r_store_open   1 <= capacity < 2^31, 0 <= seen_cap <= G4R_EXCLUDE_MAX (0: no lists are kept).  Refused while a store is open.  Every
+ *     slot starts at the zero state with an empty list.  A failed allocation frees what it got: the model stays usable, the store closed.
+ *   g4r_store_close  frees the slots (no store open: nothing happens).  g4r_destroy closes it too.
+ *   g4r_get_debug "session_store" -> (capacity, seen_cap, bytes the slots hold); all 0 without an open store.
+ *   g4r_store_push   n rows; row r is the events ev_items[ev_offs[r] .. ev_offs[r + 1]) (item indices, at least one; ev_offs rises
+ *     strictly: the history arguments of g4r_recommend_sessions) of the session in slot slots[r].  slots: distinct, in [0, capacity).
+ *     fresh[r] != 0: the row starts from the zero state, an empty list and a clear flag, whatever the slot held; otherwise from what
+ *     the slot holds.  The events step the row's state exactly as g4r_recommend_sessions steps a history from h0, and the state after
+ *     the last one is written back to the slot.  seen_cap > 0: the row's items are merged into the slot's list in event order -- an
+ *     item already listed is skipped; a full list records nothing further, and a new item then sets the slot's flag.  RULE: the list is
+ *     the first seen_cap distinct items of the session in event order, held sorted; the flag says that the session has shown more.
+ *     k == 0: nothing is selected, out_cols / out_scores are not touched.  1 <= k <= G4R_TOPK_MAX: out_cols / out_scores[n * k] are what
+ *     g4r_recommend_sessions(_scan) returns for the session's whole history from zero, bit for bit (oversample 0: the exact selection,
+ *     >= 1: the two-stage one, as g4r_continue_sessions takes it), with excl_mask and -- exclude_seen != 0 -- the slot's list AFTER this
+ *     call's merge as the row's exclusion list.  exclude_seen needs seen_cap > 0, a duplicate-free item_idx and
+ *     k + seen_cap + (candidate positions the mask takes) <= candidates: the lists live on the device, so every list counts as full
+ *     (a conservative bound).  out_overflow[n] (NULL: not wanted) receives the rows' flags after the merge (0 with seen_cap = 0).
+ *     Everything is checked before any launch and before any slot changes; a refused call changes nothing.  One stream synchronisation
+ *     per chunk of rows.  The prediction state is neither read nor changed.
+ *   g4r_store_peek   the selection of g4r_store_push (k >= 1) from what the slots hold: no events, nothing stepped, nothing written.
+ *   g4r_store_read   rows of the store by slot -> out_hidden (one pointer per layer to float[n][layers[l] padded to 4]), out_seen
+ *     int32[n][seen_cap] (entries from the row's length on are unspecified), out_len[n], out_flag[n]; any of them NULL: not wanted.
+ *   g4r_store_write  the reverse (NULL: that part of the slots stays as it is; seen and len go together).  Refused: a length outside
+ *     [0, seen_cap], a list that is not strictly ascending or holds an item index out of range.
+ * Both take distinct slots in range, any 1 <= n <= capacity. */
+int g4r_store_open(g4r_model* m, int64_t capacity, int32_t seen_cap);
+int g4r_store_close(g4r_model* m);
+int g4r_store_push(g4r_model* m, const int64_t* ev_offs, const int32_t* ev_items, const int32_t* slots, const int32_t* fresh, int32_t n,
+                   const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample, int32_t exclude_seen, const uint32_t* excl_mask,
+                   int32_t* out_cols, float* out_scores, int32_t* out_overflow);
+int g4r_store_peek(g4r_model* m, const int32_t* slots, int32_t n, const int32_t* item_idx, int64_t n_sel, int32_t k, int32_t oversample,
+                   int32_t exclude_seen, const uint32_t* excl_mask, int32_t* out_cols, float* out_scores, int32_t* out_overflow);
+int g4r_store_read(g4r_model* m, const int32_t* slots, int32_t n, float* const* out_hidden, int32_t* out_seen, int32_t* out_len,
+                   int32_t* out_flag);
+int g4r_store_write(g4r_model* m, const int32_t* slots, int32_t n, const float* const* hidden, const int32_t* seen, const int32_t* len,
+                    const int32_t* flag);
+
 /* not in the reference: beam search over the continuations of n whole sessions, stateless.  The arguments of g4r_continue_sessions with
  * k = beams (1 <= beams <= min(candidates, G4R_BEAM_MAX)) plus `combine`.  Step 0 is g4r_recommend_sessions(_scan) of the histories with
  * k = beams: beam i of a session is column i, its path score that column's score.  For s >= 1 every beam's last item is fed to the GRU
