@@ -80,7 +80,10 @@ MUTANTS = {1: 'sparse accumulator increments x 1.01', 2: 'sparse Adagrad steps x
            32: "k_owner_window's per-position entries count a repeated item whose occurrences are all sampled negatives one too low: "
                "its owner adds one step row too few",
            33: "k_store_save (g4r_store_push) reads every row's final state from the half the chunk's LONGEST row selects: in a call that "
-               "mixes odd and even event counts, the rows of the other parity store the state BEFORE their last event"}
+               "mixes odd and even event counts, the rows of the other parity store the state BEFORE their last event",
+           34: "k_score_all (COUNT = false) leaves out the By term in every row tile past the first (rbase > 0): the scores of rows 128 "
+               "onward lose their bias",
+           35: "k_gru_p1 at prediction (train == 0) takes the third K chunk onward as zeros: of K = IN + D only k < 512 contributes"}
 
 
 def mutant_path(k):

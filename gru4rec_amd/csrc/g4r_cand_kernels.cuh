@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void k_score_cand(const DevModel* __restrict__
         }
         if (lg == 0 && g0 + li < w.z) {
             float v = acc[0] + m.By[item];
-            if (apply_act) v = act_fwd(m.final_act, m.fa_p0, m.fa_p1, v);
+            if (apply_act) v = final_act_fwd(m.final_act, m.fa_p0, m.fa_p1, v);
             out[g0 + li] = v;
         }
     }

@@ -444,6 +444,17 @@ __device__ __forceinline__ float act_fwd(int kind, float p0, float p1, float x) 
         default: return x;
     }
 }
+// The FINAL activation of the inference kernels (k_score_all, k_score_cand, the top-k / scan / index tiles: one function, so that their
+// scores stay equal to the bit).  ftanh is good to an ulp of 1.0 (2^-23) whatever its argument: right for a hidden unit, but a score of 0.1
+// is then off by 1e-6 of itself, and a candidate list whose scores are all small has no larger score to measure that against
+// (tests/test_gpu_predict_edges.py, the one-candidate list: 1.24 x its bound).  Below |x| = 0.25 tanh is its odd series up to x^9 (the
+// next term, 8.9e-3 x^11, is under 1e-8 of the result); from there on ftanh's ulp is under 5e-7 of the result.
+__device__ __forceinline__ float final_act_fwd(int kind, float p0, float p1, float x) {
+    if (kind != G4R_ACT_TANH) return act_fwd(kind, p0, p1, x);
+    const float x2 = x * x;
+    const float s = x * (1.0f + x2 * (-0.33333334f + x2 * (0.13333334f + x2 * (-0.053968254f + x2 * 0.021869488f))));
+    return fabsf(x) < 0.25f ? s : ftanh(x);
+}
 // act_fwd's values without a branch around the exponential of elu / selu (element loops of the loss kernel: both sides of that
 // branch run in nearly every wave, the branch only adds its bookkeeping); a NaN input still comes out as NaN
 __device__ __forceinline__ float act_fwd_sel(int kind, float p0, float p1, float x) {

@@ -80,7 +80,11 @@ __global__ __launch_bounds__(256) void k_score_all(const DevModel* __restrict__ 
         for (int cj = 0; cj < CT; ++cj) {
             const long long n = n0 + 16 * cj + li;
             const int item = sItem[16 * cj + li];
+#if defined(G4R_MUTATE) && G4R_MUTATE == 34      // test build: the row tiles past the first 128 rows lose the bias
+            const float add = (item >= 0 && rbase == 0) ? m.By[item] : 0.f;
+#else
             const float add = item >= 0 ? m.By[item] : 0.f;
+#endif
 #pragma unroll
             for (int ri = 0; ri < 2; ++ri)
 #pragma unroll
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(256) void k_score_all(const DevModel* __restrict__ 
                     const int row = rbase + 32 * wid + 16 * ri + 4 * lg + rg;
                     if (row < mrows && n < n_sel) {
                         float v = acc[ri][cj][rg] + add;
-                        if (apply_act) v = act_fwd(m.final_act, m.fa_p0, m.fa_p1, v);
+                        if (apply_act) v = final_act_fwd(m.final_act, m.fa_p0, m.fa_p1, v);
                         out[(size_t)row * ldo + n] = v;
                     }
                 }
@@ -109,7 +113,7 @@ __global__ __launch_bounds__(256) void k_score_all(const DevModel* __restrict__ 
                 for (int cj = 0; cj < CT; ++cj) {
                     const long long n = n0 + 16 * cj + li;
                     float v = acc[ri][cj][rg] + add[cj];
-                    if (apply_act) v = act_fwd(m.final_act, m.fa_p0, m.fa_p1, v);
+                    if (apply_act) v = final_act_fwd(m.final_act, m.fa_p0, m.fa_p1, v);
                     if (tie_col) v += tie_noise(m.seed, tie_ctr, row, n);
                     const bool in = n < n_sel && n >= col_begin;
                     gt += (in && v > t) ? 1.f : 0.f;

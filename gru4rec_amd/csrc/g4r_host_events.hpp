@@ -202,7 +202,7 @@ int g4r_recommend_events(g4r_model* m, const int32_t* in_idx, const int32_t* out
             const TkEvents ev = {e_ts, m->p_cnt, mode == G4R_RANK_TIEBREAKING ? tie_col : (const int*)nullptr, items ? (long long)Mt : 0LL, (unsigned)t,
                                  seen ? (const int4*)(e_seen + t * B) : (const int4*)nullptr, e_sitems, e_sfirst, e_mask};
             if (!sm) {
-                predict_gru(m, e_in + t * B, Mt);
+                if (predict_gru(m, e_in + t * B, Mt)) return -1;
                 const float* hsrc = (const float*)m->phout[top];
                 hipLaunchKernelGGL(k_score_cand, dim3(Mt), dim3(256), 0, s, (const DevModel*)m->d_dm, hsrc, tgt, (const int4*)e_work, e_ts, 1);
                 if (excl) tk_launch<false, true>(m, s, g, hsrc, Mt, d_items, n_cand, nullptr, 0, k, ev);      // k_topk_rank_x

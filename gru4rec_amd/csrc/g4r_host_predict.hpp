@@ -162,9 +162,19 @@ static void gru_step(g4r_model* m, const GruBufs& b, int par, const int* d_in_id
 
 // one step of the prediction state: the top layer's output is left in phout[n_layers - 1] (shared by predict_forward /
 // g4r_recommend_step)
-static void predict_gru(g4r_model* m, const int* d_in_idx, int mrows) {
+// Rows from mrows on are not stepped and keep their state: gru_step leaves them untouched in the half it writes, where they are as
+// they were two steps ago, so they are carried over from the half it read (a later call with more rows goes on from there)
+static int predict_gru(g4r_model* m, const int* d_in_idx, int mrows) {
+    const DevModel& d = m->dm;
     gru_step(m, predict_bufs(m), m->ppar, d_in_idx, mrows);
+    if (mrows < m->pbatch)
+        for (int l = 0; l < d.n_layers; ++l) {
+            const size_t o = (size_t)mrows * d.D[l];
+            HIPCHK(hipMemcpyAsync(m->pH[l][m->ppar ^ 1] + o, m->pH[l][m->ppar] + o, (size_t)(m->pbatch - mrows) * d.D[l] * sizeof(float),
+                                  hipMemcpyDeviceToDevice, m->stream));
+        }
     m->ppar ^= 1;
+    return 0;
 }
 
 // scores of rows [0, mrows) of hsrc against the candidates -> out (row stride ldo), final activation applied (softmax per row)
@@ -186,7 +196,7 @@ static int predict_forward(g4r_model* m, const int* d_in_idx, int mrows, const i
     const int64_t ldo = stream ? ((mrows + 3) & ~3) : ((n_sel + 3) & ~3LL);
     const int64_t need = stream ? (int64_t)m->pbatch * ((m->pbatch + 3) & ~3) : (int64_t)m->pbatch * ldo;
     if (m->p_scores.reserve(m, need)) return -1;
-    predict_gru(m, d_in_idx, mrows);
+    if (predict_gru(m, d_in_idx, mrows)) return -1;
     const bool sm = is_softmax(d);
     const float* hsrc = (const float*)m->phout[d.n_layers - 1];
     if (stream) {
@@ -219,7 +229,7 @@ static int recommend_run(g4r_model* m, int32_t mrows, const int32_t* item_idx, i
     if (sm) {
         if (predict_forward(m, m->p_in, mrows, d_items, n_sel, nullptr)) return -1;
     } else {
-        predict_gru(m, m->p_in, mrows);
+        if (predict_gru(m, m->p_in, mrows)) return -1;
     }
     if (scan_c > 0) {
         if (topk_select_scan(m, (const float*)m->phout[d.n_layers - 1], mrows, d_items, n_sel, k, scan_c, ex)) return -1;

@@ -441,7 +441,7 @@ int g4r_score_candidates(g4r_model* m, const int32_t* in_idx, int32_t mrows, con
     if (cand_check(m, mrows, cand_offs, cand_items, k, out_scores, out_pos)) return -1;
     int64_t n_sel = 0;
     if (predict_inputs(m, in_idx, mrows, nullptr, &n_sel)) return -1;
-    predict_gru(m, m->p_in, mrows);
+    if (predict_gru(m, m->p_in, mrows)) return -1;
     CandHost hs;
     if (cand_enqueue(m, (const float*)m->phout[m->dm.n_layers - 1], mrows, nullptr, cand_offs, cand_items, k, out_scores, out_pos, hs)) return -1;
     HIPCHK(hipStreamSynchronize(m->stream));

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256) void k_ivf_scan(const DevModel* __restrict__ m
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const int cc = 32 * f + (j & 3) + 8 * (j >> 2) + 4 * half;
-                v[j] = act_fwd(m.final_act, m.fa_p0, m.fa_p1, acc[f][j] + s_by[cc]);
+                v[j] = final_act_fwd(m.final_act, m.fa_p0, m.fa_p1, acc[f][j] + s_by[cc]);
                 any |= !(v[j] < tf);
             }
             if (__any(any)) {

@@ -526,7 +526,7 @@ __global__ __launch_bounds__(256) void k_topk_range(const DevModel* __restrict__
 #pragma unroll
                 for (int ri = 0; ri < 2; ++ri)
 #pragma unroll
-                    for (int rg = 0; rg < 4; ++rg) v[ri][cj][rg] = act_fwd(m.final_act, m.fa_p0, m.fa_p1, acc[ri][cj][rg] + add);
+                    for (int rg = 0; rg < 4; ++rg) v[ri][cj][rg] = final_act_fwd(m.final_act, m.fa_p0, m.fa_p1, acc[ri][cj][rg] + add);
             }
         } else {
 #pragma unroll

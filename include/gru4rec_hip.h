@@ -163,7 +163,8 @@ int g4r_predict_begin(g4r_model* m, int32_t batch);
 /* zero rows where zero_mask[0..n_mask) != 0 (n_mask <= batch of g4r_predict_begin; later rows keep their state), then keep
  * rows in `keep_rows` order (NULL = identity), evaluation.py:134-139, gru4rec.py:712-717 */
 int g4r_predict_hidden(g4r_model* m, const uint8_t* zero_mask, int32_t n_mask, const int32_t* keep_rows, int32_t n_keep);
-/* forward only; scores[m, n_sel] = final_act(h Wy[item_idx]^T + By) (all items if item_idx NULL); out may be NULL */
+/* forward only; scores[m, n_sel] = final_act(h Wy[item_idx]^T + By) (all items if item_idx NULL); out may be NULL.
+ * mrows may be smaller than the batch of g4r_predict_begin: rows from mrows on are not stepped and keep their state */
 int g4r_predict_step(g4r_model* m, const int32_t* in_idx, int32_t mrows, const int32_t* item_idx, int64_t n_sel,
                      float* out_scores);
 /* rank of column target_col[i] of row i among columns [col_begin, n_sel) of the last g4r_predict_step's

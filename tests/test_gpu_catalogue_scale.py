@@ -12,7 +12,10 @@ accumulators with the bounds of test_gpu_parity.compare_params, the dense GRU pa
 the full tables kept its bits (a scatter that wraps or truncates an index would land there; a gather that does would read the
 pattern instead of the oracle's row and the costs would differ).
 
-The ids include the corners: 0, n_items - 1, and the rows on either side of byte offsets 2^31, 2^32 and 2^33 of the table."""
+The ids include the corners: 0, n_items - 1, and the rows on either side of byte offsets 2^31, 2^32 and 2^33 of the table.
+
+After the training comparisons each run takes one prediction step on the full table (predict_begin + predict_step: input items and
+candidates are the planted ids) against the small oracle's predict_step under the renumbering."""
 import numpy as np
 import pytest
 
@@ -111,12 +114,14 @@ def _run(tag, I, B, ns, T, store_rows, D, **kw):
     report('--- catalogue scale %s: %d items x %d, %d touched rows, largest byte offset %.2f GB' % (tag, I, D, n, (I - 1) * row_bytes / 1e9))
     close('loss curve', m.get_losses(0, T), np.array(want), atol=5e-6, rtol=5e-4, errs=errs)
     PR, PA, AR, AA = 1e-3, 1e-4, 2e-4, 1e-5
+    trained = {}      # the device's touched rows of Wy / By after the ten steps (the prediction step below)
 
     def table(name, full0, want_rows, init_rows, acc):
         """touched rows against the oracle; then those rows are put back to their uploaded values and the whole table must equal
         the uploaded image bit for bit (untouched rows kept their bits)."""
         got = m.get_param(name, full0.shape)
-        rows = got[touched].astype(np.float64)
+        trained[name] = got[touched].copy()
+        rows = trained[name].astype(np.float64)
         if acc:
             close_rel('%s %s' % (tag, name), rows, want_rows, AR, AA, errs)
         else:
@@ -145,6 +150,24 @@ def _run(tag, I, B, ns, T, store_rows, D, **kw):
         floor = 4.0 * float(np.spacing(np.float32(np.abs(wantp).max())))
         close_rel('%s d%s' % (tag, nm), m.get_param(nm, shape, 0).astype(np.float64) - w0, wantp - w0, PR, PA, errs, floor)
         close_rel('%s acc_%s' % (tag, nm), m.get_param('acc_' + nm, shape, 0), o.acc[nm][0], AR, AA, errs)
+    # ---- one prediction step on the full table (k_gru_p1's gather of the input rows and k_score_all's of the candidate rows at
+    # train = 0, both with 64-bit row offsets): 64 sessions whose input items are planted rows, the corners first, scored against all
+    # planted ids -- ascending, so the candidate list crosses byte offsets 2^31, 2^32 and 2^33 -- from a zero state.  The small oracle
+    # takes the device's own trained rows and dense parameters (compared above), so that the bound prices this step alone and not ten
+    # training steps before it.  Bound, relative to the largest score: the fp32 oracle is itself up to 5.63e-7 away from the exact scores
+    # at these widths and the device up to 4 x that (tests/test_gpu_predict_edges.py, ORACLE_DIST['widths'] and FACTOR), 5 x 5.63e-7 in
+    # all; a row read from a wrapped or truncated offset is another item's row or the fill pattern, wrong by the size of the score itself
+    pb = 64
+    in_p = touched[rng.randint(0, n, size=pb)]
+    in_p[:nc] = corners
+    o.Wy, o.By = trained['Wy'], trained['By']
+    for nm, shape in (('Wx', (D, 3 * D)), ('Wh', (D, D)), ('Wrz', (D, 2 * D)), ('Bh', (3 * D,))):
+        getattr(o, nm)[0] = m.get_param(nm, shape, 0)
+    want_p, _ = o.predict_step([np.zeros((pb, D), dtype=np.float32)], comp(in_p))
+    m.predict_begin(pb)
+    got_p = m.predict_step(in_p.astype(np.int32), touched.astype(np.int32))
+    assert got_p.shape == want_p.shape == (pb, n)
+    close_rel('%s predict' % tag, got_p, want_p, 0.0, 5 * 5.63e-7, errs)
     m.close()
     assert not errs, errs
 

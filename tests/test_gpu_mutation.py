@@ -26,6 +26,10 @@ mutant; every one of those runs has to come back red, and the tensor it names ha
             of test_gpu_wide_edges.py; the 12-slice case passes
   mutant 30 k_gru_p1s keys its embedding-dropout mask by the k offset inside the K slice -> the two-input-slice case (embedding 144) of
             test_gpu_wide_edges.py; the one-slice case (embedding 80, slice start 0) passes
+  mutant 34 k_score_all leaves out By in the row tiles past the first 128 rows -> the 129-, 130- and 257-row cases of
+            test_gpu_predict_edges.py; its 37- and 128-row cases and test_predict_and_ranks (40 rows) pass
+  mutant 35 k_gru_p1 at prediction takes the third K chunk onward as zeros -> the cases of test_gpu_predict_edges.py with K = IN + D > 512;
+            its K = 400 and K = 340 cases and test_gpu_hidden_act.py::test_predict_step (K <= 512) pass
 
 (Round 2's `atol = 1e-4` on every tensor let an accumulator that is wrong by 100 x pass.)  The same selection runs green on the
 product library in the ordinary suite."""
@@ -235,6 +239,58 @@ def test_mutant_30_turns_the_second_input_slice_red(mutants, tmp_path):
     assert state['loss curve'] and state['in144 dE'], state
     r, state = _child(mutants[30], WIDE + 'test_input_width[80]', str(tmp_path / 'm30b.txt'))
     assert r.returncode == 0, 'mutant 30 on one input slice: rc %d\n%s' % (r.returncode, (r.stdout + r.stderr)[-3000:])
+
+
+EDGES = 'tests/test_gpu_predict_edges.py::'
+
+
+def _edge_children(lib, ids, rep):
+    """Test ids in one child process on library `lib`: (return code, output, {report line name: failed})."""
+    env = dict(os.environ, G4R_LIB=lib, G4R_PARITY_REPORT=rep)
+    r = subprocess.run([sys.executable, '-m', 'pytest'] + list(ids) + ['-q', '-p', 'no:cacheprovider'], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=900)
+    lines = open(rep).read().splitlines() if os.path.exists(rep) else []
+    return r.returncode, (r.stdout + r.stderr)[-3000:], {ln[:28].strip(): ln.rstrip().endswith('FAIL') for ln in lines if 'worst/tol' in ln}
+
+
+def test_mutant_34_turns_the_rows_past_the_first_score_tile_red(mutants, tmp_path):
+    """k_score_all without By in the row tiles past the first: every candidate case of test_gpu_predict_edges.py (130 rows) and the 129-
+    and 257-row cases must fail, on every step; the 128-row case, the width cases (37 rows) and test_predict_and_ranks (40 rows) must
+    pass -- no prediction test before test_gpu_predict_edges.py had a row past the first 128."""
+    acts = ('linear', 'relu', 'tanh', 'elu-0.5', 'softmax', 'softmax_logit')
+    widths = ('d260', 'd320', 'd512_geo0', 'd512_geo1', 'd768', 'd1024')
+    ids = [EDGES + 'test_candidate_lists[%s]' % a for a in acts] + [EDGES + 'test_rows[%d]' % pb for pb in (128, 129, 257)] + \
+          [EDGES + 'test_widths[%s]' % w for w in widths]
+    rc, out, state = _edge_children(mutants[34], ids, str(tmp_path / 'm34a.txt'))
+    assert rc == 1, 'mutant 34 on the prediction edge cases: rc %d\n%s' % (rc, out)
+    for a in acts:
+        assert all(state['c %s s%d' % (a, i)] for i in (0, 3, 5)), (a, state)
+    assert all(state['r %d s%d' % (pb, i)] for pb in (129, 257) for i in range(4)), state
+    assert not any(state['r 128 s%d' % i] for i in range(4)), state
+    assert not any(state['w %s s%d' % (w, i)] for w in widths for i in range(4)), state
+    rc, out, _ = _edge_children(mutants[34], ['tests/test_gpu_parity.py::test_predict_and_ranks'], str(tmp_path / 'm34b.txt'))
+    assert rc == 0, 'mutant 34 on test_predict_and_ranks: rc %d\n%s' % (rc, out)
+
+
+def test_mutant_35_turns_the_third_k_chunk_red(mutants, tmp_path):
+    """k_gru_p1 at prediction without its K chunks from the third on (k >= 512 of K = IN + D adds zeros): the width cases and the two
+    stacks with a 512 layer of test_gpu_predict_edges.py must fail.  Where the lost columns are hidden-state columns only (D <= 512) the
+    first step, from a zero state, still passes and the second fails; at D = 768 and 1024 input columns go as well and the first step
+    fails.  D = 260 is among the failures: its K = 520 leaves 8 hidden columns in a third chunk.  K = 400 (embedding 100 + D 300), the one-hot
+    D = 340 (K = 340) and test_gpu_hidden_act.py::test_predict_step (K <= 512) must pass -- no prediction test before
+    test_gpu_predict_edges.py had a third chunk."""
+    zero_ok = ('w d260', 'w d320', 'w d512_geo0', 'w d512_geo1', 'i s36_512', 'i s512_36')
+    ids = [EDGES + 'test_widths[%s]' % w for w in ('d260', 'd320', 'd512_geo0', 'd512_geo1', 'd768', 'd1024')] + \
+          [EDGES + 'test_input_widths[%s]' % w for w in ('s36_512', 's512_36', 'e100_d300', 'onehot340')]
+    rc, out, state = _edge_children(mutants[35], ids, str(tmp_path / 'm35a.txt'))
+    assert rc == 1, 'mutant 35 on the prediction edge cases: rc %d\n%s' % (rc, out)
+    for tag in zero_ok:
+        assert not state[tag + ' s0'] and state[tag + ' s1'] and state[tag + ' s3'], (tag, state)
+    for tag in ('w d768', 'w d1024'):
+        assert state[tag + ' s0'] and state[tag + ' s1'], (tag, state)
+    assert not any(state['i %s s%d' % (w, i)] for w in ('e100_d300', 'onehot340') for i in range(4)), state
+    rc, out, _ = _edge_children(mutants[35], ['tests/test_gpu_hidden_act.py::test_predict_step'], str(tmp_path / 'm35b.txt'))
+    assert rc == 0, 'mutant 35 on test_gpu_hidden_act.py::test_predict_step: rc %d\n%s' % (rc, out)
 
 
 def test_product_library_is_not_a_mutant():
